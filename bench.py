@@ -2,7 +2,7 @@
 """bench.py - headline benchmark of the VMP hot path on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload gmm|smm|t2|t3] [--scaling weak|strong]
-                    [--n ROWS --d D --k K] [--exchange rccl|peer]
+                    [--n ROWS --d D --k K] [--exchange rccl|peer] [--full] [--dump-outputs DIR]
 
 A "step" is one pass of the hot path over one batch of synthetic Gaussian-mixture data resident in HBM:
   gmm / smm  one VMP iteration (M-step -> E-step -> assign; reference models/gmm.py:258-263, smm.py:232-238).  Default =
@@ -13,8 +13,12 @@ Multi-GPU (one rank per GPU): rows are sharded, ONE exchange of the K-sized stat
   --scaling weak    every rank holds N rows (default; `value` = N x ranks / step time)
   --scaling strong  the N rows are split over the ranks (rows / rank = N / G) - the reference's tf.split of ONE
                     minibatch over its towers (data.py:174-175); `value` = N / step time
-With more than one rank the T1 line carries BOTH: the other mode is measured right after the headline and reported under
-extra.other_scaling.  Prints ONE JSON line on rank 0.
+A plain run sets up, warms up (W steps), times exactly K steps, writes its outputs if asked and prints ONE JSON line on rank 0
+(`ms_per_step` = wall time of the K timed steps / K).  --full adds everything else the line used to carry: CPU baselines, the
+rocprofv3 traffic passes, the noise-tensor forms of T2 / T3, the T3 roofline, the accurate SMM mode, with more than one rank the
+other scaling mode (extra.other_scaling), and on one GPU the T2 / T3 / N=1e7 / forced-dist / shard-size / minibatch measurements.
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (inputs are seeded: the same arguments give the
+same inputs on every run, so two builds can be compared output for output).
 """
 import argparse
 import json
@@ -41,6 +45,37 @@ def synth(N, D, K, seed):
     r0 = np.exp(3.0 * rng.standard_normal((N, K), dtype=np.float32))
     r0 = (r0 / r0.sum(1, keepdims=True)).astype(np.float32)
     return x, r0
+
+
+DUMP_BYTES_PER_ARRAY = 8 << 20      # --dump-outputs: larger outputs are written as a fixed, seeded sample of their rows
+DUMP_BYTES_TOTAL = 64 * 10 ** 6
+
+
+def sample_rows(t, max_bytes=DUMP_BYTES_PER_ARRAY, seed=0):
+    """t itself if it fits in max_bytes, else the rows of a fixed PCG64(seed) sample (sorted, without replacement): the same
+    rows for the same shape on every run and every build"""
+    t = t.detach()
+    n = t.shape[0]
+    row = max(1, t[:1].numel() * 4)
+    keep = max(1, max_bytes // row)
+    if n <= keep:
+        return t
+    idx = np.sort(np.random.Generator(np.random.PCG64(seed)).choice(n, size=keep, replace=False))
+    return t[torch.as_tensor(idx, device=t.device)]
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: every array as <out_dir>/<name>.npy, fp64 kept, everything else as fp32; at most DUMP_BYTES_TOTAL in all"""
+    host = {}
+    for name, a in arrays.items():
+        a = a.detach().cpu() if torch.is_tensor(a) else torch.as_tensor(np.asarray(a))
+        host[name] = a.numpy().astype(np.float64 if a.dtype == torch.float64 else np.float32)
+    total = sum(v.nbytes for v in host.values())
+    if total > DUMP_BYTES_TOTAL:
+        raise RuntimeError('--dump-outputs: %d bytes exceed the %d-byte limit' % (total, DUMP_BYTES_TOTAL))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in host.items():
+        np.save(os.path.join(out_dir, name + '.npy'), a)
 
 
 def cpu_baseline(x, r0, workload, chunk=1 << 15, reps=3):
@@ -167,13 +202,16 @@ def cpu_baseline_t3(K, Ld, S, U, smm=False, Ns=1 << 14, reps=3, tower=1 << 14):
                       % ('smm' if smm else 'gmm', tower, Ns, K, Ld, S, U, reps, cands)}
 
 
-def bench_t2(N, Ld, K, S, steps, warmup, dev, dist=None, world=1, smm=False, cpu=False, tensor_mode=True):
+def bench_t2(N, Ld, K, S, steps, warmup, dev, dist=None, world=1, smm=False, cpu=False, tensor_mode=True, outputs=None,
+             noise_tensor=True):
     """T2: SVAE VMP step without the MLPs - fused E-step forward (log_z, samples, regulariser terms),
     its backward (given decoder-side gradients), categorical sub-sampling, M-step moments and the CVI update.
     The step draws its OWN noise, as sample_x_per_comp does (svae.py:113-114).  Headline (`ms_per_step`): the form SVAETrainer runs
     by default - eps generated inside the forward kernel, fresh key every step; algorithmic bytes 4N(2KSL + 2K + 4L).  Side
     measurement (`noise_tensor`): the same step with a noise TENSOR, its per-step normal_() INSIDE the timed step; 4N(4KSL + 2K + 4L).
-    smm=True: Student-t theta (svae.py:265-322; theta/mu_k, theta/L_k trainable, M-step = N_k only, experiments.py:154-176)."""
+    smm=True: Student-t theta (svae.py:265-322; theta/mu_k, theta/L_k trainable, M-step = N_k only, experiments.py:154-176).
+    noise_tensor=False: the headline form alone (no `noise_tensor` side measurement).
+    outputs (a dict): filled with what the last timed step of the headline form computed (samples of the (N, ...) arrays)."""
     import vmp_for_svae_amd as V
     from vmp_for_svae_amd.models import svae, _mix, _svae_ops
     g = torch.Generator(device=dev).manual_seed(1234)
@@ -197,6 +235,7 @@ def bench_t2(N, Ld, K, S, steps, warmup, dev, dist=None, world=1, smm=False, cpu
         """`warmup` + `steps` self-contained steps; returns (seconds, mean ms of [noise draw, forward, backward])"""
         noise = torch.empty(N, K, Ld, S, device=dev) if mode == 'tensor' else None
         ev = [E() for _ in range(5)]
+        last = {}
 
         def one(i, timed):
             if timed:
@@ -219,6 +258,8 @@ def bench_t2(N, Ld, K, S, steps, warmup, dev, dist=None, world=1, smm=False, cpu
             grads = torch.autograd.grad([x, lz, pt.T_prime], [eta1, eta2d] + phi + th_params, [Gx, Glz, r])
             if timed:
                 ev[4][i].record()
+            if timed and i == steps - 1 and outputs is not None and mode != 'tensor':
+                last.update(x=x, log_z=lz, grads=grads)
             xs = pt.x_samples if pt.x_samples is not None else svae.subsample_x(x, lz, seed=1000 + i, nb_out=1, u='philox' if mode != 'tensor' else None)[:, 0, :].contiguous()
             mom = None if (smm or dist is not None) else pt.mom
             if smm:                                               # svae.m_step_smm: N_k only (svae.py:179-196)
@@ -255,14 +296,21 @@ def bench_t2(N, Ld, K, S, steps, warmup, dev, dist=None, world=1, smm=False, cpu
         torch.cuda.synchronize()
         dt_ = max_over_ranks(dist, time.perf_counter() - t0, dev)
         ms = [float(np.mean([a.elapsed_time(b) for a, b in zip(ev[j], ev[j + 1])])) for j in (0, 1, 3)]
-        del noise
+        if last:
+            outputs.update(x=sample_rows(last['x']), log_z=sample_rows(last['log_z']))
+            for j, gg in enumerate(last['grads']):
+                outputs['grad_%d' % j] = sample_rows(gg)
+            for j, t in enumerate(theta):
+                outputs['theta_%d' % j] = t.detach().clone()
+        del noise, last
         torch.cuda.empty_cache()
         return dt_, ms
 
     dt, (_, f_ms, b_ms) = run('philox')
     if not tensor_mode:                                       # shard-size side measurements: the headline form only
         return {'ms_per_step': dt / steps * 1e3, 'fwd_kernel_ms': f_ms, 'bwd_kernel_ms': b_ms, 'rows': N}
-    dt_n, (rn_ms, fn_ms, bn_ms) = run('tensor')
+    if noise_tensor:
+        dt_n, (rn_ms, fn_ms, bn_ms) = run('tensor')
     alg = 4.0 * N * (2.0 * K * S * Ld + 2 * K + 4 * Ld)          # SURVEY 8d T2 bytes per step, in-kernel generator
     alg_n = 4.0 * N * (4.0 * K * S * Ld + 2 * K + 4 * Ld)        # ... with an injected noise tensor
     fwd_bytes = 4.0 * N * (1.0 * K * S * Ld + 2 * Ld + 2 * K)    # reads eta, writes x + log_z + T'
@@ -285,18 +333,19 @@ def bench_t2(N, Ld, K, S, steps, warmup, dev, dist=None, world=1, smm=False, cpu
            'epilogue': 'sub-sampling draw, r = exp(log_z) and (K = 16, L = 8) the M-step moment partials come out of the forward kernel; reduce + CVI is one launch',
            'fwd_GBps': gb(fwd_bytes, f_ms), 'bwd_GBps': gb(bwd_bytes, b_ms),
            'fwd_frac_hbm': gb(fwd_bytes, f_ms) / HBM_PEAK_GBS, 'bwd_frac_hbm': gb(bwd_bytes, b_ms) / HBM_PEAK_GBS,
-           'noise_tensor': {'ms_per_step': dt_n / steps * 1e3, 'includes': 'the per-step normal_() of the (N,K,L,S) tensor',
-                            'randn_ms': rn_ms, 'fwd_kernel_ms': fn_ms, 'bwd_kernel_ms': bn_ms,
-                            'algorithmic_bytes_per_step': alg_n, 'frac_hbm_whole_step': alg_n / (dt_n / steps) / 1e9 / HBM_PEAK_GBS,
-                            'fwd_frac_hbm': gb(fwd_bytes_n, fn_ms) / HBM_PEAK_GBS, 'bwd_frac_hbm': gb(bwd_bytes, bn_ms) / HBM_PEAK_GBS},
            'config': 'T2 %s-svae-vmp N=%d per GPU, L=%d, K=%d, S=%d (own noise draw, fwd+bwd of the fused E-step, sub-sampling, M-step, CVI)' % ('smm' if smm else 'gmm', N, Ld, K, S)}
+    if noise_tensor:
+        res['noise_tensor'] = {'ms_per_step': dt_n / steps * 1e3, 'includes': 'the per-step normal_() of the (N,K,L,S) tensor',
+                               'randn_ms': rn_ms, 'fwd_kernel_ms': fn_ms, 'bwd_kernel_ms': bn_ms,
+                               'algorithmic_bytes_per_step': alg_n, 'frac_hbm_whole_step': alg_n / (dt_n / steps) / 1e9 / HBM_PEAK_GBS,
+                               'fwd_frac_hbm': gb(fwd_bytes_n, fn_ms) / HBM_PEAK_GBS, 'bwd_frac_hbm': gb(bwd_bytes, bn_ms) / HBM_PEAK_GBS}
     if cpu:
         res['cpu_baseline'] = cpu_baseline_t2(K, Ld, S, smm=smm)
         res['speedup_vs_cpu_baseline'] = res['datapoints_per_sec'] / res['cpu_baseline']['value']
     return res
 
 
-def bench_t3(N, Ld, K, S, U, steps, warmup, dev, chunk, smm=False, cpu=False, randn_mode=True):
+def bench_t3(N, Ld, K, S, U, steps, warmup, dev, chunk, smm=False, cpu=False, randn_mode=True, outputs=None, noise_tensor=True):
     """T3: the full training step of experiments.py:196-267 (encoder / decoder MLP + reconstruction term in the fused
     MFMA kernels; fused E-step kernels; all gradients, TF-Adam, CVI) on synthetic y = GMM data with Dy = L.  Timed with
     eps drawn inside the E-step kernel (the trainer's default, rng='philox') and, next to it, read from a torch.randn
@@ -304,13 +353,13 @@ def bench_t3(N, Ld, K, S, U, steps, warmup, dev, chunk, smm=False, cpu=False, ra
     Every step is also bracketed by HIP events on the launch stream: min / median / max and the FIRST timed step are
     reported, so that a one-off cost that lands in the timed region (allocator growth after empty_cache, a lazily loaded
     code object) shows as one step and not as the rate (round 3's driver run: 118.6 ms/step over 3 steps after 1 warm-up,
-    against 34 ms from every run with more warm-up)."""
+    against 34 ms from every run with more warm-up).  noise_tensor=False: the headline form alone (no `noise_tensor_randn`).
+    outputs (a dict): filled with what the last timed step of the headline form computed (ELBO terms, gradients, parameters)."""
     from vmp_for_svae_amd.models import vae
     from vmp_for_svae_amd.training import SVAETrainer
-    if warmup < 3 or steps < 5:
-        print('bench_t3: warmup %d -> %d, steps %d -> %d (the caching allocator needs 3 steps to reach its steady state)'
-              % (warmup, max(3, warmup), steps, max(5, steps)), file=sys.stderr)
-    warmup, steps = max(3, warmup), max(5, steps)
+    if warmup < 3:
+        print('bench_t3: warmup %d -> 3 (the caching allocator needs 3 steps to reach its steady state)' % warmup, file=sys.stderr)
+    warmup = max(3, warmup)
     x_h, _ = synth(N, Ld, K, seed=7)
     y = torch.as_tensor(x_h).to(dev)
 
@@ -330,6 +379,12 @@ def bench_t3(N, Ld, K, S, U, steps, warmup, dev, chunk, smm=False, cpu=False, ra
         dt_ = time.perf_counter() - t0
         per = [a.elapsed_time(b) for a, b in ev]
         elbo = float(out_['elbo'])
+        if outputs is not None and rng == 'philox':
+            outputs.update({k: out_[k] for k in ('elbo', 'neg_rec_err', 'regulariser')})
+            outputs.update({'grad_' + n_.replace('/', '_'): g for n_, g in out_['grads'].items()})
+            names, params = tr.trainables()
+            outputs.update({'param_' + n_.replace('/', '_'): p_.detach().clone() for n_, p_ in zip(names, params)})
+            outputs.update({'theta_%d' % j: t.detach().clone() for j, t in enumerate(tr.theta)})
         del tr, out_
         torch.cuda.empty_cache()
         return dt_, per, elbo
@@ -337,7 +392,8 @@ def bench_t3(N, Ld, K, S, U, steps, warmup, dev, chunk, smm=False, cpu=False, ra
     dt, per, elbo = timed('philox')
     if not randn_mode:                                        # shard-size side measurements: the headline form only
         return {'ms_per_step': dt / steps * 1e3, 'per_step_ms_median': float(np.median(per)), 'rows': N}
-    dt_p, per_p, _ = timed('torch')
+    if noise_tensor:
+        dt_p, per_p, _ = timed('torch')
     rows = float(N) * K * S
     dec_flop = 3 * 2.0 * rows * (Ld * U + U * U + U * 2 * Ld + Ld * Ld)     # fwd + 2x bwd, useful flops of the decoder
 
@@ -350,13 +406,14 @@ def bench_t3(N, Ld, K, S, U, steps, warmup, dev, chunk, smm=False, cpu=False, ra
     res = {'steps_per_sec': 1.0 / med, 'ms_per_step': med * 1e3, 'ms_per_step_wall_mean': dt / steps * 1e3, 'datapoints_per_sec': N / med,
            'timing': 'median of the per-step HIP-event times over `steps` steps; wall-clock mean beside it',
            'steps': steps, 'warmup': warmup, 'per_step_ms': stats(per),
-           # the same step with a torch.randn noise tensor: the SAME two statistics as the headline (wall-clock mean over the timed
-           # region, per-step HIP-event min / median / max) - compare like with like
-           'noise_tensor_randn': {'ms_per_step': float(np.median(per_p)), 'ms_per_step_wall_mean': dt_p / steps * 1e3, 'per_step_ms': stats(per_p)},
            'elbo_per_datapoint': elbo / N, 'decoder_rows_per_step': rows,
            'decoder_useful_TFLOPs_over_whole_step': dec_flop / med / 1e12,
            'config': 'T3 %s-svae-train N=%d (%s), L=Dy=%d, K=%d, S=%d, U=%d' % (
                'smm' if smm else 'gmm', N, 'one pass' if chunk is None else 'chunks of %d' % chunk, Ld, K, S, U)}
+    if noise_tensor:
+        # the same step with a torch.randn noise tensor: the SAME two statistics as the headline (wall-clock mean over the timed
+        # region, per-step HIP-event min / median / max) - compare like with like
+        res['noise_tensor_randn'] = {'ms_per_step': float(np.median(per_p)), 'ms_per_step_wall_mean': dt_p / steps * 1e3, 'per_step_ms': stats(per_p)}
     if cpu:
         res['cpu_baseline'] = cpu_baseline_t3(K, Ld, S, U, smm=smm)
         res['speedup_vs_cpu_baseline'] = res['datapoints_per_sec'] / res['cpu_baseline']['value']
@@ -664,7 +721,9 @@ def main():
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=200)
     ap.add_argument('--warmup', type=int, default=20)
-    ap.add_argument('--reps', type=int, default=31, help='repetitions of the timed region (gmm / smm); the median is reported')
+    ap.add_argument('--reps', type=int, default=None,
+                    help='repetitions of the timed region (gmm / smm); the median is reported.  Default 1: --steps is the number of timed '
+                         'steps.  The --full side measurements of the T1 loop default to 31')
     ap.add_argument('--workload', default='gmm', choices=['gmm', 'smm', 't2', 't3'])
     ap.add_argument('--scaling', default='weak', choices=['weak', 'strong'])
     ap.add_argument('--exchange', default='auto', choices=['auto', 'rccl', 'peer'],
@@ -681,7 +740,16 @@ def main():
     ap.add_argument('--s', type=int, default=10)
     ap.add_argument('--smm', action='store_true', help='t2 / t3: the Student-t mixture SVAE (BASELINE configs[4]: compute_elbo_smm, trainable theta/mu_k, theta/L_k)')
     ap.add_argument('--u', type=int, default=50)
+    ap.add_argument('--full', action='store_true',
+                    help='also run everything beside the headline: CPU baselines, the rocprofv3 traffic passes, the other scaling mode, '
+                         'the accurate SMM mode, the noise-tensor forms of T2 / T3, the T3 roofline and (gmm / smm, one GPU) the T2 / T3 / '
+                         'N=1e7 / forced-dist / shard-size / minibatch side measurements.  Off: set up, warm up, time the steps, print')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy (fp32 / fp64, "
+                         "at most 64 MB: larger arrays as a fixed, seeded sample of their rows); rank 0's rows in a multi-rank run")
     args = ap.parse_args()
+    reps = max(1, args.reps if args.reps is not None else 1)
+    side_reps = max(1, args.reps if args.reps is not None else 31)
 
     if 'WORLD_SIZE' not in os.environ and args.gpus > 1:
         ndev = torch.cuda.device_count()                 # does not initialise the GPU on this image
@@ -694,8 +762,8 @@ def main():
     os.dup2(2, 1)
     # roofline.traffic of the dominant kernel, measured by THIS run (single-GPU T1 runs; child processes, started before
     # this process initialises the GPU)
-    traffic_live = (None, 'not measured (multi-rank run, other workload, or --no-traffic / --no-extra)')
-    if (int(os.environ.get('WORLD_SIZE', '1')) == 1 and args.workload in ('gmm', 'smm') and not args.no_traffic
+    traffic_live = (None, 'not measured (no --full, multi-rank run, other workload, or --no-traffic / --no-extra)')
+    if (args.full and int(os.environ.get('WORLD_SIZE', '1')) == 1 and args.workload in ('gmm', 'smm') and not args.no_traffic
             and not args.no_extra):
         traffic_live = measure_traffic(args.workload, args.n, args.d, args.k)
     world = int(os.environ.get('WORLD_SIZE', '1'))
@@ -810,13 +878,20 @@ def main():
         n_loc, n_job = rows_for(args.scaling)
         loop, x_h, r0_h, x, r0 = make_loop(n_loc, seed=rank)      # every rank: its own shard of the job's rows
         barrier()                                                 # every rank has its data and its loop before the first exchange
-        walls, kerns = time_t1(loop, args.steps, args.warmup, max(1, args.reps), barrier, dist, dev)
+        walls, kerns = time_t1(loop, args.steps, args.warmup, reps, barrier, dist, dev)
         dt = float(np.median(walls))
         kern_ms = float(np.median(kerns))
         assert torch.isfinite(loop.r).all()
         if world > 1:
             loop.check()                                          # a timed-out in-kernel wait voids the line: fail, do not print it
-        if world == 1 and args.workload == 'smm':
+        if args.dump_outputs and rank == 0:
+            # the last timed step: the posterior its finalize launch computed and the responsibilities of its E-pass
+            outs = {'r': sample_rows(loop.r)}
+            if loop.u is not None:
+                outs['u'] = sample_rows(loop.u)
+            outs.update({k: loop.post[k] for k in ('alpha', 'beta', 'm', 'C', 'v', 'xbar', 'S', 'pi')})
+            dump_outputs(args.dump_outputs, outs)
+        if args.full and world == 1 and args.workload == 'smm':
             # the opt-in accurate E-part (fp64 from an fp64 pack + a separate M-pass: VMPLoop(accurate=True)) beside the default
             aloop = _mix.VMPLoop(x, r0, flav, kappa=kappa, accurate=True)
             aw, _ = time_t1(aloop, args.steps, args.warmup, 7, barrier, None, dev)
@@ -824,7 +899,7 @@ def main():
                                       'what': 'VMPLoop(accurate=True): vmp_mix_finalize_ws64 + vmp_mix_estep_accurate (fp64 E-part) + vmp_mix_stats_ws_accurate (fp64 M-pass); '
                                               'meets the literal 1e-5 on r_nk at C5 (tests/test_fullsize_gpu.py smm-c5-accurate)'}
             del aloop
-        if world > 1:
+        if args.full and world > 1:
             # the OTHER scaling mode, same launch: fewer repetitions, same timed-region protocol
             other = 'strong' if args.scaling == 'weak' else 'weak'
             if loop.exchange is not None:
@@ -846,7 +921,9 @@ def main():
             barrier()
             del loop2
         # side measurements: single-GPU experiments (nothing after the timed region may take the JSON line down with it)
-        if not args.no_extra and world == 1:
+        if args.full and not args.no_extra and world == 1:
+            # the plain loop over `side_reps` timed regions: the like-for-like partner of the two forms timed below
+            pw0, _ = time_t1(loop, args.steps, args.warmup, side_reps, lambda: torch.cuda.synchronize(), None, dev)
             del loop
             torch.cuda.empty_cache()
             # (a) what the data-parallel iteration costs on top of the plain one, with ONE rank: the 3-launch RCCL form
@@ -856,7 +933,7 @@ def main():
             os.environ.setdefault('MASTER_PORT', '29533')
             dist1.init_process_group('nccl', rank=0, world_size=1, device_id=dev)
             dloop = DistributedVMPLoop(x, r0, flav, kappa=kappa)
-            dw, _ = time_t1(dloop, args.steps, args.warmup, max(1, args.reps), lambda: torch.cuda.synchronize(), None, dev)
+            dw, _ = time_t1(dloop, args.steps, args.warmup, side_reps, lambda: torch.cuda.synchronize(), None, dev)
             # the ONE collective of a T2 / T3 data-parallel step (packed fp64 buffer: moments + K-sized gradients [+ MLP gradients]),
             # in place on this stream, one rank: what the exchange adds to a step before any inter-GPU hop
             exch_us = {}
@@ -877,12 +954,12 @@ def main():
             del dloop
             ex = PeerExchange(K, D, rank=0, world=1, gather=lambda h: [h])
             ploop = DistributedVMPLoop(x, r0, flav, kappa=kappa, exchange=ex)
-            pw, _ = time_t1(ploop, args.steps, args.warmup, max(1, args.reps), lambda: torch.cuda.synchronize(), None, dev)
+            pw, _ = time_t1(ploop, args.steps, args.warmup, side_reps, lambda: torch.cuda.synchronize(), None, dev)
             p_us = float(np.median(pw)) / args.steps * 1e6
             ex.check()
             del ploop
             ex.close()
-            plain = dt / args.steps * 1e6
+            plain = float(np.median(pw0)) / args.steps * 1e6
             extra['t1_forced_dist_1rank'] = {'plain_us_per_step': plain, 'rccl_us_per_step': d_us, 'rccl_overhead_us': d_us - plain,
                                              'peer_exchange_us_per_step': p_us, 'dist_overhead_us': p_us - plain}
             del x, r0
@@ -967,17 +1044,18 @@ def main():
                 out['config']['datapoints_per_sec_by_scaling'] = vals
                 out['config']['scaling_note'] = ('`value` is the %s-scaling number (%d rows per GPU); %s scaling (%d rows per GPU) measured right after it in the same '
                                                  'launch: weak %.4g, strong %.4g datapoints/s' % (args.scaling, n_loc, o['scaling'], o['rows_per_rank'], vals['weak'], vals['strong']))
-            if world == 1 and not args.no_cpu_baseline:
+            if args.full and world == 1 and not args.no_cpu_baseline:
                 out['cpu_baseline'] = cpu_baseline(x_h, r0_h, args.workload)
                 out['speedup_vs_cpu_baseline'] = out['value'] / out['cpu_baseline']['value']
     else:
-        # ---- t2 / t3: millisecond-scale steps; `steps` capped so that the default flags finish in minutes
+        # ---- t2 / t3: millisecond-scale steps
         n_loc, n_job = rows_for(args.scaling)
-        steps = min(args.steps, 20)
-        warm = min(args.warmup, 3)
+        steps, warm = args.steps, args.warmup
         S, U = args.s, args.u
+        outs = {} if args.dump_outputs and rank == 0 else None
+        cpu = args.full and world == 1 and not args.no_cpu_baseline
         if args.workload == 't2':
-            res = bench_t2(n_loc, D, K, S, steps, warm, dev, dist, world, smm=args.smm, cpu=(world == 1 and not args.no_cpu_baseline))
+            res = bench_t2(n_loc, D, K, S, steps, warm, dev, dist, world, smm=args.smm, cpu=cpu, outputs=outs, noise_tensor=args.full)
             ms = res['ms_per_step']
             bwd_bytes = 4.0 * n_loc * (2.0 * K * S * D + 4 * D + 3 * K)
             roof = {'bound': 'hbm', 'achieved': res['bwd_GBps'], 'peak': HBM_PEAK_GBS, 'unit': 'GB/s', 'frac': res['bwd_frac_hbm'],
@@ -986,11 +1064,17 @@ def main():
             metric, wl = 'svae_vmp_step_datapoints_per_sec', 'T2 %ssvae-vmp step (fused E-step fwd + bwd, sub-sampling, M-step, CVI), L=%d, K=%d, S=%d' % ('Student-t (smm) ' if args.smm else '', D, K, S)
             extra['t2'] = res
         else:
-            res = bench_t3(n_loc, D, K, S, U, steps, warm, dev, None, smm=args.smm, cpu=(world == 1 and not args.no_cpu_baseline))
+            res = bench_t3(n_loc, D, K, S, U, steps, warm, dev, None, smm=args.smm, cpu=cpu, outputs=outs, noise_tensor=args.full)
+            steps, warm = res['steps'], res['warmup']
             ms = res['ms_per_step_wall_mean']                 # the line's own value: wall clock over the timed steps (the contract's timing)
-            roof = t3_roofline(n_loc, K, S, D, U, dev)
+            if outs is not None:
+                dump_outputs(args.dump_outputs, outs)         # before the roofline's own launches
+                outs = None
+            roof = t3_roofline(n_loc, K, S, D, U, dev) if args.full else None     # a kernel timed on its own: --full only
             metric, wl = 'svae_train_step_datapoints_per_sec', 'T3 %ssvae training step (experiments.py:196-267), L=Dy=%d, K=%d, S=%d, U=%d' % ('Student-t (smm) ' if args.smm else '', D, K, S, U)
             extra['t3'] = res
+        if outs is not None:
+            dump_outputs(args.dump_outputs, outs)
         ms = max_over_ranks(dist, ms, dev)
         if rank == 0:
             out = dict(common)
@@ -999,6 +1083,8 @@ def main():
                                    'N_per_gpu': n_loc, 'N_job': n_job, 'D': D, 'K': K,
                                    'parallelism': 'dp%d (rows sharded, 1 packed all-reduce of moments + gradients per step)' % world},
                         'roofline': roof})
+            if roof is None:
+                del out['roofline']
             if 'cpu_baseline' in res:
                 out['cpu_baseline'] = res['cpu_baseline']
                 out['speedup_vs_cpu_baseline'] = out['value'] / res['cpu_baseline']['value']

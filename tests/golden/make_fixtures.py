@@ -3,7 +3,7 @@
 
 Run in the authoring container only (needs /root/reference; the GPU box never has it):
 
-    python tests/golden/make_fixtures.py            # rewrites tests/golden/*.npz
+    python tests/golden/make_fixtures.py            # rewrites tests/golden/*.npz and reference_surface.json
 
 How: TensorFlow 1.3 is not installable here, so ``tf1_shim/tensorflow`` (an eager, torch-CPU backed
 stand-in for the ~90 tf.* calls the hot path uses) is put first on sys.path and the reference's
@@ -589,7 +589,30 @@ def case_vae_bernoulli(seed, N, K, S, L, D, U):
     return out
 
 
+SURFACE_MODULES = ('data.py', 'distributions/dirichlet.py', 'distributions/gaussian.py', 'distributions/niw.py',
+                   'distributions/student_t.py', 'helpers/scheduling.py', 'helpers/tf_utils.py', 'models/gmm.py',
+                   'models/smm.py', 'models/svae.py')
+
+
+def write_reference_surface():
+    """reference_surface.json: the names of the module-level functions of the reference's hot-path modules (names only, in
+    file order) - what tests/test_surface_cpu.py checks the product's modules against."""
+    import ast
+    import json
+    out = {}
+    for rel in SURFACE_MODULES:
+        tree = ast.parse(open(os.path.join(REF, rel)).read())
+        out[rel] = [n.name for n in tree.body if isinstance(n, ast.FunctionDef)]
+    path = os.path.join(HERE, 'reference_surface.json')
+    with open(path, 'w') as f:
+        json.dump(out, f, indent=1)
+        f.write('\n')
+    print('%-16s %4d names' % ('reference_surface', sum(len(v) for v in out.values())))
+
+
 def main():
+    if not sys.argv[1:] or 'reference_surface' in sys.argv[1:]:
+        write_reference_surface()
     cases = {
         'datasets': case_datasets,
         'svae_auto': lambda: case_svae(16, N=64, K=10, L=8, S=10, Dy=6, U=50, steps=3, y=auto_minibatch(), slim=True),

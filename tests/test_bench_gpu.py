@@ -1,7 +1,7 @@
 """bench.py's MULTI-RANK code paths executed with two ranks (the driver's 2/4/8-GPU runs cannot be rehearsed on a 1-GPU box with
 RCCL, which refuses two ranks on one device: VMP_BENCH_BACKEND=gloo lets two processes share GPU 0 - HIP kernels on the
 device, the per-step exchange staged through the host, or through the IPC peer buffers with --exchange peer).  Checks the
-contract arithmetic of both scaling modes and that the line carries the other mode as well."""
+contract arithmetic of both scaling modes and that the line carries the other mode as well (--full)."""
 import json
 import os
 import socket
@@ -43,7 +43,7 @@ def _run2(args):
 @pytest.mark.parametrize('scaling,exchange', [('weak', 'rccl'), ('strong', 'peer'), ('weak', 'auto')])
 def test_t1_two_ranks_both_scaling_modes(scaling, exchange):
     N = 40000
-    d = _run2(['--n', str(N), '--steps', '5', '--warmup', '2', '--reps', '3', '--no-extra', '--no-cpu-baseline',
+    d = _run2(['--n', str(N), '--steps', '5', '--warmup', '2', '--reps', '3', '--full', '--no-extra', '--no-cpu-baseline',
                '--scaling', scaling] + (['--exchange', exchange] if exchange != 'auto' else []))      # auto is the default
     ch = d['config']['exchange_choice']
     assert ch['requested'] == exchange
@@ -69,8 +69,47 @@ def test_t1_two_ranks_both_scaling_modes(scaling, exchange):
 def test_other_workloads_run_with_two_ranks(workload):
     """C4 (t3) and C5 (smm) bench commands, and t2, under a 2-rank launch."""
     N = 8192 if workload != 'smm' else 40000
-    d = _run2(['--workload', workload, '--n', str(N), '--steps', '3', '--warmup', '1', '--reps', '2', '--no-extra',
+    d = _run2(['--workload', workload, '--n', str(N), '--steps', '3', '--warmup', '1', '--reps', '2', '--full', '--no-extra',
                '--no-cpu-baseline'])
     assert d['n_gpus'] == 2 and d['config']['N_job'] == 2 * N
     assert abs(d['value'] - 2 * N / (d['ms_per_step'] * 1e-3)) < 1e-6 * d['value']
     assert d['roofline']['bound'] in ('hbm', 'mfma') and d['value'] > 0
+
+
+def _run1(args):
+    env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK')}
+    p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1'] + args, env=env, capture_output=True,
+                       text=True, timeout=600)
+    assert p.returncode == 0, p.stderr[-2000:]
+    lines = [l for l in p.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, lines
+    return json.loads(lines[0])
+
+
+@pytest.mark.parametrize('workload', ['gmm', 't2', 't3'])
+def test_plain_run_times_its_steps_and_dumps_the_last_one(workload, tmp_path):
+    """A run without --full: the headline alone over exactly --steps timed steps (no CPU baseline, no side measurements), and
+    --dump-outputs writes the last timed step's outputs; the same arguments give the same outputs again."""
+    import numpy as np
+    N = 40000 if workload == 'gmm' else 8192
+    lines = []
+    for tag in ('a', 'b'):
+        lines.append(_run1(['--workload', workload, '--n', str(N), '--steps', '6', '--warmup', '3',
+                            '--dump-outputs', str(tmp_path / tag)]))
+    for d in lines:
+        assert d['steps'] == 6 and d['warmup'] == 3 and d['n_gpus'] == 1 and d['dtype'] == 'f32' and d['higher_is_better'] is True
+        assert 'cpu_baseline' not in d and d['ms_per_step'] > 0
+        assert abs(d['value'] - N / (d['ms_per_step'] * 1e-3)) < 1e-6 * d['value']
+        if workload == 'gmm':
+            assert d['reps'] == 1 and 'extra' not in d
+    names = sorted(f for f in os.listdir(tmp_path / 'a'))
+    assert names == sorted(os.listdir(tmp_path / 'b')) and names
+    want = {'gmm': 'r.npy', 't2': 'x.npy', 't3': 'elbo.npy'}[workload]
+    assert want in names
+    total = 0
+    for f in names:
+        a, b = np.load(tmp_path / 'a' / f), np.load(tmp_path / 'b' / f)
+        assert a.dtype in (np.float32, np.float64) and a.shape == b.shape and np.isfinite(a).all(), f
+        assert np.allclose(a, b, rtol=1e-5, atol=1e-6), f
+        total += a.nbytes
+    assert total <= 64 * 10 ** 6

@@ -8,7 +8,7 @@ python -m pytest tests/test_fullsize_gpu.py -x -q -k "t3_training" > $O/pytest_f
 grep -E "passed|failed|Error|assert" $O/pytest_full.txt | tail -8
 for v in "" "--k 10" "--smm" "--smm --k 10"; do
   n=$(echo "t2$v" | tr -d ' -')
-  python bench.py --workload t2 $v --steps 10 --warmup 3 > $O/bench_$n.json 2> $O/bench_$n.err; echo "bench t2 $v rc=$?"
+  python bench.py --full --workload t2 $v --steps 10 --warmup 3 > $O/bench_$n.json 2> $O/bench_$n.err; echo "bench t2 $v rc=$?"
   python - <<PY
 import json
 j=json.load(open('$O/bench_$n.json')); r=j['roofline']

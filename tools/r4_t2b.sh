@@ -4,7 +4,7 @@ R=$(cd "$(dirname "$0")/.." && pwd); [ -n "$R" ] || exit 1
 O=$R/gpurun_out/r4_t2; mkdir -p $O; cd $R
 for v in "" "--k 10" "--smm" "--smm --k 10"; do
   n=$(echo "t2$v" | tr -d ' -')
-  python bench.py --workload t2 $v --steps 10 --warmup 3 > $O/bench_$n.json 2> $O/bench_$n.err; echo "bench t2 $v rc=$?"
+  python bench.py --full --workload t2 $v --steps 10 --warmup 3 > $O/bench_$n.json 2> $O/bench_$n.err; echo "bench t2 $v rc=$?"
   python - <<PY
 import json
 j=json.load(open('$O/bench_$n.json')); r=j['roofline']

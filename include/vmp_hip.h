@@ -481,6 +481,62 @@ int    vmp_svae_step_pack(double* xbuf, size_t xbuf_doubles, const float* dec_pa
                           const float* x_samples, const float* r, int64_t N, int K, int L, const double* tail_part, int tail_n,
                           int Dy, float* scalars, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * The same six-launch minibatch step for the Student-t mixture SVAE (SVAETrainer(smm=True); experiments.py:154-176, 196-267;
+ * models/svae.py:179-196, 265-322, 361-373).  Launches 2 (vmp_svae_estep_fwd_rng_epi, nu = DoF), 3 and 5 are the GMM step's;
+ * launches 1, 4 and 6 are these.  They replace, for that model, the autograd step's theta packing in torch (tril / softplus,
+ * solve_triangular, lgamma, digamma) and its autograd backward, the generic one-tile svae_estep_bwd_kernel + vmp_svae_bwd_reduce,
+ * phi_prep_bwd, the torch N_k M-step + CVI update of alpha and the Adam launch.
+ * ------------------------------------------------------------------------------------------------ */
+/* Launch 1: vmp_mlp_gauss_head_fwd_prep with the Student-t theta packed from (alpha (natural Dirichlet), theta_L_raw, dof) as
+ * svae._theta_pack does it: L_k = tril(raw) with softplus diagonal, W = L_k^-1 (K,L,L; lower, 0 above), kappa (K) =
+ * lgamma((nu+L)/2) - lgamma(nu/2) - L/2 log(pi nu) - sum log diag L_k + E[log pi_k].  The location m of the E-step is theta/mu_k
+ * itself (no output).  L = latent size Dy here, as in vmp_mlp_gauss_head_fwd_prep; scalar table as there. */
+int    vmp_mlp_gauss_head_fwd_prep_smm(const float* x, const float* W0, const float* b0, const float* W1, const float* b1,
+                                       const float* W2, const float* b2, const float* Ws, const float* bs1, const float* bs2,
+                                       int64_t R, int L, int Dy, int U, float var_scale, float* out1, float* out2,
+                                       const float* mu_k, const float* L_raw, const float* pi_raw, const float* alpha,
+                                       const float* theta_L_raw, const float* dof, int K, float* Lk, float* P, float* bias,
+                                       float* W, float* kappa, double* logpi, const void* scalar_table, int table_rows,
+                                       void* counter, void* dst16, void* stream);
+/* 1 when vmp_svae_estep_bwd_tail_t covers the shape: the envelope of vmp_svae_bwd_tail_applies (<= 256 tiles of 64 / K rows,
+ * S <= 16), 0 otherwise (the SMM step then stays the autograd step). */
+int    vmp_svae_bwd_tail_applies_t(int64_t N, int K, int L, int S);
+/* Launch 4: vmp_svae_estep_bwd_tail with Student-t theta (nu (K) = DoF, mk = theta/mu_k, Wk from launch 1).  The partial rows
+ * (vmp_svae_bwd_blocks_for(N, K, L, S, 0) = one per tile) also carry the theta half (words TH..2TH-1: d/dm, d/dW lower,
+ * d/dkappa), the layout vmp_svae_bwd_reduce reads when nu != NULL.  vmp_svae_estep_bwd_n / vmp_svae_bwd_blocks_for(...,
+ * student = 1) are unchanged (the autograd SMM step keeps the generic kernel). */
+int    vmp_svae_estep_bwd_tail_t(const float* eta1, const float* eta2d, const float* hk, const float* Pk, const float* bias,
+                                 const float* mk, const float* Wk, const float* nu, const float* x, const float* lz,
+                                 const float* T_prime, const float* ll, float sigma, const float* Gx, int64_t N, int K, int L,
+                                 int S, float* g_eta1, float* g_eta2d, float* partials, size_t partial_bytes, float* r,
+                                 double* tail_part, size_t tail_bytes, void* stream);
+/* Launch 6: vmp_svae_step_final's roles for the SMM model.  theta_p / _g / _m / _v: theta/mu_k (K,L), theta/L_k raw (K,L,L) with
+ * their gradient outputs and Adam slots - their gradients are the theta half of the partial rows (reduced in
+ * vmp_svae_bwd_reduce's order) through the theta packing: g_mu = g_m; g_Lk = -W^T g_W W^T (lower) - g_kappa / diag L_k;
+ * softplus / tril to g_L_raw.  Adam on 23 tensors (trainables() order: phi (3), theta (2), encoder (9), decoder (9)).  M-step:
+ * stats_out (K, 1) fp64 = N_k = sum_n r_nk, alpha* = prior_alpha + N_k -> alpha_star (may be NULL), alpha <- (1-rho) alpha +
+ * rho alpha* (svae.py:179-196, experiments.py:252-256).  r (N,K) from launch 4, N <= 512. */
+int    vmp_svae_step_final_smm(const float* dec_part, int dec_blocks, int dec_in, int dec_units, int dec_out,
+                               float* const* dec_p, float* const* dec_m, float* const* dec_v, float* const* dec_g,
+                               const float* enc_part, int enc_blocks, int enc_in, int enc_units, int enc_out,
+                               float* const* enc_p, float* const* enc_m, float* const* enc_v, float* const* enc_g,
+                               const float* partials, int nblk, const double* logpi,
+                               float* const* phi_p, float* const* phi_g, float* const* phi_m, float* const* phi_v,
+                               float* const* theta_p, float* const* theta_g, float* const* theta_m, float* const* theta_v,
+                               const float* r, int64_t N, const float* prior_alpha, float* alpha, float* alpha_star,
+                               const float* rho_dev, float rho, int K, int L, double* stats_out, const double* tail_part,
+                               int tail_n, int Dy, float* scalars, double beta1, double beta2, double eps, double lr_t,
+                               const float* lr_t_dev, void* stream);
+/* Data-parallel form of vmp_svae_step_final_smm (as vmp_svae_step_pack for the GMM step): nothing is updated; xbuf = [N_k (K, 1) |
+ * phi_gmm (3) | theta/mu_k, theta/L_k | encoder (9) | decoder (9) | elbo, rec, reg], the SMM step's exchange buffer. */
+int    vmp_svae_step_pack_smm(double* xbuf, size_t xbuf_doubles, const float* dec_part, int dec_blocks, int dec_in,
+                              int dec_units, int dec_out, float* const* dec_p, float* const* dec_g, const float* enc_part,
+                              int enc_blocks, int enc_in, int enc_units, int enc_out, float* const* enc_p,
+                              float* const* enc_g, const float* partials, int nblk, const double* logpi, float* const* phi_p,
+                              float* const* phi_g, float* const* theta_p, float* const* theta_g, const float* r, int64_t N,
+                              int K, int L, const double* tail_part, int tail_n, int Dy, float* scalars, void* stream);
+
 /* Writes the 16 bytes [Philox key (u64) | CVI step size (f32) | Adam step size (f32)] that a graph-captured training step
  * reads at run time (vmp_svae_estep_fwd_rng_dev / vmp_svae_subsample_rng seed_dev, vmp_svae_cvi_update rho_dev,
  * vmp_adam_step lr_t_dev = dst16 + 0 / 8 / 12): one launch, values passed by value.                                  */

@@ -93,6 +93,16 @@ _SIGNATURES = {
     'vmp_svae_step_final': (_c.c_int, [_P, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _P, _P, _P, _P] * 2 + [_P, _c.c_int, _P] + [_P] * 4
                             + [_P, _P, _c.c_int64, _P, _P, _P, _P, _c.c_float, _c.c_int, _c.c_int, _P, _P, _c.c_int, _c.c_int, _P]
                             + [_c.c_double] * 4 + [_P, _P]),
+    'vmp_mlp_gauss_head_fwd_prep_smm': (_c.c_int, [_P] * 10 + [_c.c_int64, _c.c_int, _c.c_int, _c.c_int, _c.c_float, _P, _P] + [_P] * 6
+                                        + [_c.c_int] + [_P] * 6 + [_P, _c.c_int, _P, _P, _P]),
+    'vmp_svae_bwd_tail_applies_t': (_c.c_int, [_c.c_int64, _c.c_int, _c.c_int, _c.c_int]),
+    'vmp_svae_estep_bwd_tail_t': (_c.c_int, [_P] * 12 + [_c.c_float, _P, _c.c_int64, _c.c_int, _c.c_int, _c.c_int, _P, _P, _P, _c.c_size_t, _P,
+                                             _P, _c.c_size_t, _P]),
+    'vmp_svae_step_final_smm': (_c.c_int, [_P, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _P, _P, _P, _P] * 2 + [_P, _c.c_int, _P] + [_P] * 4
+                                + [_P] * 4 + [_P, _c.c_int64, _P, _P, _P, _P, _c.c_float, _c.c_int, _c.c_int, _P, _P, _c.c_int, _c.c_int, _P]
+                                + [_c.c_double] * 4 + [_P, _P]),
+    'vmp_svae_step_pack_smm': (_c.c_int, [_P, _c.c_size_t] + [_P, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _P, _P] * 2
+                               + [_P, _c.c_int, _P, _P, _P, _P, _P, _P, _c.c_int64, _c.c_int, _c.c_int, _P, _c.c_int, _c.c_int, _P, _P]),
     'vmp_adam_step': (_c.c_int, [_c.c_int] + [_P] * 5 + [_c.c_double] * 4 + [_P, _P]),
     'vmp_pack_f64': (_c.c_int, [_c.c_int] + [_P] * 5),
     'vmp_adam_step_packed': (_c.c_int, [_c.c_int, _P, _P, _P, _c.c_double] + [_P] * 4 + [_c.c_double] * 4 + [_P, _P]),

@@ -614,9 +614,13 @@ struct StepTable {
     unsigned long long* dst16;
     unsigned rows;
 };
-template <int UT, int LP>
-__global__ __launch_bounds__(FWD_THREADS, 2) void enc_prep_kernel(DecArgs a, PhiArgs p, ThetaArgs t, StepTable st, unsigned nb) {
-    extern __shared__ __attribute__((aligned(16))) float sm[];
+template <int LP>
+__device__ __forceinline__ void enc_theta_body(const ThetaArgs& t, const int k) { theta_pack_body<LP, true>(t, k); }
+template <int LP>
+__device__ __forceinline__ void enc_theta_body(const SmmThetaArgs& t, const int k) { smm_theta_pack_body<LP, true>(t, k); }
+// TA: ThetaArgs (natural NIW / Dirichlet theta, enc_prep_kernel) or SmmThetaArgs (Student-t theta, enc_prep_smm_kernel)
+template <int UT, int LP, class TA>
+__device__ __forceinline__ void enc_prep_body(float* sm, const DecArgs& a, const PhiArgs& p, const TA& t, const StepTable& st, unsigned nb) {
     if (blockIdx.x < nb) {
         dec_fwd_body<UT>(a, sm, blockIdx.x, nb);
         return;
@@ -631,7 +635,17 @@ __global__ __launch_bounds__(FWD_THREADS, 2) void enc_prep_kernel(DecArgs a, Phi
     }
     if (threadIdx.x >= PREP_THREADS) return;
     if (b < (unsigned)p.K) phi_prep_body<LP, false, false, true>(p, (int)b);
-    else theta_pack_body<LP, true>(t, (int)(b - p.K));
+    else enc_theta_body<LP>(t, (int)(b - p.K));
+}
+template <int UT, int LP>
+__global__ __launch_bounds__(FWD_THREADS, 2) void enc_prep_kernel(DecArgs a, PhiArgs p, ThetaArgs t, StepTable st, unsigned nb) {
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    enc_prep_body<UT, LP>(sm, a, p, t, st, nb);
+}
+template <int UT, int LP>
+__global__ __launch_bounds__(FWD_THREADS, 2) void enc_prep_smm_kernel(DecArgs a, PhiArgs p, SmmThetaArgs t, StepTable st, unsigned nb) {
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    enc_prep_body<UT, LP>(sm, a, p, t, st, nb);
 }
 
 // Lanes of ONE wave exchange data through LDS: the LDS unit executes a wave's instructions in order, so no wait is
@@ -1312,6 +1326,66 @@ int mlp_gauss_bwd_impl(const char* what, float vscale, bool lazy, const float* x
     return check_launch(what);
 }
 
+template <int UT, int LP>
+void enc_prep_launch(unsigned grid, int lds, hipStream_t s, const DecArgs& a, const PhiArgs& p, const ThetaArgs& t, const StepTable& st,
+                     unsigned nb) {
+    hipLaunchKernelGGL((enc_prep_kernel<UT, LP>), dim3(grid), dim3(FWD_THREADS), lds, s, a, p, t, st, nb);
+}
+template <int UT, int LP>
+void enc_prep_launch(unsigned grid, int lds, hipStream_t s, const DecArgs& a, const PhiArgs& p, const SmmThetaArgs& t, const StepTable& st,
+                     unsigned nb) {
+    hipLaunchKernelGGL((enc_prep_smm_kernel<UT, LP>), dim3(grid), dim3(FWD_THREADS), lds, s, a, p, t, st, nb);
+}
+template <int UT, int LP> const void* enc_prep_fn(const ThetaArgs*) { return reinterpret_cast<const void*>(enc_prep_kernel<UT, LP>); }
+template <int UT, int LP> const void* enc_prep_fn(const SmmThetaArgs*) { return reinterpret_cast<const void*>(enc_prep_smm_kernel<UT, LP>); }
+
+template <class TA>
+int enc_prep_impl(const char* what, bool theta_ok, const float* x, const float* W0, const float* b0, const float* W1, const float* b1, const float* W2,
+                  const float* b2, const float* Ws, const float* bs1, const float* bs2, int64_t R, int L, int Dy, int U, float var_scale,
+                  float* out1, float* out2, const float* mu_k, const float* L_raw, const float* pi_raw, int K, float* Lk, float* P,
+                  float* bias, double* logpi, const TA& t, const void* scalar_table, int table_rows, void* counter, void* dst16,
+                  void* stream) {
+    if (int e = dec_check(what, R, 1, 1, L, Dy, U)) return e;
+    if (R < 1 || K < 1 || K > VMP_MAX_K) { set_error("%s: R = %lld, K = %d", what, (long long)R, K); return VMP_E_DIM; }
+    if (!x || !W0 || !b0 || !W1 || !b1 || !W2 || !b2 || !Ws || !bs1 || !bs2 || !out1 || !out2 || !mu_k || !L_raw || !pi_raw || !Lk || !P ||
+        !bias || !theta_ok) {
+        set_error("%s: NULL argument", what);
+        return VMP_E_BADARG;
+    }
+    if (scalar_table && (table_rows < 1 || !counter || !dst16 || (reinterpret_cast<uintptr_t>(dst16) & 7) || (reinterpret_cast<uintptr_t>(scalar_table) & 7))) {
+        set_error("%s: scalar table without rows / counter / 8-byte aligned destination", what);
+        return VMP_E_BADARG;
+    }
+    DecArgs a{};
+    a.x = x; a.W0 = W0; a.b0 = b0; a.W1 = W1; a.b1 = b1; a.W2 = W2; a.b2 = b2; a.Ws = Ws; a.bs1 = bs1; a.bs2 = bs2;
+    a.mean = out1; a.var = out2; a.vscale = var_scale;
+    a.R = (unsigned)R; a.K = 1; a.S = 1; a.L = L; a.Dy = Dy; a.U = U;
+    PhiArgs p{};
+    p.mu = mu_k; p.Lraw = L_raw; p.piraw = pi_raw; p.Lk = Lk; p.P = P; p.bias = bias; p.K = K; p.L = Dy; p.logpi_out = logpi;
+    StepTable st{static_cast<const unsigned long long*>(scalar_table), static_cast<unsigned long long*>(counter),
+                 static_cast<unsigned long long*>(dst16), (unsigned)(table_rows > 0 ? table_rows : 0)};
+    const unsigned nb = (unsigned)dec_fwd_blocks((long long)a.R);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+#define ENC_PREP_L(UTV, LP)                                                                                           \
+    do {                                                                                                              \
+        const int lds = Img<UTV>::FWD_END * (int)sizeof(float);                                                       \
+        if (const int rc_ = set_dyn_lds(enc_prep_fn<UTV, LP>(&t), (size_t)lds, "enc_prep_kernel")) return rc_;        \
+        enc_prep_launch<UTV, LP>(nb + 2 * K, lds, s, a, p, t, st, nb);                                                \
+    } while (0)
+#define ENC_PREP(UTV)                                                                                                 \
+    do {                                                                                                              \
+        switch (Dy) {                                                                                                 \
+            case 1: ENC_PREP_L(UTV, 1); break; case 2: ENC_PREP_L(UTV, 2); break; case 3: ENC_PREP_L(UTV, 3); break;  \
+            case 4: ENC_PREP_L(UTV, 4); break; case 5: ENC_PREP_L(UTV, 5); break; case 6: ENC_PREP_L(UTV, 6); break;  \
+            case 7: ENC_PREP_L(UTV, 7); break; default: ENC_PREP_L(UTV, 8); break;                                    \
+        }                                                                                                             \
+    } while (0)
+    DEC_DISPATCH(U, ENC_PREP);
+#undef ENC_PREP
+#undef ENC_PREP_L
+    return check_launch(what);
+}
+
 }  // namespace
 
 extern "C" {
@@ -1348,46 +1422,23 @@ int vmp_mlp_gauss_head_fwd_prep(const float* x, const float* W0, const float* b0
                                 float* Lk, float* P, float* bias, float* m, float* W, float* kappa, double* logpi,
                                 const void* scalar_table, int table_rows, void* counter, void* dst16, void* stream) {
     const char* what = "vmp_mlp_gauss_head_fwd_prep";
-    if (int e = dec_check(what, R, 1, 1, L, Dy, U)) return e;
-    if (R < 1 || K < 1 || K > VMP_MAX_K) { set_error("%s: R = %lld, K = %d", what, (long long)R, K); return VMP_E_DIM; }
-    if (!x || !W0 || !b0 || !W1 || !b1 || !W2 || !b2 || !Ws || !bs1 || !bs2 || !out1 || !out2 || !mu_k || !L_raw || !pi_raw || !alpha || !A ||
-        !b || !beta || !v_hat || !Lk || !P || !bias || !m || !W || !kappa) {
-        set_error("%s: NULL argument", what);
-        return VMP_E_BADARG;
-    }
-    if (scalar_table && (table_rows < 1 || !counter || !dst16 || (reinterpret_cast<uintptr_t>(dst16) & 7) || (reinterpret_cast<uintptr_t>(scalar_table) & 7))) {
-        set_error("%s: scalar table without rows / counter / 8-byte aligned destination", what);
-        return VMP_E_BADARG;
-    }
-    DecArgs a{};
-    a.x = x; a.W0 = W0; a.b0 = b0; a.W1 = W1; a.b1 = b1; a.W2 = W2; a.b2 = b2; a.Ws = Ws; a.bs1 = bs1; a.bs2 = bs2;
-    a.mean = out1; a.var = out2; a.vscale = var_scale;
-    a.R = (unsigned)R; a.K = 1; a.S = 1; a.L = L; a.Dy = Dy; a.U = U;
-    PhiArgs p{};
-    p.mu = mu_k; p.Lraw = L_raw; p.piraw = pi_raw; p.Lk = Lk; p.P = P; p.bias = bias; p.K = K; p.L = Dy; p.logpi_out = logpi;
-    ThetaArgs t{alpha, A, b, beta, v_hat, m, W, kappa, K, Dy};
-    StepTable st{static_cast<const unsigned long long*>(scalar_table), static_cast<unsigned long long*>(counter),
-                 static_cast<unsigned long long*>(dst16), (unsigned)(table_rows > 0 ? table_rows : 0)};
-    const unsigned nb = (unsigned)dec_fwd_blocks((long long)a.R);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-#define ENC_PREP_L(UTV, LP)                                                                                           \
-    do {                                                                                                              \
-        const int lds = Img<UTV>::FWD_END * (int)sizeof(float);                                                       \
-        if (const int rc_ = set_dyn_lds(reinterpret_cast<const void*>(enc_prep_kernel<UTV, LP>), (size_t)lds, "enc_prep_kernel")) return rc_; \
-        hipLaunchKernelGGL((enc_prep_kernel<UTV, LP>), dim3(nb + 2 * K), dim3(FWD_THREADS), lds, s, a, p, t, st, nb);  \
-    } while (0)
-#define ENC_PREP(UTV)                                                                                                 \
-    do {                                                                                                              \
-        switch (Dy) {                                                                                                 \
-            case 1: ENC_PREP_L(UTV, 1); break; case 2: ENC_PREP_L(UTV, 2); break; case 3: ENC_PREP_L(UTV, 3); break;  \
-            case 4: ENC_PREP_L(UTV, 4); break; case 5: ENC_PREP_L(UTV, 5); break; case 6: ENC_PREP_L(UTV, 6); break;  \
-            case 7: ENC_PREP_L(UTV, 7); break; default: ENC_PREP_L(UTV, 8); break;                                    \
-        }                                                                                                             \
-    } while (0)
-    DEC_DISPATCH(U, ENC_PREP);
-#undef ENC_PREP
-#undef ENC_PREP_L
-    return check_launch(what);
+    const bool theta_ok = alpha && A && b && beta && v_hat && m && W && kappa;
+    return enc_prep_impl(what, theta_ok, x, W0, b0, W1, b1, W2, b2, Ws, bs1, bs2, R, L, Dy, U, var_scale, out1, out2, mu_k, L_raw, pi_raw, K, Lk, P,
+                         bias, logpi, ThetaArgs{alpha, A, b, beta, v_hat, m, W, kappa, K, Dy}, scalar_table, table_rows, counter, dst16, stream);
+}
+
+// ---- the same launch for the Student-t mixture SVAE: theta = (alpha_nat, mu_k, L_k_raw, DoF) packed by smm_theta_pack_body
+int vmp_mlp_gauss_head_fwd_prep_smm(const float* x, const float* W0, const float* b0, const float* W1, const float* b1, const float* W2,
+                                    const float* b2, const float* Ws, const float* bs1, const float* bs2, int64_t R, int L, int Dy, int U,
+                                    float var_scale, float* out1, float* out2, const float* mu_k, const float* L_raw, const float* pi_raw,
+                                    const float* alpha, const float* theta_L_raw, const float* dof, int K, float* Lk, float* P, float* bias,
+                                    float* W, float* kappa, double* logpi, const void* scalar_table, int table_rows, void* counter,
+                                    void* dst16, void* stream) {
+    const char* what = "vmp_mlp_gauss_head_fwd_prep_smm";
+    const bool theta_ok = alpha && theta_L_raw && dof && W && kappa;
+    return enc_prep_impl(what, theta_ok, x, W0, b0, W1, b1, W2, b2, Ws, bs1, bs2, R, L, Dy, U, var_scale, out1, out2, mu_k, L_raw, pi_raw, K, Lk, P,
+                         bias, logpi, SmmThetaArgs{alpha, theta_L_raw, dof, W, kappa, K, Dy}, scalar_table, table_rows, counter, dst16,
+                         stream);
 }
 
 int vmp_decoder_loglike_bwd(const float* x, const float* y, const float* gA, const float* W0, const float* b0,

@@ -305,4 +305,53 @@ __device__ __forceinline__ void theta_pack_body(const ThetaArgs& a, const int k)
     if (lane == 0) a.kappa[k] = (float)(-0.5 * L * 1.8378770664093454836 + elp + lw);
 }
 
+// Student-t theta of the SMM-SVAE (svae._theta_pack for theta = (alpha_nat, mu_k, L_k_raw, DoF); svae.py:268-277, student_t.py:31-37):
+//   L_k = tril(raw) with softplus on the diagonal, W = L_k^-1, kappa_k = lgamma((nu+L)/2) - lgamma(nu/2) - L/2 log(pi nu)
+//   - sum log diag L_k + E[log pi_k];  m = mu_k itself (the caller passes mu_k where m is read).
+struct SmmThetaArgs {
+    const float *alpha, *Lraw, *dof;   // (K) natural Dirichlet, (K,L,L) raw scale factor, (K) degrees of freedom
+    float* W;                          // (K,L,L) lower, W = L_k^-1 (upper triangle written as 0)
+    float* kappa;                      // (K)
+    int K, L;
+};
+
+template <int L, bool WS = false>
+__device__ __forceinline__ void smm_theta_pack_body(const SmmThetaArgs& a, const int k) {
+    static_assert(L * L <= PREP_THREADS, "one lane per matrix element");
+    const int lane = threadIdx.x, K = a.K;
+    __shared__ double Ls[L][L + 1];
+    __shared__ double inv_d[L];
+    const int i = lane / L, j = lane % L;
+    const bool in = lane < L * L;
+    const double asum = wave_sum_d(lane < K ? (double)a.alpha[lane] + 1.0 : 0.0);            // dirichlet.natural_to_standard
+    const double dg = lane < 2 ? digamma_dd(lane == 0 ? (double)a.alpha[k] + 1.0 : asum) : 0.0;
+    const double elp = __shfl(dg, 0) - __shfl(dg, 1);
+    const float* __restrict__ raw = a.Lraw + (size_t)k * L * L;
+    double lij = 0.0;
+    if (in) {
+        if (j < i) lij = (double)raw[i * L + j];
+        else if (j == i) lij = (double)(float)softplus_d((double)raw[i * L + i]);
+        Ls[i][j] = lij;
+        if (i == j) inv_d[i] = 1.0 / lij;
+    }
+    const double ld = wave_sum_d((in && i == j) ? log(lij) : 0.0);           // sum log diag L_k
+    prep_sync<WS>();
+    if (lane < L) {                                     // W = L_k^-1: lane c solves for column c
+        const int c = lane;
+        double w[L];
+#pragma unroll
+        for (int r = 0; r < L; ++r) {
+            double t = r == c ? 1.0 : 0.0;
+#pragma unroll
+            for (int q = 0; q < r; ++q) t -= Ls[r][q] * w[q];
+            w[r] = r < c ? 0.0 : t * inv_d[r];
+            a.W[((size_t)k * L + r) * L + c] = (float)w[r];
+        }
+    }
+    if (lane == 0) {
+        const double nu = (double)a.dof[k];
+        a.kappa[k] = (float)(lgamma(0.5 * (nu + L)) - lgamma(0.5 * nu) - 0.5 * L * log(3.14159265358979323846 * nu) - ld + elp);
+    }
+}
+
 }  // namespace vmp

@@ -160,6 +160,26 @@ struct FinNet {
     int off[FIN_NET_TENSORS + 1];            // flat offsets of the tensors inside a partial row
     int nb;                                  // blocks
 };
+// SMM-SVAE (vmp_svae_step_final_smm / vmp_svae_step_pack_smm): the K moment / CVI blocks become the theta blocks of the Student-t
+// model - block k sums the THETA half of component k's partial rows (vmp_svae_bwd_reduce's order), differentiates the Student-t theta
+// packing (svae._theta_pack: m = mu_k, W = L_k^-1, kappa's -sum log diag L_k, tril / softplus), applies Adam to theta/mu_k and
+// theta/L_k, and does the SMM M-step: N_k = sum_n r_nk (fp64), alpha* = prior + N_k and the CVI update of alpha (svae.py:179-196,
+// experiments.py:252-256).
+struct SmmFin {
+    float* p[2];                             // theta/mu_k (K,L), theta/L_k raw (K,L,L)
+    float* m[2];                             // Adam slots (NULL: data-parallel form, no update)
+    float* v[2];
+    float* g[2];                             // gradients out (fp32)
+    double* gx[2];                           // data-parallel form: the gradients as doubles into the exchange buffer
+    const float* r;                          // (N,K) exp(log z) of vmp_svae_estep_bwd_tail_t
+    int N;
+    const float* prior_alpha;                // (K) natural Dirichlet prior
+    float* alpha;                            // (K) theta[0], updated in place (NULL: N_k only)
+    float* alpha_star;                       // (K) may be NULL
+    const float* rho_dev;
+    float rho;
+    double* nk;                              // (K) N_k out
+};
 struct FinArgs {
     FinNet net[2];
     PhiArgs phi;                             // (backward form: mu, Lraw, piraw, logpi in; g_mu, g_Lraw, g_piraw out)
@@ -176,8 +196,100 @@ struct FinArgs {
     // exchange buffer [moments | gradients in parameter order | elbo, rec, reg] that the step's ONE all-reduce sums
     double* xnet[2];                         // where the two nets' gradients start in the buffer (NULL: the single-process form)
     double* xscal;
+    SmmFin smm;                              // (step_final_kernel<L, true> only)
 };
+
 template <int L>
+__device__ __forceinline__ void smm_theta_final_body(const FinArgs& a, const int k, double (*part)[64], const float lr_t) {
+    constexpr int TRI = L * (L + 1) / 2, TH = L + TRI + 1, PW = 2 * TH;
+    static_assert(TH <= 64 && L * L <= 64, "one lane per partial word / matrix element");
+    const SmmFin& q = a.smm;
+    const int K = a.phi.K, tid = threadIdx.x, eg = tid & 63, bg = tid >> 6;
+    __shared__ double nkw[FIN_THREADS / WAVE];
+    __shared__ double Ls[L][L + 1], Wm[L][L + 1], Gw[L][L + 1], Am[L][L + 1], inv_d[L];
+    __shared__ double gkap;
+    __shared__ float gms[L];
+    part[bg][eg] = eg < TH ? red_group_sum(a.partials + (size_t)k * PW + TH + eg, (size_t)K * PW, a.nblk, bg) : 0.0;
+    double rv = tid < q.N ? (double)q.r[(size_t)tid * K + k] : 0.0;        // N <= SMALL_STATS_MAX_N <= FIN_THREADS rows
+    rv = wave_sum_d(rv);
+    if (eg == 0) nkw[bg] = rv;
+    __syncthreads();
+    if (tid >= WAVE) return;
+    const int lane = tid, i = lane / L, j = lane % L;
+    const bool in = lane < L * L;
+    double s = part[0][lane];
+    for (int g2 = 1; g2 < RED_GROUPS; ++g2) s += part[g2][lane];
+    const float v = (float)s;                                               // rounded as vmp_svae_bwd_reduce's tensors
+    if (lane < L) gms[lane] = v;
+    else if (lane < L + TRI) {
+        const int idx = lane - L;
+        int ii = 0;
+        while ((ii + 1) * (ii + 2) / 2 <= idx) ++ii;
+        Gw[ii][idx - ii * (ii + 1) / 2] = (double)v;
+    } else if (lane == L + TRI) gkap = (double)v;
+    const float* raw = q.p[1] + (size_t)k * L * L;           // (no restrict: Adam writes these elements below)
+    double rawd = 0.0, lij = 0.0;
+    if (in) {
+        rawd = (double)raw[i * L + j];
+        lij = j < i ? rawd : (j == i ? (double)(float)softplus_d(rawd) : 0.0);
+        Ls[i][j] = lij;
+        if (i == j) inv_d[i] = 1.0 / lij;
+        if (j > i) Gw[i][j] = 0.0;                           // W is lower: no gradient above the diagonal
+    }
+    prep_sync<true>();
+    if (lane < L) {                                          // W = L_k^-1, lane c: column c
+        const int c = lane;
+        double w[L];
+#pragma unroll
+        for (int r = 0; r < L; ++r) {
+            double t = r == c ? 1.0 : 0.0;
+#pragma unroll
+            for (int p = 0; p < r; ++p) t -= Ls[r][p] * w[p];
+            w[r] = r < c ? 0.0 : t * inv_d[r];
+            Wm[r][c] = w[r];
+        }
+    }
+    prep_sync<true>();
+    if (in) {                                                // A = W^T G_W
+        double t = 0.0;
+#pragma unroll
+        for (int p = 0; p < L; ++p) t += p >= i ? Wm[p][i] * Gw[p][j] : 0.0;
+        Am[i][j] = t;
+    }
+    prep_sync<true>();
+    const float rho = q.rho_dev ? *q.rho_dev : q.rho;
+    if (in) {
+        // d/dL_k of W = L_k^-1: -W^T G_W W^T (lower part); kappa has -log L_ii; then the softplus of the diagonal (tril: 0 above)
+        double g = 0.0;
+        if (j <= i) {
+#pragma unroll
+            for (int p = 0; p < L; ++p) g -= p <= j ? Am[i][p] * Wm[j][p] : 0.0;
+            if (i == j) {
+                g -= gkap * inv_d[i];
+                g *= 1.0 / (1.0 + exp(-rawd));               // softplus'
+            }
+        }
+        const float gf = (float)g;
+        const unsigned e = (unsigned)(k * L * L + lane);
+        q.g[1][e] = gf;
+        if (q.gx[1]) q.gx[1][e] = (double)gf;
+        if (q.m[1]) adam_update(q.p[1], q.m[1], q.v[1], e, gf, lr_t, a.b1, a.b2, a.c1, a.c2, a.eps);
+    }
+    if (lane < L) {                                          // m = mu_k
+        const float gf = gms[lane];
+        const unsigned e = (unsigned)(k * L + lane);
+        q.g[0][e] = gf;
+        if (q.gx[0]) q.gx[0][e] = (double)gf;
+        if (q.m[0]) adam_update(q.p[0], q.m[0], q.v[0], e, gf, lr_t, a.b1, a.b2, a.c1, a.c2, a.eps);
+    }
+    if (lane == 0) {
+        double nk = 0.0;
+        for (int w = 0; w < FIN_THREADS / WAVE; ++w) nk += nkw[w];
+        q.nk[k] = nk;
+        if (q.alpha) cvi_one(q.alpha, q.alpha_star, q.prior_alpha[k] + (float)nk, rho, (size_t)k);
+    }
+}
+template <int L, bool SMM = false>
 __global__ __launch_bounds__(FIN_THREADS) void step_final_kernel(FinArgs a) {
     __shared__ double part[DEC_RED_GROUPS][64];
     __shared__ double spart[SMALL_STATS_GROUPS][80];
@@ -211,9 +323,17 @@ __global__ __launch_bounds__(FIN_THREADS) void step_final_kernel(FinArgs a) {
         return;
     }
     b -= a.phi.K;
-    if (b < a.cvi.K) {
-        stats_cvi_body(a.sa, a.cvi, b, spart, st, a.xscal == nullptr);
-        return;
+    if constexpr (SMM) {
+        if (b < a.phi.K) {
+            smm_theta_final_body<L>(a, b, part, lr_t);
+            return;
+        }
+        b -= a.phi.K;
+    } else {
+        if (b < a.cvi.K) {
+            stats_cvi_body(a.sa, a.cvi, b, spart, st, a.xscal == nullptr);
+            return;
+        }
     }
     if (threadIdx.x < WAVE) {
         elbo_final_body(a.tail, a.tail_n);
@@ -265,17 +385,17 @@ int step_final_impl(const char* what, double* xbuf, const float* dec_part, int d
                         float* const* phi_g, float* const* phi_m, float* const* phi_v, const float* x_samples, const float* r, int64_t N, const float* const* prior,
                         float* const* theta, float* const* theta_star, const float* rho_dev, float rho, int K, int L,
                         double* stats_out, const double* tail_part, int tail_n, int Dy, float* scalars, double beta1, double beta2,
-                        double eps, double lr_t, const float* lr_t_dev, void* stream) {
+                        double eps, double lr_t, const float* lr_t_dev, void* stream, const SmmFin* smm = nullptr) {
     const bool pack = xbuf != nullptr;
     if (K < 1 || K > VMP_MAX_K || L < 1 || L > VMP_MAX_D || N < 1 || N > SMALL_STATS_MAX_N || tail_n < 1 || tail_n > TAIL_MAX_BLOCKS || Dy < 1) {
-        set_error("vmp_svae_step_final / _pack: K=%d L=%d N=%lld tail_n=%d outside the minibatch step's range (N <= %d)", K, L, (long long)N, tail_n,
+        set_error("%s: K=%d L=%d N=%lld tail_n=%d outside the minibatch step's range (N <= %d)", what, K, L, (long long)N, tail_n,
                   SMALL_STATS_MAX_N);
         return VMP_E_DIM;
     }
     if (!dec_part || !enc_part || dec_blocks < 1 || enc_blocks < 1 || !dec_p || !dec_m || !dec_v || !dec_g || !enc_p || !enc_m || !enc_v ||
-        !enc_g || !partials || nblk < 1 || !logpi || !phi_p || !phi_g || !phi_m || !phi_v || !x_samples || !r || (!pack && (!prior || !theta)) ||
+        !enc_g || !partials || nblk < 1 || !logpi || !phi_p || !phi_g || !phi_m || !phi_v || !x_samples || !r || (!pack && !smm && (!prior || !theta)) ||
         (!pack && !stats_out) || !tail_part || !scalars) {
-        set_error("vmp_svae_step_final: NULL argument");
+        set_error("%s: NULL argument", what);
         return VMP_E_BADARG;
     }
     FinArgs a{};
@@ -286,7 +406,7 @@ int step_final_impl(const char* what, double* xbuf, const float* dec_part, int d
     for (int n = 0; n < 2; ++n) {
         const int Li = nets[n].in, U = nets[n].units, Do = nets[n].out;
         if (Li < 1 || Li > 8 || Do < 1 || Do > 8 || U < 1 || U > 64) {
-            set_error("vmp_svae_step_final: net %d sizes in=%d units=%d out=%d outside the fused MLP's range", n, Li, U, Do);
+            set_error("%s: net %d sizes in=%d units=%d out=%d outside the fused MLP's range", what, n, Li, U, Do);
             return VMP_E_DIM;
         }
         const int sizes[FIN_NET_TENSORS] = {Li * U, U, U * U, U, U * 2 * Do, 2 * Do, Li * Do, Do, Do};   // the reference's variable order
@@ -294,7 +414,7 @@ int step_final_impl(const char* what, double* xbuf, const float* dec_part, int d
         int o = 0;
         for (int t = 0; t < FIN_NET_TENSORS; ++t) {
             if (!nets[n].p[t] || !nets[n].m[t] || !nets[n].v[t] || !nets[n].g[t]) {
-                set_error("vmp_svae_step_final: net %d tensor %d: NULL pointer", n, t);
+                set_error("%s: net %d tensor %d: NULL pointer", what, n, t);
                 return VMP_E_BADARG;
             }
             q.p[t] = nets[n].p[t]; q.m[t] = nets[n].m[t]; q.v[t] = nets[n].v[t]; q.g[t] = nets[n].g[t];
@@ -303,7 +423,7 @@ int step_final_impl(const char* what, double* xbuf, const float* dec_part, int d
         }
         q.off[FIN_NET_TENSORS] = o;
         if (o != vmp_decoder_param_words(Li, U, Do)) {
-            set_error("vmp_svae_step_final: parameter layout mismatch (%d != %d words)", o, vmp_decoder_param_words(Li, U, Do));
+            set_error("%s: parameter layout mismatch (%d != %d words)", what, o, vmp_decoder_param_words(Li, U, Do));
             return VMP_E_DIM;
         }
         q.red = DecRedArgs{nets[n].part, q.p[FIN_NET_TENSORS - 1], nullptr, nets[n].nblk, o, o - Do, Do};
@@ -311,30 +431,51 @@ int step_final_impl(const char* what, double* xbuf, const float* dec_part, int d
         blocks += (unsigned)q.nb;
     }
     for (int t = 0; t < 3; ++t) {                           // phi_gmm/mu_k (K,L), L_k (K,L,L), log_pi_k (K)
-        if (!phi_p[t] || !phi_g[t] || !phi_m[t] || !phi_v[t]) { set_error("vmp_svae_step_final: phi tensor %d: NULL pointer", t); return VMP_E_BADARG; }
+        if (!phi_p[t] || !phi_g[t] || !phi_m[t] || !phi_v[t]) { set_error("%s: phi tensor %d: NULL pointer", what, t); return VMP_E_BADARG; }
         a.phi_adam.p[t] = phi_p[t]; a.phi_adam.m[t] = phi_m[t]; a.phi_adam.v[t] = phi_v[t];
     }
     a.phi.mu = phi_p[0]; a.phi.Lraw = phi_p[1]; a.phi.piraw = phi_p[2]; a.phi.logpi = logpi;
     a.phi.g_mu = phi_g[0]; a.phi.g_Lraw = phi_g[1]; a.phi.g_piraw = phi_g[2]; a.phi.K = K; a.phi.L = L;
     a.partials = partials; a.nblk = nblk;
     blocks += (unsigned)K;
+    if (smm) {
+        a.smm = *smm;
+        a.smm.r = r; a.smm.N = (int)N;
+        for (int t = 0; t < 2; ++t)
+            if (!smm->p[t] || !smm->g[t] || (!pack && (!smm->m[t] || !smm->v[t]))) {
+                set_error("%s: theta tensor %d: NULL pointer", what, t);
+                return VMP_E_BADARG;
+            }
+        if (!pack && (!smm->prior_alpha || !smm->alpha)) { set_error("%s: prior / alpha: NULL pointer", what); return VMP_E_BADARG; }
+        a.smm.nk = pack ? xbuf : stats_out;
+        a.smm.rho_dev = rho_dev; a.smm.rho = rho;
+    }
     if (pack) {
         // [moments (K, 2+L+L*L) | phi_gmm/mu_k, L_k, log_pi_k | encoder net | decoder net | elbo, rec, reg]: the parameter order of
-        // SVAETrainer.trainables() (experiments.py:160-181), as training.pack_exchange_buffer lays it out
-        const int SW = 2 + L + L * L;
+        // SVAETrainer.trainables() (experiments.py:160-181), as training.pack_exchange_buffer lays it out.  SMM: [N_k (K, 1) | phi_gmm (3) |
+        // theta/mu_k, theta/L_k | encoder | decoder | elbo, rec, reg]
+        const int SW = smm ? 1 : 2 + L + L * L;
         double* o = xbuf + (size_t)K * SW;
         a.phi_adam.gx[0] = o; o += K * L;
         a.phi_adam.gx[1] = o; o += K * L * L;
         a.phi_adam.gx[2] = o; o += K;
+        if (smm) {
+            a.smm.gx[0] = o; o += K * L;
+            a.smm.gx[1] = o; o += K * L * L;
+            a.smm.m[0] = a.smm.m[1] = a.smm.v[0] = a.smm.v[1] = nullptr;
+            a.smm.alpha = nullptr;
+        }
         a.xnet[1] = o; o += a.net[1].red.PW;                 // encoder first
         a.xnet[0] = o; o += a.net[0].red.PW;
         a.xscal = o;
         for (int t = 0; t < 3; ++t) a.phi_adam.p[t] = nullptr;
         a.sa = SmallStatsArgs{x_samples, r, nullptr, xbuf, (int)N, L, K};
         a.cvi.K = K; a.cvi.L = L;
+    } else if (smm) {
+        a.smm.gx[0] = a.smm.gx[1] = nullptr;
     } else {
     for (int t = 0; t < 5; ++t)
-        if (!prior[t] || !theta[t]) { set_error("vmp_svae_step_final: prior / theta tensor %d: NULL pointer", t); return VMP_E_BADARG; }
+        if (!prior[t] || !theta[t]) { set_error("%s: prior / theta tensor %d: NULL pointer", what, t); return VMP_E_BADARG; }
     a.sa = SmallStatsArgs{x_samples, r, nullptr, stats_out, (int)N, L, K};
     a.cvi = CviArgs{stats_out, prior[0], prior[1], prior[2], prior[3], prior[4], theta[0], theta[1], theta[2], theta[3], theta[4],
                     theta_star ? theta_star[0] : nullptr, theta_star ? theta_star[1] : nullptr, theta_star ? theta_star[2] : nullptr,
@@ -350,7 +491,13 @@ int step_final_impl(const char* what, double* xbuf, const float* dec_part, int d
     a.c1 = (float)(1.0 - beta1); a.c2 = (float)(1.0 - beta2); a.eps = (float)eps;
     a.phi_adam.b1 = a.b1; a.phi_adam.b2 = a.b2; a.phi_adam.c1 = a.c1; a.phi_adam.c2 = a.c2; a.phi_adam.eps = a.eps;
 #define FIN_CALL(LL) case LL: hipLaunchKernelGGL((step_final_kernel<LL>), dim3(blocks), dim3(FIN_THREADS), 0, static_cast<hipStream_t>(stream), a); break
-    switch (L) { FIN_CALL(1); FIN_CALL(2); FIN_CALL(3); FIN_CALL(4); FIN_CALL(5); FIN_CALL(6); FIN_CALL(7); default: FIN_CALL(8); }
+#define FIN_CALL_SMM(LL) case LL: hipLaunchKernelGGL((step_final_kernel<LL, true>), dim3(blocks), dim3(FIN_THREADS), 0, static_cast<hipStream_t>(stream), a); break
+    if (smm) {
+        switch (L) { FIN_CALL_SMM(1); FIN_CALL_SMM(2); FIN_CALL_SMM(3); FIN_CALL_SMM(4); FIN_CALL_SMM(5); FIN_CALL_SMM(6); FIN_CALL_SMM(7); default: FIN_CALL_SMM(8); }
+    } else {
+        switch (L) { FIN_CALL(1); FIN_CALL(2); FIN_CALL(3); FIN_CALL(4); FIN_CALL(5); FIN_CALL(6); FIN_CALL(7); default: FIN_CALL(8); }
+    }
+#undef FIN_CALL_SMM
 #undef FIN_CALL
     return check_launch(what);
 }
@@ -395,6 +542,56 @@ int vmp_svae_step_pack(double* xbuf, size_t xbuf_doubles, const float* dec_part,
                            enc_blocks, enc_in, enc_units, enc_out, enc_p, enc_p, enc_p, enc_g, partials, nblk, logpi, phi_p, phi_g, phi_p,
                            phi_p, x_samples, r, N, nullptr, nullptr, nullptr, nullptr, 0.f, K, L, nullptr, tail_part, tail_n, Dy, scalars,
                            0.9, 0.999, 1e-8, 0.0, nullptr, stream);
+}
+
+// The closing launch of the SMM-SVAE's minibatch step: vmp_svae_step_final's roles with the Student-t model's theta (see SmmFin):
+// Adam on the 23 tensors of SVAETrainer.trainables() (phi_gmm (3), theta/mu_k, theta/L_k, encoder (9), decoder (9)), the N_k-only
+// M-step and the CVI update of alpha; stats_out (K, 1) fp64 = N_k.  partials: vmp_svae_estep_bwd_tail_t's (theta half included).
+int vmp_svae_step_final_smm(const float* dec_part, int dec_blocks, int dec_in, int dec_units, int dec_out, float* const* dec_p,
+                            float* const* dec_m, float* const* dec_v, float* const* dec_g, const float* enc_part, int enc_blocks,
+                            int enc_in, int enc_units, int enc_out, float* const* enc_p, float* const* enc_m, float* const* enc_v,
+                            float* const* enc_g, const float* partials, int nblk, const double* logpi, float* const* phi_p,
+                            float* const* phi_g, float* const* phi_m, float* const* phi_v, float* const* theta_p, float* const* theta_g,
+                            float* const* theta_m, float* const* theta_v, const float* r, int64_t N, const float* prior_alpha,
+                            float* alpha, float* alpha_star, const float* rho_dev, float rho, int K, int L, double* stats_out,
+                            const double* tail_part, int tail_n, int Dy, float* scalars, double beta1, double beta2, double eps,
+                            double lr_t, const float* lr_t_dev, void* stream) {
+    if (!theta_p || !theta_g || !theta_m || !theta_v) { set_error("vmp_svae_step_final_smm: NULL argument"); return VMP_E_BADARG; }
+    SmmFin f{};
+    for (int t = 0; t < 2; ++t) { f.p[t] = theta_p[t]; f.g[t] = theta_g[t]; f.m[t] = theta_m[t]; f.v[t] = theta_v[t]; }
+    f.prior_alpha = prior_alpha; f.alpha = alpha; f.alpha_star = alpha_star;
+    // (x_samples is not read by the SMM M-step: r stands in for the pointer check)
+    return step_final_impl("vmp_svae_step_final_smm", nullptr, dec_part, dec_blocks, dec_in, dec_units, dec_out, dec_p, dec_m, dec_v, dec_g,
+                           enc_part, enc_blocks, enc_in, enc_units, enc_out, enc_p, enc_m, enc_v, enc_g, partials, nblk, logpi, phi_p, phi_g,
+                           phi_m, phi_v, r, r, N, nullptr, nullptr, nullptr, rho_dev, rho, K, L, stats_out, tail_part, tail_n, Dy, scalars,
+                           beta1, beta2, eps, lr_t, lr_t_dev, stream, &f);
+}
+
+// Data-parallel form of vmp_svae_step_final_smm: xbuf [N_k (K, 1) | phi_gmm (3) | theta/mu_k, theta/L_k | encoder (9) | decoder (9) |
+// elbo, rec, reg] (training.pack_exchange_buffer's layout of the SMM step); nothing is updated.
+int vmp_svae_step_pack_smm(double* xbuf, size_t xbuf_doubles, const float* dec_part, int dec_blocks, int dec_in, int dec_units,
+                           int dec_out, float* const* dec_p, float* const* dec_g, const float* enc_part, int enc_blocks, int enc_in,
+                           int enc_units, int enc_out, float* const* enc_p, float* const* enc_g, const float* partials, int nblk,
+                           const double* logpi, float* const* phi_p, float* const* phi_g, float* const* theta_p, float* const* theta_g,
+                           const float* r, int64_t N, int K, int L, const double* tail_part, int tail_n, int Dy, float* scalars,
+                           void* stream) {
+    if (!xbuf || !theta_p || !theta_g) { set_error("vmp_svae_step_pack_smm: NULL argument"); return VMP_E_BADARG; }
+    if (K < 1 || L < 1 || dec_in < 1 || dec_units < 1 || dec_out < 1 || enc_in < 1 || enc_units < 1 || enc_out < 1) {
+        set_error("vmp_svae_step_pack_smm: bad sizes");
+        return VMP_E_DIM;
+    }
+    const size_t need = (size_t)K + 2 * ((size_t)K * L + (size_t)K * L * L) + K + (size_t)vmp_decoder_param_words(enc_in, enc_units, enc_out) +
+                        (size_t)vmp_decoder_param_words(dec_in, dec_units, dec_out) + 3;
+    if (xbuf_doubles < need) {
+        set_error("vmp_svae_step_pack_smm: exchange buffer too small (%zu < %zu doubles)", xbuf_doubles, need);
+        return VMP_E_WS;
+    }
+    SmmFin f{};
+    for (int t = 0; t < 2; ++t) { f.p[t] = theta_p[t]; f.g[t] = theta_g[t]; }
+    return step_final_impl("vmp_svae_step_pack_smm", xbuf, dec_part, dec_blocks, dec_in, dec_units, dec_out, dec_p, dec_p, dec_p, dec_g, enc_part,
+                           enc_blocks, enc_in, enc_units, enc_out, enc_p, enc_p, enc_p, enc_g, partials, nblk, logpi, phi_p, phi_g, phi_p,
+                           phi_p, r, r, N, nullptr, nullptr, nullptr, nullptr, 0.f, K, L, nullptr, tail_part, tail_n, Dy, scalars,
+                           0.9, 0.999, 1e-8, 0.0, nullptr, stream, &f);
 }
 
 size_t vmp_svae_elbo_tail_workspace_bytes(void) { return tail_workspace_bytes(); }

@@ -2331,6 +2331,44 @@ int vmp_svae_estep_bwd_tail(const float* eta1, const float* eta2d, const float* 
     return svae_bwd1_launch(a, L, nt, (S + 1) / 2, true, stream);
 }
 
+// ---- the SMM-SVAE's minibatch step: vmp_svae_estep_bwd_tail with Student-t theta (svae_estep_bwd1_kernel<L, true, true>).  The same
+// envelope as the Gaussian form (<= 256 tiles, S <= 16): the kernel's per-pair theta sums take a second round through the LDS area of
+// the first, so the block's LDS is the Gaussian form's.  (vmp_svae_bwd_blocks_for(..., student = 1) and vmp_svae_estep_bwd_n keep
+// their generic-kernel answer: the autograd SMM step is unchanged.)
+int vmp_svae_bwd_tail_applies_t(int64_t N, int K, int L, int S) {
+    if (!(N > 0 && K >= 1 && K <= WAVE && L >= 1 && L <= 8 && S >= 1)) return 0;
+    const long long nt = (N + WAVE / K - 1) / (WAVE / K);
+    return VMP_BWD1 && nt <= BWD1_MAX_TILES && (S + 1) / 2 <= BWD1_MAX_PAIRS ? 1 : 0;
+}
+
+int vmp_svae_estep_bwd_tail_t(const float* eta1, const float* eta2d, const float* hk, const float* Pk, const float* bias,
+                              const float* mk, const float* Wk, const float* nu, const float* x, const float* lz, const float* T_prime,
+                              const float* ll, float sigma, const float* Gx, int64_t N, int K, int L, int S, float* g_eta1,
+                              float* g_eta2d, float* partials, size_t partial_bytes, float* r, double* tail_part, size_t tail_bytes,
+                              void* stream) {
+    int rc = check_sv(N, K, L, S);
+    if (rc) return rc;
+    if (!eta1 || !eta2d || !hk || !Pk || !bias || !mk || !Wk || !nu || !x || !lz || !T_prime || !ll || !Gx || !g_eta1 || !g_eta2d ||
+        !partials || !r || !tail_part || sigma == 0.f) {
+        set_error("vmp_svae_estep_bwd_tail_t: null pointer or sigma == 0");
+        return VMP_E_BADARG;
+    }
+    if (!vmp_svae_bwd_tail_applies_t(N, K, L, S)) {
+        set_error("vmp_svae_estep_bwd_tail_t: N=%lld K=%d L=%d S=%d outside the minibatch form (<= %d tiles, S <= %d)", (long long)N, K, L,
+                  S, BWD1_MAX_TILES, 2 * BWD1_MAX_PAIRS);
+        return VMP_E_DIM;
+    }
+    const int nt = (int)((N + WAVE / K - 1) / (WAVE / K));
+    const int PW = vmp_svae_bwd_partial_words(L);
+    if (partial_bytes < (size_t)nt * K * PW * sizeof(float) || tail_bytes < (size_t)nt * 2 * sizeof(double)) {
+        set_error("vmp_svae_estep_bwd_tail_t: partials / tail_part buffer too small for %d tiles", nt);
+        return VMP_E_WS;
+    }
+    EBwdArgs a{eta1, eta2d, hk, Pk, bias, mk, Wk, nu, x, lz, Gx, nullptr, nullptr, g_eta1, g_eta2d, partials, N, K, S, 0};
+    a.Tp = T_prime; a.ll = ll; a.r_out = r; a.tail_part = tail_part; a.sigma = sigma;
+    return svae_bwd1_t_launch(a, L, nt, (S + 1) / 2, stream);
+}
+
 int vmp_svae_bwd_blocks_for(int64_t N, int K, int L, int S, int student) {
     if (N <= 0 || K < 1 || K > WAVE) return 0;
     if (bwd1_applies(N, K, L, S, student != 0)) return (int)((N + WAVE / K - 1) / (WAVE / K));

@@ -148,4 +148,5 @@ namespace vmp {
 // write are zeroed by the kernel).
 int svae_bwd_ring_launch(const EBwdArgs& a, int L, int nblk_abi, void* stream);
 int svae_bwd1_launch(const EBwdArgs& a, int L, int ntiles, int P, bool tail, void* stream);      // vmp_svae_mini.hip: one block per tile, one wave per sample pair
+int svae_bwd1_t_launch(const EBwdArgs& a, int L, int ntiles, int P, void* stream);                // the same with Student-t theta and the tail
 }

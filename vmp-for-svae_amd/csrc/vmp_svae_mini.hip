@@ -22,9 +22,15 @@ constexpr int BWD1_MAX_PAIRS = 8;
 // does it) forms dLoss/dlog_z from the cell's S reconstruction sums (tail_cell, vmp_tail.h: the arithmetic of elbo_tail_body), writes
 // r = exp(log z) and the tile's terms of the ELBO's two fp64 sums, and hands dLoss/dlog_z to wave 0 through LDS - it is done long
 // before the pair waves reach the block barrier.
-template <int L, bool TAIL>
+// STUDENT (the SMM-SVAE's minibatch step, vmp_svae_estep_bwd_tail_t): Student-t theta (nu = a.nu), trainable - every pair wave also
+// sums the theta-term adjoint of its two samples (dL/dm = -W^T c y, dL/dW = c y d^T, c = (nu+L)/(nu+delta^2); the generic kernel's
+// arithmetic), and these L + TRI per-pair sums meet in wave 0 in a SECOND round through the same LDS area (both rounds at once would
+// need 2 x 8 x 44 x 64 floats at L = 8, S = 16: more than the 160 KiB of a CU).  The partial row then carries its theta half
+// (words TH..2TH-1: g_mk | g_Wk lower | g_kappa), the layout vmp_svae_bwd_reduce reads for nu != NULL.
+template <int L, bool TAIL, bool STUDENT = false>
 __global__ __launch_bounds__(BWD1_MAX_PAIRS * WAVE) void svae_estep_bwd1_kernel(EBwdArgs a) {
     constexpr int TRI = SvGeo<L>::TRI, TH = L + TRI + 1, PW = 2 * TH, NV = L + TRI;
+    constexpr int PWA = STUDENT ? PW : TH;                  // accumulator rows of wave 0's epilogue
     constexpr int AST = SV_AST;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
@@ -34,14 +40,15 @@ __global__ __launch_bounds__(BWD1_MAX_PAIRS * WAVE) void svae_estep_bwd1_kernel(
     const bool tailw = TAIL && nw > np;
     float* scr = smem + wave * WAVE;                         // [nw][64] row-reduction scratch (the tail wave's slot: dLoss/dlog_z of the cells)
     float* red = smem + nw * WAVE;                           // [np][NV][64] per-pair sums
-    float* accl = red;                                       // wave 0, after the sums are read: [TH][AST] per-lane values of the tile
-    float* rows = red + TH * AST;                            //                                  [2L][AST] row-sum scratch
+    float* accl = red;                                       // wave 0, after the sums are read: [PWA][AST] per-lane values of the tile
+    float* rows = red + PWA * AST;                           //                                  [2L][AST] row-sum scratch
     const bool lane_on = lane < CT;
     const int r = lane / K, k = lane - r * K, rbase = lane_on ? r * K : 0, kc = lane_on ? k : 0;
     const long long t = blockIdx.x, row = t * RPT + r;
     const bool on = lane_on && row < a.N;
     const long long rowc = on ? row : 0, cellid = rowc * K + kc;
     float Lm[TRI], mu[L], Wsum[L], M[TRI];
+    float Tm[STUDENT ? L : 1], Tw[STUDENT ? TRI : 1];        // STUDENT: theta-side sums (dL/dm, dL/dW lower) of this wave's samples
     float glzv = 0.f, gT = 0.f;
     const float lzv = a.lz[cellid];
     if (TAIL && (tailw ? wave == np : wave == 0)) {
@@ -110,6 +117,15 @@ __global__ __launch_bounds__(BWD1_MAX_PAIRS * WAVE) void svae_estep_bwd1_kernel(
     solve_lower_t<L>(Lm, mu);                               // mu~ = Pt^-1 ht
     gT = on ? gTv : 0.f;
     const float gts = gT * (1.0f / (float)S);
+    float nuk = 1.f;
+    if constexpr (STUDENT) {
+        const float nv = a.nu[kc];
+        nuk = lane_on ? nv : 1.f;
+#pragma unroll
+        for (int i = 0; i < L; ++i) Tm[i] = 0.f;
+#pragma unroll
+        for (int i = 0; i < TRI; ++i) Tw[i] = 0.f;
+    }
     // ---- this wave's two samples
 #pragma unroll
     for (int i = 0; i < L; ++i) Wsum[i] = 0.f;
@@ -121,18 +137,39 @@ __global__ __launch_bounds__(BWD1_MAX_PAIRS * WAVE) void svae_estep_bwd1_kernel(
         float xs[L], gx[L], d[L], y[L];
 #pragma unroll
         for (int i = 0; i < L; ++i) { xs[i] = xp[h * L + i]; gx[i] = gp[h * L + i]; d[i] = xs[i] - mkk[i]; }
+        float del2 = 0.f;
 #pragma unroll
         for (int i = 0; i < L; ++i) {
             float yy = 0.f;
 #pragma unroll
             for (int j = 0; j <= i; ++j) yy = fmaf(Wt[tri(i, j)], d[j], yy);
             y[i] = yy;
+            if (STUDENT) del2 = fmaf(yy, yy, del2);
         }
+        // d/dx of the theta term of T':  (1/S) c_s W^T W (x - m),  c_s = 1 (Gaussian) or (nu+L)/(nu+delta^2)
+        const float gc = STUDENT ? gts * (nuk + (float)L) / (nuk + del2) : gts;
 #pragma unroll
         for (int i = 0; i < L; ++i) {
-            const float gy = gts * y[i];
+            const float gy = gc * y[i];
 #pragma unroll
             for (int j = 0; j <= i; ++j) gx[j] = fmaf(Wt[tri(i, j)], gy, gx[j]);
+        }
+        if constexpr (STUDENT) {
+            // theta is trainable in the SMM model: d/dm = -(the x-gradient of the theta term), d/dW = c y d^T (off cells: gts = 0)
+            float tx[L];
+#pragma unroll
+            for (int j = 0; j < L; ++j) tx[j] = 0.f;
+#pragma unroll
+            for (int i = 0; i < L; ++i) {
+                const float gy = gc * y[i];
+#pragma unroll
+                for (int j = 0; j <= i; ++j) {
+                    tx[j] = fmaf(Wt[tri(i, j)], gy, tx[j]);
+                    Tw[tri(i, j)] = fmaf(gy, d[j], Tw[tri(i, j)]);
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < L; ++j) Tm[j] -= tx[j];
         }
         solve_lower<L>(Lm, gx);                             // w_s = Lt^-1 gx_s
 #pragma unroll
@@ -161,7 +198,37 @@ __global__ __launch_bounds__(BWD1_MAX_PAIRS * WAVE) void svae_estep_bwd1_kernel(
 #pragma unroll
         for (int i = 0; i < TRI; ++i) M[i] += rw[(L + i) * WAVE];
     }
+    }   // wave 0
+    if constexpr (STUDENT) {
+        // second round: the theta-side sums of the pair waves 1.. through the same LDS area, once wave 0 has read the first
+        __syncthreads();
+        if (wave > 0 && wave < np) {
+            float* rw = red + wave * (NV * WAVE) + lane;
+#pragma unroll
+            for (int i = 0; i < L; ++i) rw[i * WAVE] = Tm[i];
+#pragma unroll
+            for (int i = 0; i < TRI; ++i) rw[(L + i) * WAVE] = Tw[i];
+        }
+        __syncthreads();
+        if (wave == 0) {
+            for (int w = 1; w < np; ++w) {
+                const float* rw = red + w * (NV * WAVE) + lane;
+#pragma unroll
+                for (int i = 0; i < L; ++i) Tm[i] += rw[i * WAVE];
+#pragma unroll
+                for (int i = 0; i < TRI; ++i) Tw[i] += rw[(L + i) * WAVE];
+            }
+        }
+    }
+    if (wave == 0) {
     __builtin_amdgcn_wave_barrier();                         // (accl / rows below overlay the sums just read)
+    if constexpr (STUDENT) {                                 // theta half of the tile's values; T' has -kappa_k
+#pragma unroll
+        for (int i = 0; i < L; ++i) accl[(TH + i) * AST + lane] = on ? Tm[i] : 0.f;
+#pragma unroll
+        for (int i = 0; i < TRI; ++i) accl[(TH + L + i) * AST + lane] = on ? Tw[i] : 0.f;
+        accl[(TH + L + TRI) * AST + lane] = on ? -gT : 0.f;
+    }
     const float glz = on ? glzv : 0.f;
     const float rnk = on ? __expf(lzv) : 0.f;
     const float gsum = row_sum(glz, scr, lane, rbase, K);
@@ -260,25 +327,25 @@ __global__ __launch_bounds__(BWD1_MAX_PAIRS * WAVE) void svae_estep_bwd1_kernel(
     for (int e = threadIdx.x; e < K * PW; e += blockDim.x) {
         const int kk = e / PW, f = e - kk * PW;
         float sq = 0.f;
-        if (f < TH)
+        if (f < PWA)
             for (int rr = 0; rr < RPT; ++rr) sq += accl[f * AST + rr * K + kk];
         out[e] = sq;
     }
 }
 
-template <int L, bool TAIL>
+template <int L, bool TAIL, bool STUDENT = false>
 int launch_bwd1(const EBwdArgs& a, int ntiles, int P, void* stream) {
     constexpr int TRI = L * (L + 1) / 2;
     constexpr int NV = L + TRI;
     constexpr int TH = L + TRI + 1;
-    const int epi = TH * SV_AST + 2 * L * SV_AST;
+    const int epi = (STUDENT ? 2 * TH : TH) * SV_AST + 2 * L * SV_AST;
     const int work = P * NV * WAVE > epi ? P * NV * WAVE : epi;
     const int nwv = (TAIL && P < BWD1_MAX_PAIRS) ? P + 1 : P;       // the tail wave (with S = 16 the block is full: wave 0 runs the tail)
     const size_t lds1 = (size_t)(nwv * WAVE + work) * sizeof(float);
     if (lds1 > 48 * 1024) {
-        if (const int rc = set_dyn_lds(reinterpret_cast<const void*>(svae_estep_bwd1_kernel<L, TAIL>), lds1, "svae_estep_bwd1_kernel")) return rc;
+        if (const int rc = set_dyn_lds(reinterpret_cast<const void*>(svae_estep_bwd1_kernel<L, TAIL, STUDENT>), lds1, "svae_estep_bwd1_kernel")) return rc;
     }
-    hipLaunchKernelGGL((svae_estep_bwd1_kernel<L, TAIL>), dim3(ntiles), dim3(nwv * WAVE), lds1, static_cast<hipStream_t>(stream), a);
+    hipLaunchKernelGGL((svae_estep_bwd1_kernel<L, TAIL, STUDENT>), dim3(ntiles), dim3(nwv * WAVE), lds1, static_cast<hipStream_t>(stream), a);
     return check_launch("svae_estep_bwd1_kernel");
 }
 
@@ -292,5 +359,14 @@ int svae_bwd1_launch(const EBwdArgs& a, int L, int ntiles, int P, bool tail, voi
         default: return -1;
     }
 #undef BWD1_CASE
+}
+// Student-t theta, with the ELBO's scalar tail (vmp_svae_estep_bwd_tail_t): the theta half of every partial row is written
+int svae_bwd1_t_launch(const EBwdArgs& a, int L, int ntiles, int P, void* stream) {
+#define BWD1T_CASE(LL) case LL: return launch_bwd1<LL, true, true>(a, ntiles, P, stream)
+    switch (L) {
+        BWD1T_CASE(1); BWD1T_CASE(2); BWD1T_CASE(3); BWD1T_CASE(4); BWD1T_CASE(5); BWD1T_CASE(6); BWD1T_CASE(7); BWD1T_CASE(8);
+        default: return -1;
+    }
+#undef BWD1T_CASE
 }
 }  // namespace vmp

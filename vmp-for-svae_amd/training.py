@@ -283,9 +283,9 @@ class SVAETrainer(object):
         return self._step_back(ctx, _dev_scalars)
 
     def _direct_ok(self, y, noise, z_draws, chunk, u):
-        """Whether _step_direct covers this call: GMM-SVAE, this process's whole minibatch (shard) at once (<= 512 rows, the minibatch
-        forms of the E-step kernels), noise drawn in the kernels, fused encoder / decoder."""
-        if not self.direct_step or self.smm or self.reference_call_order or not self.fused_decoder or self.rng != 'philox':
+        """Whether _step_direct covers this call: GMM- or SMM-SVAE, this process's whole minibatch (shard) at once (<= 512 rows, the
+        minibatch forms of the E-step kernels), noise drawn in the kernels, fused encoder / decoder."""
+        if not self.direct_step or self.reference_call_order or not self.fused_decoder or self.rng != 'philox':
             return False
         if noise is not None or z_draws is not None or u is not None:
             return False
@@ -298,8 +298,9 @@ class SVAETrainer(object):
         ok = self._direct_shapes.get(key)
         if ok is None:
             lib = L.lib()
+            tail_ok = lib.vmp_svae_bwd_tail_applies_t if self.smm else lib.vmp_svae_bwd_tail_applies     # (Student-t / Gaussian theta)
             ok = bool(vae._fused_mlp_eligible(Dy, self.encoder_layers) and vae.fused_decoder_eligible(self.L, self.decoder_layers)
-                      and lib.vmp_svae_rng_in_kernel(self.K, self.L, self.S) and lib.vmp_svae_bwd_tail_applies(rows, self.K, self.L, self.S))
+                      and lib.vmp_svae_rng_in_kernel(self.K, self.L, self.S) and tail_ok(rows, self.K, self.L, self.S))
             self._direct_shapes[key] = ok
         return ok
 
@@ -312,7 +313,11 @@ class SVAETrainer(object):
         gradient, moment and parameter it leaves is bit-identical to that step's (tests/test_svae_gpu.py); the three ELBO scalars
         are summed per tile (fp64) and agree to fp32 rounding.
         pack=True (several ranks): the closing launch updates nothing - moments, gradients and scalars go into the packed fp64 exchange
-        buffer (vmp_svae_step_pack) and the context of _step_exchange / _step_back is returned."""
+        buffer (vmp_svae_step_pack) and the context of _step_exchange / _step_back is returned.
+        SMM-SVAE (self.smm): the same six launches with the Student-t theta (alpha, mu_k, L_k, DoF): launch 1 packs it
+        (vmp_mlp_gauss_head_fwd_prep_smm), launch 4 also writes the theta half of the partial rows (vmp_svae_estep_bwd_tail_t), launch 6
+        (vmp_svae_step_final_smm / _pack_smm) differentiates the packing, runs Adam on the 23 tensors and the N_k-only M-step + CVI of
+        alpha (experiments.py:252-256); stats = N_k (K, 1)."""
         import ctypes
         lib, dev = L.lib(), y.device
         f32 = dict(dtype=torch.float32, device=dev)
@@ -325,8 +330,10 @@ class SVAETrainer(object):
         opt = self.opt
         if not opt._fused_ok():
             raise L.VmpError('SVAETrainer: parameters must be contiguous fp32 GPU tensors')
-        phi, enc, dec = params[:3], params[3:12], params[12:21]
-        prior = [L.dev_f32(t.detach(), 'prior') for t in self.gmm_prior]
+        smm = self.smm
+        nth = 2 if smm else 0                                # theta/mu_k, theta/L_k: trainables between phi_gmm and the encoder
+        phi, th, enc, dec = params[:3], params[3:3 + nth], params[3 + nth:12 + nth], params[12 + nth:21 + nth]
+        prior = [L.dev_f32(t.detach(), 'prior') for t in ([self.gmm_prior] if smm else self.gmm_prior)]
         for t in self.theta:
             if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
                 raise L.VmpError('theta must be contiguous fp32 GPU tensors')
@@ -344,7 +351,7 @@ class SVAETrainer(object):
         PWp = lib.vmp_svae_bwd_partial_words(Ld)
         nb_dec, nb_enc = lib.vmp_decoder_bwd_blocks(N * K * S), lib.vmp_decoder_bwd_blocks(N)
         wsb_dec, wsb_enc = lib.vmp_decoder_workspace_bytes(N, K, S, Ld, U, Dy), lib.vmp_decoder_workspace_bytes(N, 1, 1, Dy, U, Ld)
-        sizes = dict(eta1=4 * N * Ld, eta2d=4 * N * Ld, Lk=4 * K * Ld * Ld, P=4 * K * Ld * Ld, bias=4 * K, mk=4 * K * Ld, Wk=4 * K * Ld * Ld,
+        sizes = dict(eta1=4 * N * Ld, eta2d=4 * N * Ld, Lk=4 * K * Ld * Ld, P=4 * K * Ld * Ld, bias=4 * K, mk=0 if smm else 4 * K * Ld, Wk=4 * K * Ld * Ld,
                      kappa=4 * K, logpi=8 * K, Tp=4 * N * K, r_epi=4 * N * K, dx=4 * N * K * S * Ld, ll=4 * N * K * S, g_eta1=4 * N * Ld,
                      g_eta2d=4 * N * Ld, partials=4 * nt * K * PWp, r=4 * N * K, tail_part=16 * nt, ws_dec=wsb_dec, ws_enc=wsb_enc)
         off, o = {}, 0
@@ -357,38 +364,68 @@ class SVAETrainer(object):
         # 1: encoder (natparam head: eta1, -1/2 var) + recognition unpacking + theta packing (+ a replayed step's scalars from its table)
         mu_k, L_raw, pi_raw = phi
         tab = _dev_scalars[3] if (_dev_scalars is not None and len(_dev_scalars) > 3) else None     # (table, rows, counter, dst16)
-        L.check(lib.vmp_mlp_gauss_head_fwd_prep(L.ptr(y), *pp(enc), N, Dy, Ld, U, -0.5, A('eta1'), A('eta2d'), L.ptr(mu_k), L.ptr(L_raw),
-                                                L.ptr(pi_raw), *pp(self.theta), K, A('Lk'), A('P'), A('bias'), A('mk'), A('Wk'),
-                                                A('kappa'), A('logpi'), L.ptr(tab[0]) if tab else None, tab[1] if tab else 0,
-                                                L.ptr(tab[2]) if tab else None, L.ptr(tab[3]) if tab else None, st),
-                'vmp_mlp_gauss_head_fwd_prep')
+        tab_args = (L.ptr(tab[0]) if tab else None, tab[1] if tab else 0, L.ptr(tab[2]) if tab else None, L.ptr(tab[3]) if tab else None)
+        if smm:
+            alpha, th_mu, th_L, dof = self.theta             # (alpha_nat, mu_k, L_k, DoF); m of the E-step = theta/mu_k itself
+            L.check(lib.vmp_mlp_gauss_head_fwd_prep_smm(L.ptr(y), *pp(enc), N, Dy, Ld, U, -0.5, A('eta1'), A('eta2d'), L.ptr(mu_k),
+                                                        L.ptr(L_raw), L.ptr(pi_raw), L.ptr(alpha), L.ptr(th_L), L.ptr(dof), K, A('Lk'), A('P'),
+                                                        A('bias'), A('Wk'), A('kappa'), A('logpi'), *tab_args, st),
+                    'vmp_mlp_gauss_head_fwd_prep_smm')
+            m_ptr, nu_ptr = L.ptr(th_mu), L.ptr(dof)
+        else:
+            L.check(lib.vmp_mlp_gauss_head_fwd_prep(L.ptr(y), *pp(enc), N, Dy, Ld, U, -0.5, A('eta1'), A('eta2d'), L.ptr(mu_k), L.ptr(L_raw),
+                                                    L.ptr(pi_raw), *pp(self.theta), K, A('Lk'), A('P'), A('bias'), A('mk'), A('Wk'),
+                                                    A('kappa'), A('logpi'), *tab_args, st),
+                    'vmp_mlp_gauss_head_fwd_prep')
+            m_ptr, nu_ptr = A('mk'), None
         # 2: E-step on in-kernel noise; its epilogue draws the one sub-sample per row
         x = torch.empty(N, K, S, Ld, **f32)
         lz = torch.empty(N, K, **f32)
         xs = torch.empty(N, Ld, **f32)
         key = 0 if seed_dev is not None else (self._step_seed(0) & 0xFFFFFFFFFFFFFFFF)
         L.check(lib.vmp_svae_estep_fwd_rng_epi(A('eta1'), A('eta2d'), L.ptr(mu_k), A('P'), A('bias'), key, L.ptr(seed_dev),
-                                               A('mk'), A('Wk'), A('kappa'), None, N, K, Ld, S, L.ptr(x), L.ptr(lz), A('Tp'),
+                                               m_ptr, A('Wk'), A('kappa'), nu_ptr, N, K, Ld, S, L.ptr(x), L.ptr(lz), A('Tp'),
                                                L.ptr(xs), A('r_epi'), None, 0, st), 'vmp_svae_estep_fwd_rng_epi')
         # 3: decoder value + gradients of loss = -elbo (sigma = -1); parameter partials stay in ws_dec
         L.check(lib.vmp_decoder_elbo_lazy(L.ptr(x), L.ptr(y), L.ptr(lz), -1.0, *pp(dec), N, K, S, Ld, Dy, U, A('dx'), A('ll'),
                                           A('ws_dec'), wsb_dec, st), 'vmp_decoder_elbo_lazy')
-        # 4: ELBO tail + E-step backward
-        L.check(lib.vmp_svae_estep_bwd_tail(A('eta1'), A('eta2d'), L.ptr(mu_k), A('P'), A('bias'), A('mk'), A('Wk'),
-                                            L.ptr(x), L.ptr(lz), A('Tp'), A('ll'), -1.0, A('dx'), N, K, Ld, S, A('g_eta1'),
-                                            A('g_eta2d'), A('partials'), sizes['partials'], A('r'), A('tail_part'),
-                                            sizes['tail_part'], st), 'vmp_svae_estep_bwd_tail')
+        # 4: ELBO tail + E-step backward (SMM: with the theta half of the partial rows)
+        if smm:
+            L.check(lib.vmp_svae_estep_bwd_tail_t(A('eta1'), A('eta2d'), L.ptr(mu_k), A('P'), A('bias'), m_ptr, A('Wk'), nu_ptr,
+                                                  L.ptr(x), L.ptr(lz), A('Tp'), A('ll'), -1.0, A('dx'), N, K, Ld, S, A('g_eta1'),
+                                                  A('g_eta2d'), A('partials'), sizes['partials'], A('r'), A('tail_part'),
+                                                  sizes['tail_part'], st), 'vmp_svae_estep_bwd_tail_t')
+        else:
+            L.check(lib.vmp_svae_estep_bwd_tail(A('eta1'), A('eta2d'), L.ptr(mu_k), A('P'), A('bias'), A('mk'), A('Wk'),
+                                                L.ptr(x), L.ptr(lz), A('Tp'), A('ll'), -1.0, A('dx'), N, K, Ld, S, A('g_eta1'),
+                                                A('g_eta2d'), A('partials'), sizes['partials'], A('r'), A('tail_part'),
+                                                sizes['tail_part'], st), 'vmp_svae_estep_bwd_tail')
         # 5: encoder backward; parameter partials stay in ws_enc
         L.check(lib.vmp_mlp_gauss_head_bwd_lazy(L.ptr(y), A('g_eta1'), A('g_eta2d'), -0.5, *pp(enc), N, Dy, Ld, U, None,
                                                 A('ws_enc'), wsb_enc, st), 'vmp_mlp_gauss_head_bwd_lazy')
         # 6: the closing launch (phi_gmm gradients from the partial rows, both MLP reductions, Adam, moments + CVI, ELBO scalars)
         g_phi = [torch.empty_like(t) for t in phi]
+        g_th = [torch.empty_like(t) for t in th]
         g_enc, g_dec = [torch.empty_like(t) for t in enc], [torch.empty_like(t) for t in dec]
-        stats = torch.empty(K, 2 + Ld + Ld * Ld, dtype=torch.float64, device=dev)
-        star = [torch.empty_like(t) for t in self.theta]
+        SW = 1 if smm else 2 + Ld + Ld * Ld                  # SMM: N_k only (svae.m_step_smm)
+        stats = torch.empty(K, SW, dtype=torch.float64, device=dev)
+        star = [torch.empty_like(t) for t in (self.theta[:1] if smm else self.theta)]
         scal = torch.empty(3, **f32)
+        if pack and smm:
+            sizes = [p.numel() for p in params]
+            goffs, o = [], K * SW
+            for n_ in sizes:
+                goffs.append(o)
+                o += n_
+            buf = torch.empty(o + 3, dtype=torch.float64, device=dev)
+            L.check(lib.vmp_svae_step_pack_smm(L.ptr(buf), buf.numel(), A('ws_dec'), nb_dec, Ld, U, Dy, arr(dec), arr(g_dec), A('ws_enc'),
+                                               nb_enc, Dy, U, Ld, arr(enc), arr(g_enc), A('partials'), nt, A('logpi'), arr(phi), arr(g_phi),
+                                               arr(th), arr(g_th), A('r'), N, K, Ld, A('tail_part'), nt, Dy, L.ptr(scal), st),
+                    'vmp_svae_step_pack_smm')
+            return dict(world=self._world(), names=names, params=params, grads=g_phi + g_th + g_enc + g_dec, stats=buf[:K * SW].view(K, SW),
+                        fused_m=False, keep=dict(log_z=lz, x_samples=xs, x_k=x), r_whole=None, scal=(scal[0], scal[1], scal[2]), buf=buf,
+                        goffs=goffs, mom_whole=None)
         if pack:
-            SW = 2 + Ld + Ld * Ld
             sizes = [p.numel() for p in params]
             goffs, o = [], K * SW
             for n_ in sizes:
@@ -407,18 +444,27 @@ class SVAETrainer(object):
         else:
             lr_t = 0.0
         m, v = opt.m, opt.v
-        L.check(lib.vmp_svae_step_final(A('ws_dec'), nb_dec, Ld, U, Dy, arr(dec), arr(m[12:21]), arr(v[12:21]), arr(g_dec),
-                                        A('ws_enc'), nb_enc, Dy, U, Ld, arr(enc), arr(m[3:12]), arr(v[3:12]), arr(g_enc),
-                                        A('partials'), nt, A('logpi'), arr(phi), arr(g_phi), arr(m[:3]), arr(v[:3]), L.ptr(xs),
-                                        A('r'), N,
-                                        arr(prior), arr(self.theta), arr(star), L.ptr(rho_dev),
-                                        0.0 if rho_dev is not None else float(lrcvi), K, Ld, L.ptr(stats), A('tail_part'), nt, Dy,
-                                        L.ptr(scal), opt.b1, opt.b2, opt.eps, lr_t, L.ptr(lr_dev), st), 'vmp_svae_step_final')
+        if smm:
+            L.check(lib.vmp_svae_step_final_smm(A('ws_dec'), nb_dec, Ld, U, Dy, arr(dec), arr(m[14:23]), arr(v[14:23]), arr(g_dec),
+                                                A('ws_enc'), nb_enc, Dy, U, Ld, arr(enc), arr(m[5:14]), arr(v[5:14]), arr(g_enc),
+                                                A('partials'), nt, A('logpi'), arr(phi), arr(g_phi), arr(m[:3]), arr(v[:3]),
+                                                arr(th), arr(g_th), arr(m[3:5]), arr(v[3:5]), A('r'), N, L.ptr(prior[0]),
+                                                L.ptr(self.theta[0]), L.ptr(star[0]), L.ptr(rho_dev),
+                                                0.0 if rho_dev is not None else float(lrcvi), K, Ld, L.ptr(stats), A('tail_part'), nt, Dy,
+                                                L.ptr(scal), opt.b1, opt.b2, opt.eps, lr_t, L.ptr(lr_dev), st), 'vmp_svae_step_final_smm')
+        else:
+            L.check(lib.vmp_svae_step_final(A('ws_dec'), nb_dec, Ld, U, Dy, arr(dec), arr(m[12:21]), arr(v[12:21]), arr(g_dec),
+                                            A('ws_enc'), nb_enc, Dy, U, Ld, arr(enc), arr(m[3:12]), arr(v[3:12]), arr(g_enc),
+                                            A('partials'), nt, A('logpi'), arr(phi), arr(g_phi), arr(m[:3]), arr(v[:3]), L.ptr(xs),
+                                            A('r'), N,
+                                            arr(prior), arr(self.theta), arr(star), L.ptr(rho_dev),
+                                            0.0 if rho_dev is not None else float(lrcvi), K, Ld, L.ptr(stats), A('tail_part'), nt, Dy,
+                                            L.ptr(scal), opt.b1, opt.b2, opt.eps, lr_t, L.ptr(lr_dev), st), 'vmp_svae_step_final')
         for t in list(params) + list(self.theta):
             torch.autograd.graph.increment_version(t)
         if _dev_scalars is None:
             self.global_step += 1
-        return dict(elbo=scal[0], neg_rec_err=scal[1], regulariser=scal[2], grads=dict(zip(names, g_phi + g_enc + g_dec)),
+        return dict(elbo=scal[0], neg_rec_err=scal[1], regulariser=scal[2], grads=dict(zip(names, g_phi + g_th + g_enc + g_dec)),
                     theta_star=star, lrcvi=lrcvi, log_z=lz, x_samples=xs, x_k=x, stats=stats)
 
     def _world(self):
@@ -597,7 +643,7 @@ class GraphedSVAEStep(object):
         self._counter = torch.zeros(1, dtype=torch.int64, device=dev) if self.table_mode else None
         self._table_base, self._table_used = None, 0
         if self.n_steps > 1 and not self.table_mode:
-            raise L.VmpError('GraphedSVAEStep: steps_per_replay > 1 needs the direct single-process GMM step on in-kernel noise')
+            raise L.VmpError('GraphedSVAEStep: steps_per_replay > 1 needs the direct single-process step (GMM or SMM) on in-kernel noise')
         # Warm-up steps (they create the variables / Adam slots and size the workspaces) must not train: everything a
         # step mutates is snapshotted first and put back before the capture, so that call number i of this object
         # is training step number i of the eager trainer (and of the reference).

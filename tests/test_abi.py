@@ -27,6 +27,63 @@ def test_header_symbols_exported():
     assert lib.vmp_abi_version() == 1
 
 
+def _c_kind(decl):
+    """(kind, bytes) of a C parameter or return type as the header writes it: any pointer is ('ptr', 8)"""
+    if '*' in decl:
+        return ('ptr', ctypes.sizeof(ctypes.c_void_p))
+    words = [w for w in decl.split() if w != 'const']
+    for n in range(len(words), 0, -1):                           # the longest leading run of words that names a type; the rest is the name
+        kind = {'int': ('int', ctypes.sizeof(ctypes.c_int)), 'int64_t': ('int', 8), 'uint64_t': ('uint', 8),
+                'unsigned long long': ('uint', ctypes.sizeof(ctypes.c_ulonglong)), 'size_t': ('uint', ctypes.sizeof(ctypes.c_size_t)),
+                'float': ('float', 4), 'double': ('float', 8), 'void': ('void', 0)}.get(' '.join(words[:n]))
+        if kind is not None and len(words) - n <= 1:
+            return kind
+    raise AssertionError('type not understood: %r' % decl)
+
+
+def _ctypes_kind(t):
+    if t is None:
+        return ('void', 0)
+    if t in (ctypes.c_void_p, ctypes.c_char_p) or issubclass(t, ctypes._Pointer):
+        return ('ptr', ctypes.sizeof(t))
+    code = t._type_                                               # struct-module letter of a simple ctypes class
+    if code in 'fd':
+        return ('float', ctypes.sizeof(t))
+    assert code in 'bhilqBHILQ', t
+    return ('int' if code.islower() else 'uint', ctypes.sizeof(t))
+
+
+def _prototypes():
+    """{name: (return declaration, [parameter declarations])} of every prototype in include/vmp_hip.h"""
+    txt = open(os.path.join(ROOT, 'include', 'vmp_hip.h')).read()
+    txt = re.sub(r'/\*.*?\*/', '', txt, flags=re.S)
+    txt = re.sub(r'//[^\n]*', '', txt)
+    txt = re.sub(r'^\s*#[^\n]*', '', txt, flags=re.M)
+    out = {}
+    for ret, name, args in re.findall(r'([A-Za-z_][\w\s]*?[\s\*]+)(vmp_[a-z0-9_]+)\s*\(([^()]*)\)\s*;', txt):
+        assert name not in out, name
+        args = args.strip()
+        out[name] = (ret.strip(), [] if args in ('', 'void') else [a.strip() for a in args.split(',')])
+    return out
+
+
+def test_ctypes_table_matches_header_prototypes():
+    """_lib._SIGNATURES repeats every prototype of include/vmp_hip.h by hand, and ctypes converts to whatever the table says: a c_int
+    where the header has int64_t, or a missing pointer, is garbage in a register of a 50-argument call, not an error.  Every prototype,
+    argument by argument and the return type, by kind (pointer / signed / unsigned / floating) and byte width - c_uint64, c_size_t and
+    c_ulong are one ctypes class on LP64, and the header writes one uint64 parameter as unsigned long long."""
+    import vmp_for_svae_amd as V
+    protos = _prototypes()
+    assert sorted(protos) == _declared(), sorted(set(_declared()) ^ set(protos))      # no prototype escapes the pattern
+    assert sorted(V._lib._SIGNATURES) == sorted(protos)
+    for name, (ret, args) in sorted(protos.items()):
+        res, argtypes = V._lib._SIGNATURES[name]
+        assert _ctypes_kind(res) == _c_kind(ret), (name, 'return', ret, res)
+        assert len(argtypes) == len(args), (name, len(argtypes), len(args))
+        for i, (decl, t) in enumerate(zip(args, argtypes)):
+            assert _ctypes_kind(t) == _c_kind(decl), (name, i, decl, t)
+
+
 def test_size_helpers():
     import vmp_for_svae_amd as V
     lib = V._lib.lib()
@@ -116,6 +173,22 @@ def test_minibatch_step_entry_points_validate_on_the_host():
     assert fin(64, 0) != 0                                                                                                  # no partial rows
     rc = lib.vmp_svae_step_pack(P, 10, P, 100, 8, 50, 6, arr, arr, P, 1, 6, 50, 8, arr, arr, P, 11, P, arr, arr, P, P, 64, 10, 8, P, 11, 6, P, None)
     assert rc != 0 and b'too small' in lib.vmp_last_error()
+    # The closing launch checks its pointers by form: each one that vmp_svae_step_final / _pack reads is refused when NULL (VMP_E_BADARG
+    # = -1); with every one that it does NOT read NULL (theta_star, the device words of the step sizes, the stream) the call gets past
+    # the pointer checks and fails on the size check behind them (N = 513: VMP_E_DIM = -2) - nothing is launched either way.
+    nul = (ctypes.c_void_p * 9)(*([0] + [64] * 8))                                                                         # an array whose first tensor is NULL
+    final = [P, 100, 8, 50, 6, arr, arr, arr, arr, P, 1, 6, 50, 8, arr, arr, arr, arr, P, 11, P, arr, arr, arr, arr, P, P, 64, arr, arr, arr, P, 0.2,
+             10, 8, P, P, 11, 6, P, 0.9, 0.999, 1e-8, 1e-3, P, None]
+    pack = [P, 1 << 20, P, 100, 8, 50, 6, arr, arr, P, 1, 6, 50, 8, arr, arr, P, 11, P, arr, arr, P, P, 64, 10, 8, P, 11, 6, P, None]
+    for fn, args, n_at, needed, unread in ((lib.vmp_svae_step_final, final, 27, (0, 5, 6, 7, 8, 9, 14, 15, 16, 17, 18, 20, 21, 22, 23, 24, 25, 26, 28, 29, 35, 36, 39),
+                                            (30, 31, 44, 45)),
+                                           (lib.vmp_svae_step_pack, pack, 23, (0, 2, 7, 8, 9, 14, 15, 16, 18, 19, 20, 21, 22, 26, 29), (30,))):
+        for i in needed:
+            assert fn(*[None if j == i else a for j, a in enumerate(args)]) == -1 and b'NULL' in lib.vmp_last_error(), (fn.__name__, i)
+            if args[i] is arr:
+                assert fn(*[nul if j == i else a for j, a in enumerate(args)]) == -1 and b'NULL' in lib.vmp_last_error(), (fn.__name__, i)
+        rest = [None if j in unread else (513 if j == n_at else a) for j, a in enumerate(args)]
+        assert fn(*rest) == -2 and b'range' in lib.vmp_last_error(), fn.__name__
 
 
 def test_no_cpu_fallback():

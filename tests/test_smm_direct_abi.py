@@ -69,6 +69,22 @@ def test_smm_step_entry_points_validate_on_the_host():
                                                         arr, P, 64, 16, 8, P, 16, 8, P, None)
     assert pack(10) != 0 and b'too small' in lib.vmp_last_error()
     assert pack(1 << 20, xbuf=None) != 0 and b'NULL' in lib.vmp_last_error()
+    # The closing launch checks its pointers by form: each one that vmp_svae_step_final_smm / _pack_smm reads is refused when NULL
+    # (VMP_E_BADARG = -1); with every one that it does NOT read NULL (alpha_star, the device words of the step sizes, the stream) the
+    # call gets past the pointer checks and fails on the size check behind them (N = 513: VMP_E_DIM = -2) - nothing is launched either way.
+    nul = (ctypes.c_void_p * 9)(*([0] + [64] * 8))                              # an array whose first tensor is NULL
+    final = [P, 100, 8, 50, 8, arr, arr, arr, arr, P, 1, 8, 50, 8, arr, arr, arr, arr, P, 16, P, arr, arr, arr, arr, arr, arr, arr, arr, P, 64, P, P, P,
+             P, 0.2, 16, 8, P, P, 16, 8, P, 0.9, 0.999, 1e-8, 1e-3, P, None]
+    packed = [P, 1 << 20, P, 100, 8, 50, 8, arr, arr, P, 1, 8, 50, 8, arr, arr, P, 16, P, arr, arr, arr, arr, P, 64, 16, 8, P, 16, 8, P, None]
+    for fn, args, n_at, needed, unread in ((lib.vmp_svae_step_final_smm, final, 30, (0, 5, 6, 7, 8, 9, 14, 15, 16, 17, 18, 20, 21, 22, 23, 24, 25, 26, 27, 28, 29, 31, 32,
+                                                                                38, 39, 42), (33, 34, 47, 48)),
+                                           (lib.vmp_svae_step_pack_smm, packed, 24, (0, 2, 7, 8, 9, 14, 15, 16, 18, 19, 20, 21, 22, 23, 27, 30), (31,))):
+        for i in needed:
+            assert fn(*[None if j == i else a for j, a in enumerate(args)]) == -1 and b'NULL' in lib.vmp_last_error(), (fn.__name__, i)
+            if args[i] is arr:
+                assert fn(*[nul if j == i else a for j, a in enumerate(args)]) == -1 and b'NULL' in lib.vmp_last_error(), (fn.__name__, i)
+        rest = [None if j in unread else (513 if j == n_at else a) for j, a in enumerate(args)]
+        assert fn(*rest) == -2 and b'range' in lib.vmp_last_error(), fn.__name__
 
 
 def _kernel_notes(pattern):

@@ -344,6 +344,170 @@ __global__ __launch_bounds__(FIN_THREADS) void step_final_kernel(FinArgs a) {
     }
 }
 
+// ---- host side of the closing launch ------------------------------------------------------------------------------
+// One closing launch, described by name: the four entry points below fill this and call step_final_launch.  `pack` (data-parallel
+// form: nothing is updated; moments, gradients and scalars go into xbuf) and `smm` (Student-t theta) say which form it is.  A field
+// that the form does not use stays NULL and never reaches FinArgs.
+struct FinSpec {
+    const char* what;
+    bool pack, smm;
+    struct Tensors { float* const* p; float* const* g; float* const* m; float* const* v; };   // values, gradients out; Adam's slots: !pack
+    struct Net {
+        const float* part;                   // per-block partial rows of the fused MLP backward kernel
+        int blocks, in, units, out;
+        Tensors w;                           // 9 tensors, the reference's variable order
+    } net[2];                                // decoder, encoder
+    Tensors phi;                             // phi_gmm/mu_k (K,L), L_k (K,L,L), log_pi_k (K)
+    const float* partials; int nblk; const double* logpi;      // partial rows of the E-step backward kernel, the forward pass's log pi
+    const float* x_samples;                  // (!smm)
+    const float* const* prior;               // (!smm, !pack) 5 tensors
+    float* const* theta;                     // (!smm, !pack) 5 tensors
+    float* const* theta_star;                // (!smm, !pack) may be NULL
+    Tensors th;                              // (smm) theta/mu_k (K,L), theta/L_k (K,L,L)
+    const float* prior_alpha; float* alpha;  // (smm, !pack)
+    float* alpha_star;                       // (smm, !pack) may be NULL
+    const float* r; int64_t N; int K, L;
+    const float* rho_dev; float rho;         // CVI step size: device word, or by value
+    double* stats_out;                       // (!pack)
+    const double* tail_part; int tail_n, Dy; float* scalars;
+    double beta1, beta2, eps, lr_t; const float* lr_t_dev;
+    double* xbuf; size_t xbuf_doubles;       // (pack)
+    void* stream;
+};
+
+// The fp64 exchange buffer of a data-parallel step, offsets in doubles: [moments (K, 2+L+L*L; SMM: N_k (K, 1)) | phi_gmm/mu_k, L_k,
+// log_pi_k | SMM: theta/mu_k, theta/L_k | encoder net | decoder net | elbo, rec, reg] - the parameter order of
+// SVAETrainer.trainables() (experiments.py:160-181), as training.exchange_layout lays it out.
+struct XLayout { size_t phi[3], theta[2], net[2], scal, total; };       // (net: decoder, encoder - the order of FinArgs)
+XLayout exchange_layout(int K, int L, int enc_words, int dec_words, bool smm) {
+    XLayout x{};
+    const size_t KL = (size_t)K * L;
+    size_t o = smm ? (size_t)K : (size_t)K * (2 + L + L * L);
+    x.phi[0] = o; o += KL;
+    x.phi[1] = o; o += KL * L;
+    x.phi[2] = o; o += K;
+    if (smm) {
+        x.theta[0] = o; o += KL;
+        x.theta[1] = o; o += KL * L;
+    }
+    x.net[1] = o; o += enc_words;
+    x.net[0] = o; o += dec_words;
+    x.scal = o;
+    x.total = o + 3;
+    return x;
+}
+
+template <bool SMM>
+void step_final_dispatch(int L, unsigned blocks, void* stream, const FinArgs& a) {
+#define FIN_CALL(LL) case LL: hipLaunchKernelGGL((step_final_kernel<LL, SMM>), dim3(blocks), dim3(FIN_THREADS), 0, static_cast<hipStream_t>(stream), a); break
+    switch (L) { FIN_CALL(1); FIN_CALL(2); FIN_CALL(3); FIN_CALL(4); FIN_CALL(5); FIN_CALL(6); FIN_CALL(7); default: FIN_CALL(8); }
+#undef FIN_CALL
+}
+
+template <class T>
+bool all_set(T* const* a, int n) {           // the array and its n pointers
+    for (int t = 0; a && t < n; ++t)
+        if (!a[t]) return false;
+    return a != nullptr;
+}
+bool tensors_set(const FinSpec::Tensors& w, int n, bool adam) {
+    return all_set(w.p, n) && all_set(w.g, n) && (!adam || (all_set(w.m, n) && all_set(w.v, n)));
+}
+
+int step_final_launch(const FinSpec& s) {
+    const bool upd = !s.pack;
+    const int K = s.K, L = s.L;
+    // pointers first, by what the form reads, then sizes: nothing is launched before both have passed
+    bool ok = s.partials && s.nblk >= 1 && s.logpi && s.r && s.tail_part && s.scalars && tensors_set(s.phi, 3, upd);
+    for (const FinSpec::Net& n : s.net) ok = ok && n.part && n.blocks >= 1 && tensors_set(n.w, FIN_NET_TENSORS, upd);
+    ok = ok && (s.pack ? s.xbuf != nullptr : s.stats_out != nullptr);
+    if (s.smm) ok = ok && tensors_set(s.th, 2, upd) && (s.pack || (s.prior_alpha && s.alpha));
+    else ok = ok && s.x_samples && (s.pack || (all_set(s.prior, 5) && all_set(s.theta, 5)));
+    if (!ok) {
+        set_error("%s: NULL argument", s.what);
+        return VMP_E_BADARG;
+    }
+    if (K < 1 || K > VMP_MAX_K || L < 1 || L > VMP_MAX_D || s.N < 1 || s.N > SMALL_STATS_MAX_N || s.tail_n < 1 || s.tail_n > TAIL_MAX_BLOCKS ||
+        s.Dy < 1) {
+        set_error("%s: K=%d L=%d N=%lld tail_n=%d outside the minibatch step's range (N <= %d)", s.what, K, L, (long long)s.N, s.tail_n,
+                  SMALL_STATS_MAX_N);
+        return VMP_E_DIM;
+    }
+    FinArgs a{};
+    for (int n = 0; n < 2; ++n) {
+        const FinSpec::Net& w = s.net[n];
+        const int Li = w.in, U = w.units, Do = w.out;
+        if (Li < 1 || Li > 8 || Do < 1 || Do > 8 || U < 1 || U > 64) {
+            set_error("%s: net %d sizes in=%d units=%d out=%d outside the fused MLP's range", s.what, n, Li, U, Do);
+            return VMP_E_DIM;
+        }
+        const int sizes[FIN_NET_TENSORS] = {Li * U, U, U * U, U, U * 2 * Do, 2 * Do, Li * Do, Do, Do};   // the reference's variable order
+        FinNet& q = a.net[n];
+        int o = 0;
+        for (int t = 0; t < FIN_NET_TENSORS; ++t) {
+            q.p[t] = w.w.p[t]; q.g[t] = w.w.g[t];
+            if (upd) { q.m[t] = w.w.m[t]; q.v[t] = w.w.v[t]; }
+            q.off[t] = o;
+            o += sizes[t];
+        }
+        q.off[FIN_NET_TENSORS] = o;
+        if (o != vmp_decoder_param_words(Li, U, Do)) {
+            set_error("%s: parameter layout mismatch (%d != %d words)", s.what, o, vmp_decoder_param_words(Li, U, Do));
+            return VMP_E_DIM;
+        }
+        q.red = DecRedArgs{w.part, q.p[FIN_NET_TENSORS - 1], nullptr, w.blocks, o, o - Do, Do};
+        q.nb = (o + 63) / 64;
+    }
+    const XLayout x = exchange_layout(K, L, a.net[1].red.PW, a.net[0].red.PW, s.smm);
+    if (s.pack && s.xbuf_doubles < x.total) {
+        set_error("%s: exchange buffer too small (%zu < %zu doubles)", s.what, s.xbuf_doubles, x.total);
+        return VMP_E_WS;
+    }
+    for (int t = 0; t < 3; ++t) {
+        if (upd) { a.phi_adam.p[t] = s.phi.p[t]; a.phi_adam.m[t] = s.phi.m[t]; a.phi_adam.v[t] = s.phi.v[t]; }
+        else a.phi_adam.gx[t] = s.xbuf + x.phi[t];
+    }
+    if (s.pack) {
+        for (int n = 0; n < 2; ++n) a.xnet[n] = s.xbuf + x.net[n];
+        a.xscal = s.xbuf + x.scal;
+    }
+    a.phi.mu = s.phi.p[0]; a.phi.Lraw = s.phi.p[1]; a.phi.piraw = s.phi.p[2]; a.phi.logpi = s.logpi;
+    a.phi.g_mu = s.phi.g[0]; a.phi.g_Lraw = s.phi.g[1]; a.phi.g_piraw = s.phi.g[2]; a.phi.K = K; a.phi.L = L;
+    a.partials = s.partials; a.nblk = s.nblk;
+    double* const moments = s.pack ? s.xbuf : s.stats_out;  // (the exchange buffer starts with them)
+    if (s.smm) {
+        SmmFin& q = a.smm;
+        for (int t = 0; t < 2; ++t) {
+            q.p[t] = s.th.p[t]; q.g[t] = s.th.g[t];
+            if (upd) { q.m[t] = s.th.m[t]; q.v[t] = s.th.v[t]; }
+            else q.gx[t] = s.xbuf + x.theta[t];
+        }
+        if (upd) { q.prior_alpha = s.prior_alpha; q.alpha = s.alpha; q.alpha_star = s.alpha_star; }
+        q.r = s.r; q.N = (int)s.N; q.nk = moments;
+        q.rho_dev = s.rho_dev; q.rho = s.rho;
+    } else {
+        a.sa = SmallStatsArgs{s.x_samples, s.r, nullptr, moments, (int)s.N, L, K};
+        a.cvi.K = K; a.cvi.L = L;
+        if (upd) {
+            const float* const* pr = s.prior;
+            float* const* th = s.theta;
+            float* const* ts = s.theta_star;
+            a.cvi = CviArgs{moments, pr[0], pr[1], pr[2], pr[3], pr[4], th[0], th[1], th[2], th[3], th[4], ts ? ts[0] : nullptr,
+                            ts ? ts[1] : nullptr, ts ? ts[2] : nullptr, ts ? ts[3] : nullptr, ts ? ts[4] : nullptr, s.rho_dev, s.rho, K, L};
+        }
+    }
+    a.tail.part = const_cast<double*>(s.tail_part);
+    a.tail.scal = s.scalars;
+    a.tail.cst = (double)s.N * s.Dy * 0.5 * 1.8378770664093453;        // log(2 pi): as tail_setup
+    a.tail_n = (unsigned)s.tail_n;
+    a.lr_t_dev = s.lr_t_dev; a.lr_t = (float)s.lr_t; a.b1 = (float)s.beta1; a.b2 = (float)s.beta2;
+    a.c1 = (float)(1.0 - s.beta1); a.c2 = (float)(1.0 - s.beta2); a.eps = (float)s.eps;
+    a.phi_adam.b1 = a.b1; a.phi_adam.b2 = a.b2; a.phi_adam.c1 = a.c1; a.phi_adam.c2 = a.c2; a.phi_adam.eps = a.eps;
+    const unsigned blocks = (unsigned)(a.net[0].nb + a.net[1].nb + 2 * K + 1);     // the roles of step_final_kernel, in its order
+    if (s.smm) step_final_dispatch<true>(L, blocks, s.stream, a);
+    else step_final_dispatch<false>(L, blocks, s.stream, a);
+    return check_launch(s.what);
+}
 }  // namespace
 
 extern "C" {
@@ -377,132 +541,6 @@ int vmp_svae_step_inputs(void* dst16, uint64_t philox_key, float cvi_step, float
     return check_launch("vmp_svae_step_inputs");
 }
 
-namespace {
-int step_final_impl(const char* what, double* xbuf, const float* dec_part, int dec_blocks, int dec_in, int dec_units, int dec_out, float* const* dec_p,
-                        float* const* dec_m, float* const* dec_v, float* const* dec_g, const float* enc_part, int enc_blocks,
-                        int enc_in, int enc_units, int enc_out, float* const* enc_p, float* const* enc_m, float* const* enc_v,
-                        float* const* enc_g, const float* partials, int nblk, const double* logpi, float* const* phi_p,
-                        float* const* phi_g, float* const* phi_m, float* const* phi_v, const float* x_samples, const float* r, int64_t N, const float* const* prior,
-                        float* const* theta, float* const* theta_star, const float* rho_dev, float rho, int K, int L,
-                        double* stats_out, const double* tail_part, int tail_n, int Dy, float* scalars, double beta1, double beta2,
-                        double eps, double lr_t, const float* lr_t_dev, void* stream, const SmmFin* smm = nullptr) {
-    const bool pack = xbuf != nullptr;
-    if (K < 1 || K > VMP_MAX_K || L < 1 || L > VMP_MAX_D || N < 1 || N > SMALL_STATS_MAX_N || tail_n < 1 || tail_n > TAIL_MAX_BLOCKS || Dy < 1) {
-        set_error("%s: K=%d L=%d N=%lld tail_n=%d outside the minibatch step's range (N <= %d)", what, K, L, (long long)N, tail_n,
-                  SMALL_STATS_MAX_N);
-        return VMP_E_DIM;
-    }
-    if (!dec_part || !enc_part || dec_blocks < 1 || enc_blocks < 1 || !dec_p || !dec_m || !dec_v || !dec_g || !enc_p || !enc_m || !enc_v ||
-        !enc_g || !partials || nblk < 1 || !logpi || !phi_p || !phi_g || !phi_m || !phi_v || !x_samples || !r || (!pack && !smm && (!prior || !theta)) ||
-        (!pack && !stats_out) || !tail_part || !scalars) {
-        set_error("%s: NULL argument", what);
-        return VMP_E_BADARG;
-    }
-    FinArgs a{};
-    unsigned blocks = 0;
-    const struct { const float* part; int nblk, in, units, out; float* const* p; float* const* m; float* const* v; float* const* g; } nets[2] = {
-        {dec_part, dec_blocks, dec_in, dec_units, dec_out, dec_p, dec_m, dec_v, dec_g},
-        {enc_part, enc_blocks, enc_in, enc_units, enc_out, enc_p, enc_m, enc_v, enc_g}};
-    for (int n = 0; n < 2; ++n) {
-        const int Li = nets[n].in, U = nets[n].units, Do = nets[n].out;
-        if (Li < 1 || Li > 8 || Do < 1 || Do > 8 || U < 1 || U > 64) {
-            set_error("%s: net %d sizes in=%d units=%d out=%d outside the fused MLP's range", what, n, Li, U, Do);
-            return VMP_E_DIM;
-        }
-        const int sizes[FIN_NET_TENSORS] = {Li * U, U, U * U, U, U * 2 * Do, 2 * Do, Li * Do, Do, Do};   // the reference's variable order
-        FinNet& q = a.net[n];
-        int o = 0;
-        for (int t = 0; t < FIN_NET_TENSORS; ++t) {
-            if (!nets[n].p[t] || !nets[n].m[t] || !nets[n].v[t] || !nets[n].g[t]) {
-                set_error("%s: net %d tensor %d: NULL pointer", what, n, t);
-                return VMP_E_BADARG;
-            }
-            q.p[t] = nets[n].p[t]; q.m[t] = nets[n].m[t]; q.v[t] = nets[n].v[t]; q.g[t] = nets[n].g[t];
-            q.off[t] = o;
-            o += sizes[t];
-        }
-        q.off[FIN_NET_TENSORS] = o;
-        if (o != vmp_decoder_param_words(Li, U, Do)) {
-            set_error("%s: parameter layout mismatch (%d != %d words)", what, o, vmp_decoder_param_words(Li, U, Do));
-            return VMP_E_DIM;
-        }
-        q.red = DecRedArgs{nets[n].part, q.p[FIN_NET_TENSORS - 1], nullptr, nets[n].nblk, o, o - Do, Do};
-        q.nb = (o + 63) / 64;
-        blocks += (unsigned)q.nb;
-    }
-    for (int t = 0; t < 3; ++t) {                           // phi_gmm/mu_k (K,L), L_k (K,L,L), log_pi_k (K)
-        if (!phi_p[t] || !phi_g[t] || !phi_m[t] || !phi_v[t]) { set_error("%s: phi tensor %d: NULL pointer", what, t); return VMP_E_BADARG; }
-        a.phi_adam.p[t] = phi_p[t]; a.phi_adam.m[t] = phi_m[t]; a.phi_adam.v[t] = phi_v[t];
-    }
-    a.phi.mu = phi_p[0]; a.phi.Lraw = phi_p[1]; a.phi.piraw = phi_p[2]; a.phi.logpi = logpi;
-    a.phi.g_mu = phi_g[0]; a.phi.g_Lraw = phi_g[1]; a.phi.g_piraw = phi_g[2]; a.phi.K = K; a.phi.L = L;
-    a.partials = partials; a.nblk = nblk;
-    blocks += (unsigned)K;
-    if (smm) {
-        a.smm = *smm;
-        a.smm.r = r; a.smm.N = (int)N;
-        for (int t = 0; t < 2; ++t)
-            if (!smm->p[t] || !smm->g[t] || (!pack && (!smm->m[t] || !smm->v[t]))) {
-                set_error("%s: theta tensor %d: NULL pointer", what, t);
-                return VMP_E_BADARG;
-            }
-        if (!pack && (!smm->prior_alpha || !smm->alpha)) { set_error("%s: prior / alpha: NULL pointer", what); return VMP_E_BADARG; }
-        a.smm.nk = pack ? xbuf : stats_out;
-        a.smm.rho_dev = rho_dev; a.smm.rho = rho;
-    }
-    if (pack) {
-        // [moments (K, 2+L+L*L) | phi_gmm/mu_k, L_k, log_pi_k | encoder net | decoder net | elbo, rec, reg]: the parameter order of
-        // SVAETrainer.trainables() (experiments.py:160-181), as training.pack_exchange_buffer lays it out.  SMM: [N_k (K, 1) | phi_gmm (3) |
-        // theta/mu_k, theta/L_k | encoder | decoder | elbo, rec, reg]
-        const int SW = smm ? 1 : 2 + L + L * L;
-        double* o = xbuf + (size_t)K * SW;
-        a.phi_adam.gx[0] = o; o += K * L;
-        a.phi_adam.gx[1] = o; o += K * L * L;
-        a.phi_adam.gx[2] = o; o += K;
-        if (smm) {
-            a.smm.gx[0] = o; o += K * L;
-            a.smm.gx[1] = o; o += K * L * L;
-            a.smm.m[0] = a.smm.m[1] = a.smm.v[0] = a.smm.v[1] = nullptr;
-            a.smm.alpha = nullptr;
-        }
-        a.xnet[1] = o; o += a.net[1].red.PW;                 // encoder first
-        a.xnet[0] = o; o += a.net[0].red.PW;
-        a.xscal = o;
-        for (int t = 0; t < 3; ++t) a.phi_adam.p[t] = nullptr;
-        a.sa = SmallStatsArgs{x_samples, r, nullptr, xbuf, (int)N, L, K};
-        a.cvi.K = K; a.cvi.L = L;
-    } else if (smm) {
-        a.smm.gx[0] = a.smm.gx[1] = nullptr;
-    } else {
-    for (int t = 0; t < 5; ++t)
-        if (!prior[t] || !theta[t]) { set_error("%s: prior / theta tensor %d: NULL pointer", what, t); return VMP_E_BADARG; }
-    a.sa = SmallStatsArgs{x_samples, r, nullptr, stats_out, (int)N, L, K};
-    a.cvi = CviArgs{stats_out, prior[0], prior[1], prior[2], prior[3], prior[4], theta[0], theta[1], theta[2], theta[3], theta[4],
-                    theta_star ? theta_star[0] : nullptr, theta_star ? theta_star[1] : nullptr, theta_star ? theta_star[2] : nullptr,
-                    theta_star ? theta_star[3] : nullptr, theta_star ? theta_star[4] : nullptr, rho_dev, rho, K, L};
-    }
-    blocks += (unsigned)K;
-    a.tail.part = const_cast<double*>(tail_part);
-    a.tail.scal = scalars;
-    a.tail.cst = (double)N * Dy * 0.5 * 1.8378770664093453;            // log(2 pi): as tail_setup
-    a.tail_n = (unsigned)tail_n;
-    blocks += 1;
-    a.lr_t_dev = lr_t_dev; a.lr_t = (float)lr_t; a.b1 = (float)beta1; a.b2 = (float)beta2;
-    a.c1 = (float)(1.0 - beta1); a.c2 = (float)(1.0 - beta2); a.eps = (float)eps;
-    a.phi_adam.b1 = a.b1; a.phi_adam.b2 = a.b2; a.phi_adam.c1 = a.c1; a.phi_adam.c2 = a.c2; a.phi_adam.eps = a.eps;
-#define FIN_CALL(LL) case LL: hipLaunchKernelGGL((step_final_kernel<LL>), dim3(blocks), dim3(FIN_THREADS), 0, static_cast<hipStream_t>(stream), a); break
-#define FIN_CALL_SMM(LL) case LL: hipLaunchKernelGGL((step_final_kernel<LL, true>), dim3(blocks), dim3(FIN_THREADS), 0, static_cast<hipStream_t>(stream), a); break
-    if (smm) {
-        switch (L) { FIN_CALL_SMM(1); FIN_CALL_SMM(2); FIN_CALL_SMM(3); FIN_CALL_SMM(4); FIN_CALL_SMM(5); FIN_CALL_SMM(6); FIN_CALL_SMM(7); default: FIN_CALL_SMM(8); }
-    } else {
-        switch (L) { FIN_CALL(1); FIN_CALL(2); FIN_CALL(3); FIN_CALL(4); FIN_CALL(5); FIN_CALL(6); FIN_CALL(7); default: FIN_CALL(8); }
-    }
-#undef FIN_CALL_SMM
-#undef FIN_CALL
-    return check_launch(what);
-}
-}  // namespace
-
 int vmp_svae_step_final(const float* dec_part, int dec_blocks, int dec_in, int dec_units, int dec_out, float* const* dec_p,
                         float* const* dec_m, float* const* dec_v, float* const* dec_g, const float* enc_part, int enc_blocks,
                         int enc_in, int enc_units, int enc_out, float* const* enc_p, float* const* enc_m, float* const* enc_v,
@@ -511,37 +549,34 @@ int vmp_svae_step_final(const float* dec_part, int dec_blocks, int dec_in, int d
                         const float* const* prior, float* const* theta, float* const* theta_star, const float* rho_dev, float rho, int K,
                         int L, double* stats_out, const double* tail_part, int tail_n, int Dy, float* scalars, double beta1, double beta2,
                         double eps, double lr_t, const float* lr_t_dev, void* stream) {
-    return step_final_impl("vmp_svae_step_final", nullptr, dec_part, dec_blocks, dec_in, dec_units, dec_out, dec_p, dec_m, dec_v, dec_g,
-                           enc_part, enc_blocks, enc_in, enc_units, enc_out, enc_p, enc_m, enc_v, enc_g, partials, nblk, logpi, phi_p, phi_g,
-                           phi_m, phi_v, x_samples, r, N, prior, theta, theta_star, rho_dev, rho, K, L, stats_out, tail_part, tail_n, Dy,
-                           scalars, beta1, beta2, eps, lr_t, lr_t_dev, stream);
+    return step_final_launch(FinSpec{
+        .what = "vmp_svae_step_final",
+        .net = {{dec_part, dec_blocks, dec_in, dec_units, dec_out, {.p = dec_p, .g = dec_g, .m = dec_m, .v = dec_v}},
+                {enc_part, enc_blocks, enc_in, enc_units, enc_out, {.p = enc_p, .g = enc_g, .m = enc_m, .v = enc_v}}},
+        .phi = {.p = phi_p, .g = phi_g, .m = phi_m, .v = phi_v}, .partials = partials, .nblk = nblk, .logpi = logpi,
+        .x_samples = x_samples, .prior = prior, .theta = theta, .theta_star = theta_star,
+        .r = r, .N = N, .K = K, .L = L, .rho_dev = rho_dev, .rho = rho, .stats_out = stats_out,
+        .tail_part = tail_part, .tail_n = tail_n, .Dy = Dy, .scalars = scalars,
+        .beta1 = beta1, .beta2 = beta2, .eps = eps, .lr_t = lr_t, .lr_t_dev = lr_t_dev, .stream = stream});
 }
 
 // The closing launch of a DATA-PARALLEL minibatch step: the same block roles, but nothing is updated - this rank's moments, its 21
-// gradients and its three scalars go as doubles into xbuf [moments (K, 2+L+L*L) | phi_gmm (3 tensors) | encoder (9) | decoder (9) |
-// elbo, rec, reg], the packed buffer the step's one all-reduce sums (training.pack_exchange_buffer's layout; experiments.py:247-260);
-// vmp_svae_cvi_update and vmp_adam_step_packed follow the all-reduce.  The fp32 gradients are also left in *_g.
+// gradients and its three scalars go as doubles into xbuf (exchange_layout above), the packed buffer the step's one all-reduce sums
+// (experiments.py:247-260); vmp_svae_cvi_update and vmp_adam_step_packed follow the all-reduce.  The fp32 gradients are also left in *_g.
 int vmp_svae_step_pack(double* xbuf, size_t xbuf_doubles, const float* dec_part, int dec_blocks, int dec_in, int dec_units, int dec_out,
                        float* const* dec_p, float* const* dec_g, const float* enc_part, int enc_blocks, int enc_in, int enc_units,
                        int enc_out, float* const* enc_p, float* const* enc_g, const float* partials, int nblk, const double* logpi,
                        float* const* phi_p, float* const* phi_g, const float* x_samples, const float* r, int64_t N, int K, int L,
                        const double* tail_part, int tail_n, int Dy, float* scalars, void* stream) {
-    if (!xbuf) { set_error("vmp_svae_step_pack: NULL exchange buffer"); return VMP_E_BADARG; }
-    if (K < 1 || L < 1 || dec_in < 1 || dec_units < 1 || dec_out < 1 || enc_in < 1 || enc_units < 1 || enc_out < 1) {
-        set_error("vmp_svae_step_pack: bad sizes");
-        return VMP_E_DIM;
-    }
-    const size_t need = (size_t)K * (2 + L + L * L) + (size_t)K * L + (size_t)K * L * L + K +
-                        (size_t)vmp_decoder_param_words(enc_in, enc_units, enc_out) + (size_t)vmp_decoder_param_words(dec_in, dec_units, dec_out) + 3;
-    if (xbuf_doubles < need) {
-        set_error("vmp_svae_step_pack: exchange buffer too small (%zu < %zu doubles)", xbuf_doubles, need);
-        return VMP_E_WS;
-    }
-    // (Adam slots are not touched in this form: the parameter tensors stand in for the pointer checks)
-    return step_final_impl("vmp_svae_step_pack", xbuf, dec_part, dec_blocks, dec_in, dec_units, dec_out, dec_p, dec_p, dec_p, dec_g, enc_part,
-                           enc_blocks, enc_in, enc_units, enc_out, enc_p, enc_p, enc_p, enc_g, partials, nblk, logpi, phi_p, phi_g, phi_p,
-                           phi_p, x_samples, r, N, nullptr, nullptr, nullptr, nullptr, 0.f, K, L, nullptr, tail_part, tail_n, Dy, scalars,
-                           0.9, 0.999, 1e-8, 0.0, nullptr, stream);
+    return step_final_launch(FinSpec{
+        .what = "vmp_svae_step_pack", .pack = true,
+        .net = {{dec_part, dec_blocks, dec_in, dec_units, dec_out, {.p = dec_p, .g = dec_g}},
+                {enc_part, enc_blocks, enc_in, enc_units, enc_out, {.p = enc_p, .g = enc_g}}},
+        .phi = {.p = phi_p, .g = phi_g}, .partials = partials, .nblk = nblk, .logpi = logpi,
+        .x_samples = x_samples,
+        .r = r, .N = N, .K = K, .L = L,
+        .tail_part = tail_part, .tail_n = tail_n, .Dy = Dy, .scalars = scalars,
+        .xbuf = xbuf, .xbuf_doubles = xbuf_doubles, .stream = stream});
 }
 
 // The closing launch of the SMM-SVAE's minibatch step: vmp_svae_step_final's roles with the Student-t model's theta (see SmmFin):
@@ -556,42 +591,33 @@ int vmp_svae_step_final_smm(const float* dec_part, int dec_blocks, int dec_in, i
                             float* alpha, float* alpha_star, const float* rho_dev, float rho, int K, int L, double* stats_out,
                             const double* tail_part, int tail_n, int Dy, float* scalars, double beta1, double beta2, double eps,
                             double lr_t, const float* lr_t_dev, void* stream) {
-    if (!theta_p || !theta_g || !theta_m || !theta_v) { set_error("vmp_svae_step_final_smm: NULL argument"); return VMP_E_BADARG; }
-    SmmFin f{};
-    for (int t = 0; t < 2; ++t) { f.p[t] = theta_p[t]; f.g[t] = theta_g[t]; f.m[t] = theta_m[t]; f.v[t] = theta_v[t]; }
-    f.prior_alpha = prior_alpha; f.alpha = alpha; f.alpha_star = alpha_star;
-    // (x_samples is not read by the SMM M-step: r stands in for the pointer check)
-    return step_final_impl("vmp_svae_step_final_smm", nullptr, dec_part, dec_blocks, dec_in, dec_units, dec_out, dec_p, dec_m, dec_v, dec_g,
-                           enc_part, enc_blocks, enc_in, enc_units, enc_out, enc_p, enc_m, enc_v, enc_g, partials, nblk, logpi, phi_p, phi_g,
-                           phi_m, phi_v, r, r, N, nullptr, nullptr, nullptr, rho_dev, rho, K, L, stats_out, tail_part, tail_n, Dy, scalars,
-                           beta1, beta2, eps, lr_t, lr_t_dev, stream, &f);
+    return step_final_launch(FinSpec{
+        .what = "vmp_svae_step_final_smm", .smm = true,
+        .net = {{dec_part, dec_blocks, dec_in, dec_units, dec_out, {.p = dec_p, .g = dec_g, .m = dec_m, .v = dec_v}},
+                {enc_part, enc_blocks, enc_in, enc_units, enc_out, {.p = enc_p, .g = enc_g, .m = enc_m, .v = enc_v}}},
+        .phi = {.p = phi_p, .g = phi_g, .m = phi_m, .v = phi_v}, .partials = partials, .nblk = nblk, .logpi = logpi,
+        .th = {.p = theta_p, .g = theta_g, .m = theta_m, .v = theta_v}, .prior_alpha = prior_alpha, .alpha = alpha, .alpha_star = alpha_star,
+        .r = r, .N = N, .K = K, .L = L, .rho_dev = rho_dev, .rho = rho, .stats_out = stats_out,
+        .tail_part = tail_part, .tail_n = tail_n, .Dy = Dy, .scalars = scalars,
+        .beta1 = beta1, .beta2 = beta2, .eps = eps, .lr_t = lr_t, .lr_t_dev = lr_t_dev, .stream = stream});
 }
 
-// Data-parallel form of vmp_svae_step_final_smm: xbuf [N_k (K, 1) | phi_gmm (3) | theta/mu_k, theta/L_k | encoder (9) | decoder (9) |
-// elbo, rec, reg] (training.pack_exchange_buffer's layout of the SMM step); nothing is updated.
+// Data-parallel form of vmp_svae_step_final_smm: xbuf as exchange_layout above gives it for the SMM step; nothing is updated.
 int vmp_svae_step_pack_smm(double* xbuf, size_t xbuf_doubles, const float* dec_part, int dec_blocks, int dec_in, int dec_units,
                            int dec_out, float* const* dec_p, float* const* dec_g, const float* enc_part, int enc_blocks, int enc_in,
                            int enc_units, int enc_out, float* const* enc_p, float* const* enc_g, const float* partials, int nblk,
                            const double* logpi, float* const* phi_p, float* const* phi_g, float* const* theta_p, float* const* theta_g,
                            const float* r, int64_t N, int K, int L, const double* tail_part, int tail_n, int Dy, float* scalars,
                            void* stream) {
-    if (!xbuf || !theta_p || !theta_g) { set_error("vmp_svae_step_pack_smm: NULL argument"); return VMP_E_BADARG; }
-    if (K < 1 || L < 1 || dec_in < 1 || dec_units < 1 || dec_out < 1 || enc_in < 1 || enc_units < 1 || enc_out < 1) {
-        set_error("vmp_svae_step_pack_smm: bad sizes");
-        return VMP_E_DIM;
-    }
-    const size_t need = (size_t)K + 2 * ((size_t)K * L + (size_t)K * L * L) + K + (size_t)vmp_decoder_param_words(enc_in, enc_units, enc_out) +
-                        (size_t)vmp_decoder_param_words(dec_in, dec_units, dec_out) + 3;
-    if (xbuf_doubles < need) {
-        set_error("vmp_svae_step_pack_smm: exchange buffer too small (%zu < %zu doubles)", xbuf_doubles, need);
-        return VMP_E_WS;
-    }
-    SmmFin f{};
-    for (int t = 0; t < 2; ++t) { f.p[t] = theta_p[t]; f.g[t] = theta_g[t]; }
-    return step_final_impl("vmp_svae_step_pack_smm", xbuf, dec_part, dec_blocks, dec_in, dec_units, dec_out, dec_p, dec_p, dec_p, dec_g, enc_part,
-                           enc_blocks, enc_in, enc_units, enc_out, enc_p, enc_p, enc_p, enc_g, partials, nblk, logpi, phi_p, phi_g, phi_p,
-                           phi_p, r, r, N, nullptr, nullptr, nullptr, nullptr, 0.f, K, L, nullptr, tail_part, tail_n, Dy, scalars,
-                           0.9, 0.999, 1e-8, 0.0, nullptr, stream, &f);
+    return step_final_launch(FinSpec{
+        .what = "vmp_svae_step_pack_smm", .pack = true, .smm = true,
+        .net = {{dec_part, dec_blocks, dec_in, dec_units, dec_out, {.p = dec_p, .g = dec_g}},
+                {enc_part, enc_blocks, enc_in, enc_units, enc_out, {.p = enc_p, .g = enc_g}}},
+        .phi = {.p = phi_p, .g = phi_g}, .partials = partials, .nblk = nblk, .logpi = logpi,
+        .th = {.p = theta_p, .g = theta_g},
+        .r = r, .N = N, .K = K, .L = L,
+        .tail_part = tail_part, .tail_n = tail_n, .Dy = Dy, .scalars = scalars,
+        .xbuf = xbuf, .xbuf_doubles = xbuf_doubles, .stream = stream});
 }
 
 size_t vmp_svae_elbo_tail_workspace_bytes(void) { return tail_workspace_bytes(); }

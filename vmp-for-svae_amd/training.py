@@ -114,6 +114,24 @@ class TFAdam(object):
             torch._foreach_sub_(data, upd)
 
 
+def exchange_layout(n_stats, grad_sizes, n_scalars=3):
+    """The packed fp64 buffer of a data-parallel step, [stats | gradients in trainables() order | elbo, rec, reg], in elements:
+    (offset of every gradient, offset of the scalars, total).  The one statement of this layout on the host side; the closing launch of
+    the minibatch step writes the same one (csrc/vmp_step.hip, exchange_layout)."""
+    goffs, o = [], n_stats
+    for n_ in grad_sizes:
+        goffs.append(o)
+        o += n_
+    return goffs, o, o + n_scalars
+
+
+def param_groups(smm):
+    """Where the parameter groups sit in SVAETrainer.trainables(): phi_gmm (3), theta/mu_k and theta/L_k (SMM only), encoder_net (9),
+    decoder_net (9).  The slices apply alike to the parameters, Adam's m and v and the gradient lists."""
+    t = 5 if smm else 3
+    return dict(phi=slice(0, 3), theta=slice(3, t), enc=slice(t, t + 9), dec=slice(t + 9, t + 18))
+
+
 def pack_exchange_buffer(stats, grads, scalars):
     """[stats (fp64) | grads (flattened, fp64) | scalars] -> one contiguous fp64 buffer with ONE launch (vmp_pack_f64, pointer
     table in the launch packet) instead of a torch.cat over ~25 .double() copies.  Returns (buffer, gradient offsets).
@@ -121,43 +139,28 @@ def pack_exchange_buffer(stats, grads, scalars):
     import ctypes
     ts = [stats.reshape(-1)] + [g.reshape(-1) for g in grads] + [s.reshape(-1) for s in scalars]
     ok = all(t.is_cuda and t.is_contiguous() and t.dtype in (torch.float32, torch.float64) for t in ts)
-    sizes = [t.numel() for t in ts]
-    offs, o = [], 0
-    for n_ in sizes:
-        offs.append(o)
-        o += n_
-    goffs = offs[1:1 + len(grads)]
+    goffs, _, total = exchange_layout(stats.numel(), [g.numel() for g in grads], sum(s.numel() for s in scalars))
     if not ok:                                                # host tensors (gloo tests on CPU): the torch form
         return torch.cat([t.double() for t in ts]), goffs
-    buf = torch.empty(o, dtype=torch.float64, device=stats.device)
+    buf = torch.empty(total, dtype=torch.float64, device=stats.device)
     n = len(ts)
     L.check(L.lib().vmp_pack_f64(n, (ctypes.c_void_p * n)(*[t.data_ptr() for t in ts]),
                                  (ctypes.c_int * n)(*[int(t.dtype == torch.float64) for t in ts]),
-                                 (ctypes.c_int64 * n)(*sizes), L.ptr(buf), L.stream()), 'vmp_pack_f64')
+                                 (ctypes.c_int64 * n)(*[t.numel() for t in ts]), L.ptr(buf), L.stream()), 'vmp_pack_f64')
     return buf, goffs
 
 
 def pack_for_allreduce(stats, grads, scalars):
-    """[stats (fp64) | grads (flattened, fp64) | scalars] -> one contiguous fp64 buffer."""
+    """[stats (fp64) | grads (flattened, fp64) | scalars] -> one contiguous fp64 buffer (torch.cat: the layout by construction)."""
     parts = [stats.reshape(-1).double()] + [g.reshape(-1).double() for g in grads] + [torch.stack([s.double().reshape(()) for s in scalars])]
     return torch.cat(parts)
 
 
 def unpack_after_allreduce(buf, stats_shape, grad_shapes, n_scalars):
-    o = 0
-    n = 1
-    for s in stats_shape:
-        n *= s
-    stats = buf[o:o + n].reshape(stats_shape)
-    o += n
-    grads = []
-    for shp in grad_shapes:
-        n = 1
-        for s in shp:
-            n *= s
-        grads.append(buf[o:o + n].reshape(shp))
-        o += n
-    return stats, grads, buf[o:o + n_scalars]
+    sizes = [math.prod(shp) for shp in grad_shapes]
+    goffs, so, total = exchange_layout(math.prod(stats_shape), sizes, n_scalars)
+    grads = [buf[o:o + n].reshape(shp) for o, n, shp in zip(goffs, sizes, grad_shapes)]
+    return buf[:math.prod(stats_shape)].reshape(stats_shape), grads, buf[so:total]
 
 
 class SVAETrainer(object):
@@ -165,7 +168,7 @@ class SVAETrainer(object):
                  device='cuda', m_uniform=None, pi_normal=None, group=None, smm=False, dof=5.0, fused_decoder=True,
                  rng='philox', reference_call_order=False, direct_step=True):
         self.K, self.L, self.S = K, Ld, nb_samples
-        # True (default): a whole-minibatch single-process GMM step on in-kernel noise runs as the 8-launch kernel sequence of
+        # True (default): a whole-minibatch GMM or SMM step on in-kernel noise runs as the six-launch kernel sequence of
         # _step_direct (round 6) instead of the autograd graph over the same kernels (13 launches); False: always autograd
         self.direct_step = bool(direct_step)
         self._direct_shapes = {}
@@ -212,7 +215,8 @@ class SVAETrainer(object):
             vae.decoder_variables(Ld, self.decoder_layers, self.stddev_init_nn, seed, self.device)
 
     def trainables(self):
-        """21 tensors in the reference's order: phi_gmm (3), encoder_net (9), decoder_net (9)."""
+        """(names, tensors) in the reference's order: phi_gmm (3), SMM only: theta/mu_k, theta/L_k, encoder_net (9), decoder_net (9) -
+        21 tensors (SMM: 23); param_groups() names the groups."""
         names = ['phi_gmm/mu_k', 'phi_gmm/L_k', 'phi_gmm/log_pi_k']
         ts = list(self.phi_gmm)
         if self.smm:                                             # experiments.py:160-161
@@ -330,9 +334,8 @@ class SVAETrainer(object):
         opt = self.opt
         if not opt._fused_ok():
             raise L.VmpError('SVAETrainer: parameters must be contiguous fp32 GPU tensors')
-        smm = self.smm
-        nth = 2 if smm else 0                                # theta/mu_k, theta/L_k: trainables between phi_gmm and the encoder
-        phi, th, enc, dec = params[:3], params[3:3 + nth], params[3 + nth:12 + nth], params[12 + nth:21 + nth]
+        smm, grp = self.smm, param_groups(self.smm)
+        phi, th, enc, dec = (params[grp[k_]] for k_ in ('phi', 'theta', 'enc', 'dec'))
         prior = [L.dev_f32(t.detach(), 'prior') for t in ([self.gmm_prior] if smm else self.gmm_prior)]
         for t in self.theta:
             if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
@@ -340,9 +343,8 @@ class SVAETrainer(object):
         st = L.stream()
         pp = lambda ts: [L.ptr(t) for t in ts]
         arr = lambda ts: (ctypes.c_void_p * len(ts))(*[t.data_ptr() if t is not None else None for t in ts])
-        seed_dev = None if _dev_scalars is None or len(_dev_scalars) < 3 else _dev_scalars[2]
-        rho_dev = None if _dev_scalars is None else _dev_scalars[0]
-        lr_dev = None if _dev_scalars is None else _dev_scalars[1]
+        # (CVI step size, Adam step size[, Philox key[, (table, rows, counter, dst16)]]) of a captured step, as device words
+        rho_dev, lr_dev, seed_dev, tab = (tuple(_dev_scalars or ()) + (None,) * 4)[:4]
         lrcvi = exponential_decay(self.lrcvi0, self.global_step, 1000, self.decay_rate)
         # Scratch that nothing outside this step reads - encoder outputs, the K-sized prep, T', dL/dx, the per-sample reconstruction sums,
         # partial rows, the two MLP workspaces ... - is ONE allocation addressed by offsets (twenty torch.empty calls cost more host time
@@ -360,24 +362,27 @@ class SVAETrainer(object):
             o += (nb_ + 255) & ~255
         arena = torch.empty(o, dtype=torch.uint8, device=dev)
         base = arena.data_ptr()
-        A = lambda k_: ctypes.c_void_p(base + off[k_])
+        A = {k_: ctypes.c_void_p(base + o_) for k_, o_ in off.items()}.__getitem__     # section name -> device pointer
+        # What the two models differ in, chosen once: entry points of launches 1, 4, 6; theta as launch 1 reads it, the packed mean it writes
+        # (SMM: none, m = theta/mu_k itself); m / nu of launches 2, 4; moments per component (SMM: N_k only, svae.m_step_smm); what CVI updates
+        if smm:
+            alpha, th_mu, th_L, dof = self.theta             # (alpha_nat, mu_k, L_k, DoF)
+            suffix, bwd_tail = '_smm', 'vmp_svae_estep_bwd_tail_t'
+            theta_in, mk_out = (L.ptr(alpha), L.ptr(th_L), L.ptr(dof)), ()
+            m_ptr, nu_ptr, nu_bwd = L.ptr(th_mu), L.ptr(dof), (L.ptr(dof),)
+            SW, cvi_theta = 1, self.theta[:1]
+        else:
+            suffix, bwd_tail = '', 'vmp_svae_estep_bwd_tail'
+            theta_in, mk_out = pp(self.theta), (A('mk'),)
+            m_ptr, nu_ptr, nu_bwd = A('mk'), None, ()
+            SW, cvi_theta = 2 + Ld + Ld * Ld, self.theta
         # 1: encoder (natparam head: eta1, -1/2 var) + recognition unpacking + theta packing (+ a replayed step's scalars from its table)
         mu_k, L_raw, pi_raw = phi
-        tab = _dev_scalars[3] if (_dev_scalars is not None and len(_dev_scalars) > 3) else None     # (table, rows, counter, dst16)
+        enc_p = pp(enc)                                      # (launches 1 and 5)
         tab_args = (L.ptr(tab[0]) if tab else None, tab[1] if tab else 0, L.ptr(tab[2]) if tab else None, L.ptr(tab[3]) if tab else None)
-        if smm:
-            alpha, th_mu, th_L, dof = self.theta             # (alpha_nat, mu_k, L_k, DoF); m of the E-step = theta/mu_k itself
-            L.check(lib.vmp_mlp_gauss_head_fwd_prep_smm(L.ptr(y), *pp(enc), N, Dy, Ld, U, -0.5, A('eta1'), A('eta2d'), L.ptr(mu_k),
-                                                        L.ptr(L_raw), L.ptr(pi_raw), L.ptr(alpha), L.ptr(th_L), L.ptr(dof), K, A('Lk'), A('P'),
-                                                        A('bias'), A('Wk'), A('kappa'), A('logpi'), *tab_args, st),
-                    'vmp_mlp_gauss_head_fwd_prep_smm')
-            m_ptr, nu_ptr = L.ptr(th_mu), L.ptr(dof)
-        else:
-            L.check(lib.vmp_mlp_gauss_head_fwd_prep(L.ptr(y), *pp(enc), N, Dy, Ld, U, -0.5, A('eta1'), A('eta2d'), L.ptr(mu_k), L.ptr(L_raw),
-                                                    L.ptr(pi_raw), *pp(self.theta), K, A('Lk'), A('P'), A('bias'), A('mk'), A('Wk'),
-                                                    A('kappa'), A('logpi'), *tab_args, st),
-                    'vmp_mlp_gauss_head_fwd_prep')
-            m_ptr, nu_ptr = A('mk'), None
+        name = 'vmp_mlp_gauss_head_fwd_prep' + suffix
+        L.check(getattr(lib, name)(L.ptr(y), *enc_p, N, Dy, Ld, U, -0.5, A('eta1'), A('eta2d'), L.ptr(mu_k), L.ptr(L_raw), L.ptr(pi_raw),
+                                   *theta_in, K, A('Lk'), A('P'), A('bias'), *mk_out, A('Wk'), A('kappa'), A('logpi'), *tab_args, st), name)
         # 2: E-step on in-kernel noise; its epilogue draws the one sub-sample per row
         x = torch.empty(N, K, S, Ld, **f32)
         lz = torch.empty(N, K, **f32)
@@ -390,81 +395,49 @@ class SVAETrainer(object):
         L.check(lib.vmp_decoder_elbo_lazy(L.ptr(x), L.ptr(y), L.ptr(lz), -1.0, *pp(dec), N, K, S, Ld, Dy, U, A('dx'), A('ll'),
                                           A('ws_dec'), wsb_dec, st), 'vmp_decoder_elbo_lazy')
         # 4: ELBO tail + E-step backward (SMM: with the theta half of the partial rows)
-        if smm:
-            L.check(lib.vmp_svae_estep_bwd_tail_t(A('eta1'), A('eta2d'), L.ptr(mu_k), A('P'), A('bias'), m_ptr, A('Wk'), nu_ptr,
-                                                  L.ptr(x), L.ptr(lz), A('Tp'), A('ll'), -1.0, A('dx'), N, K, Ld, S, A('g_eta1'),
-                                                  A('g_eta2d'), A('partials'), sizes['partials'], A('r'), A('tail_part'),
-                                                  sizes['tail_part'], st), 'vmp_svae_estep_bwd_tail_t')
-        else:
-            L.check(lib.vmp_svae_estep_bwd_tail(A('eta1'), A('eta2d'), L.ptr(mu_k), A('P'), A('bias'), A('mk'), A('Wk'),
-                                                L.ptr(x), L.ptr(lz), A('Tp'), A('ll'), -1.0, A('dx'), N, K, Ld, S, A('g_eta1'),
-                                                A('g_eta2d'), A('partials'), sizes['partials'], A('r'), A('tail_part'),
-                                                sizes['tail_part'], st), 'vmp_svae_estep_bwd_tail')
+        L.check(getattr(lib, bwd_tail)(A('eta1'), A('eta2d'), L.ptr(mu_k), A('P'), A('bias'), m_ptr, A('Wk'), *nu_bwd, L.ptr(x), L.ptr(lz),
+                                       A('Tp'), A('ll'), -1.0, A('dx'), N, K, Ld, S, A('g_eta1'), A('g_eta2d'), A('partials'),
+                                       sizes['partials'], A('r'), A('tail_part'), sizes['tail_part'], st), bwd_tail)
         # 5: encoder backward; parameter partials stay in ws_enc
-        L.check(lib.vmp_mlp_gauss_head_bwd_lazy(L.ptr(y), A('g_eta1'), A('g_eta2d'), -0.5, *pp(enc), N, Dy, Ld, U, None,
+        L.check(lib.vmp_mlp_gauss_head_bwd_lazy(L.ptr(y), A('g_eta1'), A('g_eta2d'), -0.5, *enc_p, N, Dy, Ld, U, None,
                                                 A('ws_enc'), wsb_enc, st), 'vmp_mlp_gauss_head_bwd_lazy')
-        # 6: the closing launch (phi_gmm gradients from the partial rows, both MLP reductions, Adam, moments + CVI, ELBO scalars)
+        # 6: the closing launch (phi_gmm gradients from the partial rows, both MLP reductions, Adam, moments + CVI, ELBO scalars);
+        # pack: the same roles write the exchange buffer instead, and no argument of an update is passed
         g_phi = [torch.empty_like(t) for t in phi]
         g_th = [torch.empty_like(t) for t in th]
         g_enc, g_dec = [torch.empty_like(t) for t in enc], [torch.empty_like(t) for t in dec]
-        SW = 1 if smm else 2 + Ld + Ld * Ld                  # SMM: N_k only (svae.m_step_smm)
+        grads = g_phi + g_th + g_enc + g_dec
         stats = torch.empty(K, SW, dtype=torch.float64, device=dev)
-        star = [torch.empty_like(t) for t in (self.theta[:1] if smm else self.theta)]
+        star = [torch.empty_like(t) for t in cvi_theta]
         scal = torch.empty(3, **f32)
-        if pack and smm:
-            sizes = [p.numel() for p in params]
-            goffs, o = [], K * SW
-            for n_ in sizes:
-                goffs.append(o)
-                o += n_
-            buf = torch.empty(o + 3, dtype=torch.float64, device=dev)
-            L.check(lib.vmp_svae_step_pack_smm(L.ptr(buf), buf.numel(), A('ws_dec'), nb_dec, Ld, U, Dy, arr(dec), arr(g_dec), A('ws_enc'),
-                                               nb_enc, Dy, U, Ld, arr(enc), arr(g_enc), A('partials'), nt, A('logpi'), arr(phi), arr(g_phi),
-                                               arr(th), arr(g_th), A('r'), N, K, Ld, A('tail_part'), nt, Dy, L.ptr(scal), st),
-                    'vmp_svae_step_pack_smm')
-            return dict(world=self._world(), names=names, params=params, grads=g_phi + g_th + g_enc + g_dec, stats=buf[:K * SW].view(K, SW),
-                        fused_m=False, keep=dict(log_z=lz, x_samples=xs, x_k=x), r_whole=None, scal=(scal[0], scal[1], scal[2]), buf=buf,
-                        goffs=goffs, mom_whole=None)
         if pack:
-            sizes = [p.numel() for p in params]
-            goffs, o = [], K * SW
-            for n_ in sizes:
-                goffs.append(o)
-                o += n_
-            buf = torch.empty(o + 3, dtype=torch.float64, device=dev)
-            L.check(lib.vmp_svae_step_pack(L.ptr(buf), buf.numel(), A('ws_dec'), nb_dec, Ld, U, Dy, arr(dec), arr(g_dec), A('ws_enc'),
-                                           nb_enc, Dy, U, Ld, arr(enc), arr(g_enc), A('partials'), nt, A('logpi'), arr(phi), arr(g_phi),
-                                           L.ptr(xs), A('r'), N, K, Ld, A('tail_part'), nt, Dy, L.ptr(scal), st), 'vmp_svae_step_pack')
-            return dict(world=self._world(), names=names, params=params, grads=g_phi + g_enc + g_dec, stats=buf[:K * SW].view(K, SW),
-                        fused_m=False, keep=dict(log_z=lz, x_samples=xs, x_k=x), r_whole=None, scal=(scal[0], scal[1], scal[2]), buf=buf,
-                        goffs=goffs, mom_whole=None)
-        if lr_dev is None:
-            opt.t += 1
-            lr_t = opt.lr_t(opt.t)
+            goffs, _, total = exchange_layout(K * SW, [p.numel() for p in params])
+            buf = torch.empty(total, dtype=torch.float64, device=dev)
+            slots = lambda k_: ()
+            head, cvi, tail = (L.ptr(buf), total), (), (A('tail_part'), nt, Dy, L.ptr(scal), st)
         else:
             lr_t = 0.0
-        m, v = opt.m, opt.v
-        if smm:
-            L.check(lib.vmp_svae_step_final_smm(A('ws_dec'), nb_dec, Ld, U, Dy, arr(dec), arr(m[14:23]), arr(v[14:23]), arr(g_dec),
-                                                A('ws_enc'), nb_enc, Dy, U, Ld, arr(enc), arr(m[5:14]), arr(v[5:14]), arr(g_enc),
-                                                A('partials'), nt, A('logpi'), arr(phi), arr(g_phi), arr(m[:3]), arr(v[:3]),
-                                                arr(th), arr(g_th), arr(m[3:5]), arr(v[3:5]), A('r'), N, L.ptr(prior[0]),
-                                                L.ptr(self.theta[0]), L.ptr(star[0]), L.ptr(rho_dev),
-                                                0.0 if rho_dev is not None else float(lrcvi), K, Ld, L.ptr(stats), A('tail_part'), nt, Dy,
-                                                L.ptr(scal), opt.b1, opt.b2, opt.eps, lr_t, L.ptr(lr_dev), st), 'vmp_svae_step_final_smm')
-        else:
-            L.check(lib.vmp_svae_step_final(A('ws_dec'), nb_dec, Ld, U, Dy, arr(dec), arr(m[12:21]), arr(v[12:21]), arr(g_dec),
-                                            A('ws_enc'), nb_enc, Dy, U, Ld, arr(enc), arr(m[3:12]), arr(v[3:12]), arr(g_enc),
-                                            A('partials'), nt, A('logpi'), arr(phi), arr(g_phi), arr(m[:3]), arr(v[:3]), L.ptr(xs),
-                                            A('r'), N,
-                                            arr(prior), arr(self.theta), arr(star), L.ptr(rho_dev),
-                                            0.0 if rho_dev is not None else float(lrcvi), K, Ld, L.ptr(stats), A('tail_part'), nt, Dy,
-                                            L.ptr(scal), opt.b1, opt.b2, opt.eps, lr_t, L.ptr(lr_dev), st), 'vmp_svae_step_final')
+            if lr_dev is None:
+                opt.t += 1
+                lr_t = opt.lr_t(opt.t)
+            slots = lambda k_: (arr(opt.m[grp[k_]]), arr(opt.v[grp[k_]]))            # Adam's m, v of a parameter group
+            cvi = (L.ptr(prior[0]), L.ptr(alpha), L.ptr(star[0])) if smm else (arr(prior), arr(self.theta), arr(star))
+            cvi += (L.ptr(rho_dev), 0.0 if rho_dev is not None else float(lrcvi))
+            head, tail = (), (L.ptr(stats), A('tail_part'), nt, Dy, L.ptr(scal), opt.b1, opt.b2, opt.eps, lr_t, L.ptr(lr_dev), st)
+        mix = (arr(th), arr(g_th), *slots('theta'), A('r'), N) if smm else (L.ptr(xs), A('r'), N)
+        name = 'vmp_svae_step_' + ('pack' if pack else 'final') + suffix
+        L.check(getattr(lib, name)(*head, A('ws_dec'), nb_dec, Ld, U, Dy, arr(dec), *slots('dec'), arr(g_dec),
+                                   A('ws_enc'), nb_enc, Dy, U, Ld, arr(enc), *slots('enc'), arr(g_enc),
+                                   A('partials'), nt, A('logpi'), arr(phi), arr(g_phi), *slots('phi'), *mix, *cvi, K, Ld, *tail), name)
+        if pack:
+            return dict(world=self._world(), names=names, params=params, grads=grads, stats=buf[:K * SW].view(K, SW),
+                        fused_m=False, keep=dict(log_z=lz, x_samples=xs, x_k=x), r_whole=None, scal=(scal[0], scal[1], scal[2]), buf=buf,
+                        goffs=goffs, mom_whole=None)
         for t in list(params) + list(self.theta):
             torch.autograd.graph.increment_version(t)
         if _dev_scalars is None:
             self.global_step += 1
-        return dict(elbo=scal[0], neg_rec_err=scal[1], regulariser=scal[2], grads=dict(zip(names, g_phi + g_th + g_enc + g_dec)),
+        return dict(elbo=scal[0], neg_rec_err=scal[1], regulariser=scal[2], grads=dict(zip(names, grads)),
                     theta_star=star, lrcvi=lrcvi, log_z=lz, x_samples=xs, x_k=x, stats=stats)
 
     def _world(self):
@@ -543,10 +516,10 @@ class SVAETrainer(object):
         elbo_t, rec_t, reg_t = ctx['scal']
         packed = None
         if world > 1:
-            buf, goffs = ctx['buf'], ctx['goffs']
-            ns = stats.numel()
-            stats = buf[:ns].reshape(stats.shape)
-            elbo_t, rec_t, reg_t = buf[-3], buf[-2], buf[-1]
+            buf = ctx['buf']
+            goffs, so, _ = exchange_layout(stats.numel(), [g.numel() for g in grads])
+            stats = buf[:stats.numel()].reshape(stats.shape)
+            elbo_t, rec_t, reg_t = buf[so], buf[so + 1], buf[so + 2]
             packed = (buf, goffs, 1.0 / world)                                      # average_gradients (tf_utils.py:79)
         lrcvi = exponential_decay(self.lrcvi0, self.global_step, 1000, self.decay_rate)
         if self.opt is None:

@@ -182,6 +182,17 @@ int    vmp_svae_philox_noise_dev(const uint64_t* seed_dev, int64_t N, int K, int
 int    vmp_svae_estep_fwd_rng(const float* eta1, const float* eta2d, const float* hk, const float* Pk, const float* bias,
                               uint64_t seed, const float* mk, const float* Wk, const float* kappa, const float* nu,
                               int64_t N, int K, int L, int S, float* x, float* lz, float* Tp, float* noise_ws, void* stream);
+/* Row offset (walking a large set in chunks): row n of the launch draws the stream of GLOBAL row row0 + n - the Philox cell id is
+ * (row0 + n) K + k - so a chunk [row0, row0 + N) of a set gets exactly the noise it gets in one launch over the whole set.
+ * vmp_svae_philox_noise_at == rows [row0, row0 + N) of vmp_svae_philox_noise, bit for bit.  vmp_svae_estep_fwd_rng_at is
+ * vmp_svae_estep_fwd_rng (same shapes, noise_ws for those outside the in-kernel path) except that it always runs the streaming
+ * kernels, never the one-block-per-tile minibatch form (whose T' sums in another order): x, lz and T' of a row are bit-identical
+ * whatever the launch's N and row0 split.  row0 >= 0.                                                                  */
+int    vmp_svae_philox_noise_at(uint64_t seed, int64_t row0, int64_t N, int K, int L, int S, float* noise, void* stream);
+int    vmp_svae_estep_fwd_rng_at(const float* eta1, const float* eta2d, const float* hk, const float* Pk, const float* bias,
+                                 uint64_t seed, int64_t row0, const float* mk, const float* Wk, const float* kappa,
+                                 const float* nu, int64_t N, int K, int L, int S, float* x, float* lz, float* Tp,
+                                 float* noise_ws, void* stream);
 /* The same with the key read from a DEVICE word at execution time (in-kernel shapes only, vmp_svae_rng_in_kernel != 0): a
  * launch captured in a HIP graph draws fresh noise on every replay once the caller refreshes *seed_dev.            */
 int    vmp_svae_estep_fwd_rng_dev(const float* eta1, const float* eta2d, const float* hk, const float* Pk, const float* bias,
@@ -611,6 +622,17 @@ int    vmp_student_t_logprob_bwd(const float* y, const float* mu, const float* W
 int    vmp_eval_cell_metrics(const float* y, const float* mean, const float* var, const float* logw,
                              int logw_per_sample, const uint8_t* mask, int mask_mse, int64_t N, int K, int S, int Dy,
                              float* mse, float* lse, void* stream);
+
+/* The same two per-cell metrics straight from the samples x (N,K,S,L): the fused decoder forward (vmp_decoder_loglike_fwd: same
+ * parameters, same compiled range L, Dy <= 8, U <= 64, bit-identical mean / var per row) with the metrics as its epilogue, so that
+ * no (N,K,S,Dy) tensor exists.  The kernel leaves two fp32 words per sample row in `ws` (N*K*S*8 bytes, 8-byte aligned, required);
+ * a second small launch takes the mean / the online log-sum-exp over s.  Definitions and quirks as above (`log var`, not
+ * log(var + 1e-8); mask_mse); logw is (N,K) or NULL; mask (N,Dy) uint8 or NULL; mse, lse (N,K): either may be NULL, not both.
+ * The sum over d runs in another order than vmp_eval_cell_metrics' (last bits).                                          */
+int    vmp_decoder_eval_fwd(const float* x, const float* y, const float* W0, const float* b0, const float* W1, const float* b1,
+                            const float* W2, const float* b2, const float* Ws, const float* bs1, const float* bs2,
+                            const uint8_t* mask, int mask_mse, const float* logw, int64_t N, int K, int S, int L, int Dy,
+                            int U, float* mse, float* lse, void* ws, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Multi-GPU exchange (replaces the in-graph tower gather + mean of experiments.py:247-260 and

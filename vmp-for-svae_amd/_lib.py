@@ -39,6 +39,9 @@ _SIGNATURES = {
     'vmp_svae_rng_in_kernel': (_c.c_int, [_c.c_int, _c.c_int, _c.c_int]),
     'vmp_svae_philox_noise': (_c.c_int, [_c.c_uint64, _c.c_int64, _c.c_int, _c.c_int, _c.c_int, _P, _P]),
     'vmp_svae_estep_fwd_rng': (_c.c_int, [_P] * 5 + [_c.c_uint64] + [_P] * 4 + [_c.c_int64, _c.c_int, _c.c_int, _c.c_int, _P, _P, _P, _P, _P]),
+    'vmp_svae_philox_noise_at': (_c.c_int, [_c.c_uint64, _c.c_int64, _c.c_int64, _c.c_int, _c.c_int, _c.c_int, _P, _P]),
+    'vmp_svae_estep_fwd_rng_at': (_c.c_int, [_P] * 5 + [_c.c_uint64, _c.c_int64] + [_P] * 4 + [_c.c_int64, _c.c_int, _c.c_int, _c.c_int]
+                                  + [_P] * 5),
     'vmp_svae_philox_noise_dev': (_c.c_int, [_P, _c.c_int64, _c.c_int, _c.c_int, _c.c_int, _P, _P]),
     'vmp_svae_estep_fwd_rng_dev': (_c.c_int, [_P] * 10 + [_c.c_int64, _c.c_int, _c.c_int, _c.c_int, _P, _P, _P, _P]),
     'vmp_svae_fwd_mom_blocks': (_c.c_int, [_c.c_int64, _c.c_int, _c.c_int, _c.c_int]),
@@ -60,6 +63,7 @@ _SIGNATURES = {
     'vmp_student_t_bwd_blocks': (_c.c_int, [_c.c_int64, _c.c_int]),
     'vmp_student_t_logprob_bwd': (_c.c_int, [_P, _P, _P, _P, _P, _c.c_int64, _c.c_int, _c.c_int, _c.c_int, _P, _P, _P]),
     'vmp_eval_cell_metrics': (_c.c_int, [_P, _P, _P, _P, _c.c_int, _P, _c.c_int, _c.c_int64, _c.c_int, _c.c_int, _c.c_int, _P, _P, _P]),
+    'vmp_decoder_eval_fwd': (_c.c_int, [_P] * 12 + [_c.c_int, _P, _c.c_int64] + [_c.c_int] * 5 + [_P, _P, _P, _c.c_size_t, _P]),
     'vmp_diag_gauss_loglike_fwd': (_c.c_int, [_P, _P, _P, _c.c_int64, _c.c_int, _c.c_int, _c.c_int, _c.c_float, _P, _P]),
     'vmp_diag_gauss_loglike_bwd': (_c.c_int, [_P, _P, _P, _P, _c.c_int64, _c.c_int, _c.c_int, _c.c_int, _c.c_float, _P, _P, _P]),
     'vmp_bernoulli_rows_fwd': (_c.c_int, [_P, _P, _P, _c.c_int64, _c.c_int, _c.c_int, _c.c_int, _P, _P]),

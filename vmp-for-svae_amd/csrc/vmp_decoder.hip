@@ -602,6 +602,131 @@ __global__ __launch_bounds__(FWD_THREADS, 2) void dec_fwd_kernel(DecArgs a) {
     dec_fwd_body<UT>(a, sm, blockIdx.x, gridDim.x);
 }
 
+// Test-time evaluation (reference experiments.py:270-304 / losses.py:9-38, 83-145 at nb_samples_te = 100): the forward pass above with
+// the evaluation metrics as its epilogue - mean and var of a sample row stay in the tile's registers (the same fill_images /
+// dec_forward_tile instructions as dec_fwd_kernel: bit-identical mu, vr) and only TWO fp32 words per row (n,k,s) leave the kernel:
+//   rows[row] = ( sum_d m'_nd (y_nd - mean_d)^2 ,  -1/2 sum_d m_nd [ (y_nd - mean_d)^2 / var_d + log var_d + log 2pi ] )
+// with m = the missing-data mask (1 without one) and m' = m under mask_mse, else 1 - the per-row terms of vmp_eval_cell_metrics
+// (csrc/vmp_loglike.hip: true division, logf, `log var` without the 1e-8 of the training loss), summed over d as lane-group partials
+// (d = 2g, 2g+1) + rows4_sum instead of sequentially.  dec_eval_reduce_kernel then takes the mean / the online log-sum-exp over s.
+struct EvalEpi {
+    const uint8_t* mask;   // (N, Dy) or NULL
+    int mask_mse;
+    v2f* rows;             // (R)
+};
+// (U <= 32: eight blocks per CU asked of the register allocator - the 64 registers that give dec_fwd_kernel<1>, <2> their eight waves
+// per SIMD)
+template <int UT>
+__global__ __launch_bounds__(FWD_THREADS, UT <= 2 ? 8 : 2) void dec_eval_kernel(DecArgs a, EvalEpi e) {
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    using I = Img<UT>;
+    fill_images<UT, false, FWD_THREADS>(sm, a);
+    __syncthreads();
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, g = lane >> 4, c = lane & 15;
+    const unsigned ntiles = (a.R + 15u) / 16u;
+    const unsigned nwaves = gridDim.x * (FWD_THREADS / WAVE);
+    const int L = a.L, Dy = a.Dy;
+    const float invS = 1.0f / (float)a.S, invK = 1.0f / (float)a.K;
+    const unsigned ncells = a.R / a.S;
+    const float LOG2PI = 1.8378770664093454836f;
+    for (unsigned tile = blockIdx.x * (FWD_THREADS / WAVE) + wave; tile < ntiles; tile += nwaves) {
+        asm volatile("" ::: "memory");                  // as dec_fwd_body: the operand-image reads stay inside the loop
+        const unsigned row = tile * 16u + c;
+        const bool ok = row < a.R;
+        const unsigned rr = ok ? row : a.R - 1u;
+        const float* __restrict__ xr = a.x + (size_t)rr * L;
+        const float xb0 = g < L ? xr[g] : 0.f;
+        const float xb1 = 4 + g < L ? xr[4 + g] : 0.f;
+        unsigned xs[3];
+        split_bf16<3>(v2f{xb0, xb1}, xs);
+        const XOps xo = x_operands(xs);
+        f32x4 h0[UT], h1[UT], O;
+        unsigned h0s[3][4 * I::KB], h1s[3][4 * I::KB];
+        dec_forward_tile<UT, false>(sm, lane, xo, -1, h0, h0s, h1, h1s, O);
+        asm volatile("" ::: "memory");                  // the epilogue's loads and arithmetic stay behind the tile
+        // y and the mask bytes are fetched behind the tile's arithmetic (nothing of the epilogue lives across it: the register file
+        // is dec_fwd_kernel's or smaller); the loads' latency is covered by the other resident waves
+        const RowMap rm = row_map(tile, c, a.S, a.K, invS, invK, ncells);
+        const size_t yi0 = (size_t)rm.n * Dy;
+        float yv[2], mv[2];
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const bool in = 2 * g + j < Dy;
+            yv[j] = in ? a.y[yi0 + 2 * g + j] : 0.f;
+            mv[j] = (e.mask && in) ? (e.mask[yi0 + 2 * g + j] ? 1.f : 0.f) : 1.f;
+        }
+        float q = 0.f, lp = 0.f;
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int d = 2 * g + j;
+            const float mu = O[j];
+            const float vr = softplus_f(O[2 + j]) + sm[I::SP2 + (d & 7)];
+            const float df = yv[j] - mu;
+            const float qd = (e.mask_mse ? mv[j] * df : df) * df;
+            const float term = df * df / vr + logf(vr) + LOG2PI;
+            q += d < Dy ? qd : 0.f;
+            lp += d < Dy ? -0.5f * mv[j] * term : 0.f;
+        }
+        q = rows4_sum(q);
+        lp = rows4_sum(lp);
+        if (ok && g == 0) e.rows[row] = v2f{q, lp};
+    }
+}
+
+// (rows (N,K,S) pairs, logw (N,K) or NULL) -> mse (N,K) = mean_s q, lse (N,K) = log 1/S sum_s exp(logw + lp): the S-reduction of
+// eval_kernel (csrc/vmp_loglike.hip) - min(S, 64) lanes per cell, an online log-sum-exp per lane, lanes merged in a fixed order.
+struct EvalRedArgs {
+    const v2f* rows;
+    const float* logw;
+    float* mse;
+    float* lse;
+    long long cells;
+    int S;
+};
+__global__ __launch_bounds__(256) void dec_eval_reduce_kernel(EvalRedArgs a) {
+    __shared__ float s_mx[4][WAVE], s_se[4][WAVE], s_sq[4][WAVE];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
+    const int S = a.S;
+    const int SL = S < WAVE ? S : WAVE;
+    const int CPT = WAVE / SL;
+    const int c_in = lane / SL, sub = lane - c_in * SL;
+    const bool lane_on = c_in < CPT;
+    const long long ntiles = (a.cells + CPT - 1) / CPT;
+    for (long long t = (long long)blockIdx.x * nw + wave; t < ntiles; t += (long long)gridDim.x * nw) {
+        const long long cell = t * CPT + c_in;
+        const bool on = lane_on && cell < a.cells;
+        const long long cc = on ? cell : 0;
+        float mx = -INFINITY, se = 0.f, sq = 0.f;
+        if (on) {
+            const float lw = a.logw ? a.logw[cc] : 0.f;
+            for (int s = sub; s < S; s += SL) {
+                const v2f pr = a.rows[cc * S + s];
+                sq += pr.x;
+                const float lp = pr.y + lw;
+                const float nm = fmaxf(mx, lp);                     // online log-sum-exp; a term of -inf (logw = -inf) adds nothing
+                if (nm > -INFINITY) se = se * __expf(mx - nm) + __expf(lp - nm);
+                mx = nm;
+            }
+        }
+        s_mx[wave][lane] = mx; s_se[wave][lane] = se; s_sq[wave][lane] = sq;
+        __builtin_amdgcn_wave_barrier();
+        if (on && sub == 0) {
+            float M = -INFINITY, Q = 0.f;
+            for (int j = 0; j < SL; ++j) { M = fmaxf(M, s_mx[wave][c_in * SL + j]); Q += s_sq[wave][c_in * SL + j]; }
+            if (a.mse) a.mse[cell] = Q / (float)S;
+            if (a.lse) {
+                float E = 0.f;
+                for (int j = 0; j < SL; ++j) {
+                    const float mj = s_mx[wave][c_in * SL + j];
+                    if (mj > -INFINITY) E += s_se[wave][c_in * SL + j] * __expf(mj - M);
+                }
+                a.lse[cell] = M > -INFINITY ? M + logf(E) - logf((float)S) : -INFINITY;
+            }
+        }
+        __builtin_amdgcn_wave_barrier();
+    }
+}
+
 // The first launch of the minibatch training step (round 6): everything that depends on the parameters and the minibatch only, as
 // ONE grid - blocks [0, nb) the encoder's forward pass (dec_fwd_body), blocks [nb, nb + K) the recognition unpacking and
 // [nb + K, nb + 2K) the theta packing (wave 0 of the block: phi_prep_body / theta_pack_body, vmp_prep_parts.h; prep_both_kernel was
@@ -1294,6 +1419,45 @@ int decoder_fwd_impl(const char* what, float vscale, const float* x, const float
     return check_launch(what);
 }
 
+int decoder_eval_impl(const char* what, const float* x, const float* y, const float* W0, const float* b0, const float* W1, const float* b1,
+                      const float* W2, const float* b2, const float* Ws, const float* bs1, const float* bs2, const uint8_t* mask,
+                      int mask_mse, const float* logw, int64_t N, int K, int S, int L, int Dy, int U, float* mse, float* lse, void* ws,
+                      size_t ws_bytes, void* stream) {
+    if (int e = dec_check(what, N, K, S, L, Dy, U)) return e;
+    if (!x || !y || !W0 || !b0 || !W1 || !b1 || !W2 || !b2 || !Ws || !bs1 || !bs2 || !ws || (!mse && !lse)) {
+        set_error("%s: NULL argument", what);
+        return VMP_E_BADARG;
+    }
+    if (N == 0) return 0;
+    const size_t rows = (size_t)N * K * S;
+    if (ws_bytes < rows * sizeof(v2f) || (reinterpret_cast<uintptr_t>(ws) & 7)) {
+        set_error("%s: workspace of %zu bytes (8-byte aligned) needed for the per-row pairs, got %zu", what, rows * sizeof(v2f), ws_bytes);
+        return VMP_E_WS;
+    }
+    DecArgs a{};
+    a.x = x; a.y = y; a.W0 = W0; a.b0 = b0; a.W1 = W1; a.b1 = b1; a.W2 = W2; a.b2 = b2; a.Ws = Ws; a.bs1 = bs1; a.bs2 = bs2;
+    a.vscale = 1.0f;
+    a.R = (unsigned)rows; a.K = (unsigned)K; a.S = (unsigned)S; a.L = L; a.Dy = Dy; a.U = U;
+    const EvalEpi e{mask, (mask && mask_mse) ? 1 : 0, static_cast<v2f*>(ws)};
+    const int blocks = dec_fwd_blocks((long long)a.R);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+#define DEC_EVAL(UTV)                                                                                                 \
+    do {                                                                                                              \
+        const int lds = Img<UTV>::FWD_END * (int)sizeof(float);                                                       \
+        if (const int rc_ = set_dyn_lds(reinterpret_cast<const void*>(dec_eval_kernel<UTV>), (size_t)lds, "dec_eval_kernel")) return rc_; \
+        hipLaunchKernelGGL((dec_eval_kernel<UTV>), dim3(blocks), dim3(FWD_THREADS), lds, s, a, e);                    \
+    } while (0)
+    DEC_DISPATCH(U, DEC_EVAL);
+#undef DEC_EVAL
+    if (int rc = check_launch("dec_eval_kernel")) return rc;
+    const EvalRedArgs r{static_cast<const v2f*>(ws), logw, mse, lse, (long long)N * K, S};
+    const int SL = S < WAVE ? S : WAVE, CPT = WAVE / SL;
+    long long rb = (((long long)N * K + CPT - 1) / CPT + 3) / 4;
+    if (rb > 4096) rb = 4096;
+    hipLaunchKernelGGL(dec_eval_reduce_kernel, dim3((int)rb), dim3(256), 0, s, r);
+    return check_launch("dec_eval_reduce_kernel");
+}
+
 int mlp_gauss_bwd_impl(const char* what, float vscale, bool lazy, const float* x, const float* gmean, const float* gvar, const float* W0, const float* b0,
                       const float* W1, const float* b1, const float* W2, const float* b2, const float* Ws, const float* bs1,
                       const float* bs2, int64_t R, int L, int Dy, int U, float* dx, float* dparams, void* ws,
@@ -1397,6 +1561,14 @@ int vmp_decoder_param_words(int L, int U, int Dy) { return dec_geo(L, U, Dy).PW;
 
 size_t vmp_decoder_workspace_bytes(int64_t N, int K, int S, int L, int U, int Dy) {
     return (size_t)dec_bwd_blocks((long long)N * K * S) * (size_t)dec_geo(L, U, Dy).PW * sizeof(float);
+}
+
+int vmp_decoder_eval_fwd(const float* x, const float* y, const float* W0, const float* b0, const float* W1, const float* b1,
+                         const float* W2, const float* b2, const float* Ws, const float* bs1, const float* bs2, const uint8_t* mask,
+                         int mask_mse, const float* logw, int64_t N, int K, int S, int L, int Dy, int U, float* mse, float* lse,
+                         void* ws, size_t ws_bytes, void* stream) {
+    return decoder_eval_impl("vmp_decoder_eval_fwd", x, y, W0, b0, W1, b1, W2, b2, Ws, bs1, bs2, mask, mask_mse, logw, N, K, S, L, Dy, U,
+                             mse, lse, ws, ws_bytes, stream);
 }
 
 int vmp_decoder_loglike_fwd(const float* x, const float* y, const float* W0, const float* b0, const float* W1,

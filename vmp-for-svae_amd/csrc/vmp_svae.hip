@@ -50,6 +50,8 @@ struct EFwdArgs {
     float* xs;              // (N,L)
     float* r;               // (N,K)
     double* mom;            // (blocks, 16, 48): features [x_0..x_7 | 1 | x_a x_b (a >= b, packed lower) | 0 0 0]
+    long long row0;         // in-kernel noise of the streaming forms: row n of the launch draws the stream of global row row0 + n (the
+                            // _at entry points; 0 everywhere else).  The minibatch form (svae_estep_fwd1_kernel) does not read it.
 #ifdef VMP_DEBUG_TS
     long long* dbg_t;
 #endif
@@ -792,7 +794,7 @@ __device__ __forceinline__ void philox_normal8(unsigned long long cell, unsigned
     for (int t = 0; t < 4; ++t) p[t] = box_muller_word<TAB>(c[t], sct);
 }
 
-struct NoiseArgs { float* out; long long cells; int L, S; unsigned long long seed; const unsigned long long* seed_dev; };
+struct NoiseArgs { float* out; long long cells; int L, S; unsigned long long seed; const unsigned long long* seed_dev; long long cell0; };
 // Materialises the same stream as a (cells, L, S) tensor: for shapes the in-kernel path does not cover, and for tests.
 __global__ __launch_bounds__(256) void philox_noise_kernel(NoiseArgs a) {
     const int SP = (a.S + 1) >> 1, L4 = (a.L + 3) / 4, NB = SP * L4;
@@ -801,7 +803,7 @@ __global__ __launch_bounds__(256) void philox_noise_kernel(NoiseArgs a) {
         const long long cell = e / NB;
         const int b = (int)(e - cell * NB), sp = b / L4, j = b - sp * L4;
         v2f pr[4];
-        philox_normal8((unsigned long long)cell, (unsigned)b, a.seed_dev ? *a.seed_dev : a.seed, pr);
+        philox_normal8((unsigned long long)(cell + a.cell0), (unsigned)b, a.seed_dev ? *a.seed_dev : a.seed, pr);
         float* o = a.out + cell * a.L * a.S;
         const int s2 = 2 * sp;
 #pragma unroll
@@ -915,6 +917,7 @@ __global__ __launch_bounds__((RNG ? 8 : 4) * WAVE) void svae_estep_fwd4_kernel(E
     const int r = lane / K, k = lane - r * K, rbase = lane_on ? r * K : 0;
     const bool k16 = (K == 16);
     const unsigned long long rng_seed = (RNG && a.seed_dev) ? *a.seed_dev : a.seed;
+    const unsigned long long rng_cell0 = (unsigned long long)a.row0 * (unsigned long long)K;   // Philox cell id of the launch's cell 0
     SV_TS(16);
 
 
@@ -1193,7 +1196,7 @@ __global__ __launch_bounds__((RNG ? 8 : 4) * WAVE) void svae_estep_fwd4_kernel(E
 #pragma unroll
             for (int j = 0; j < L4; ++j) {
                 v2f p4[4];
-                philox_normal8<SCT>(cellid, pr * L4 + j, rng_seed, p4, sct);
+                philox_normal8<SCT>(cellid + rng_cell0, pr * L4 + j, rng_seed, p4, sct);
 #pragma unroll
                 for (int t2 = 0; t2 < 4; ++t2)
                     if (4 * j + t2 < L) eo[4 * j + t2] = p4[t2];
@@ -2039,7 +2042,7 @@ static int fwd4_plan(int K, int L, int S, int& CS, size_t& lds4, bool rng = fals
     return nw4;
 }
 
-static int run_fwd(EFwdArgs a, int L, void* stream, bool rng) {
+static int run_fwd(EFwdArgs a, int L, void* stream, bool rng, bool fwd1_ok = true) {
 #ifdef VMP_DEBUG_TS
     a.dbg_t = g_dbg_svae;
 #endif
@@ -2054,7 +2057,7 @@ static int run_fwd(EFwdArgs a, int L, void* stream, bool rng) {
         {   // minibatch sizes: one block per tile, one wave per sample pair (svae_estep_fwd1_kernel)
             const long long nt1 = (N + WAVE / K - 1) / (WAVE / K);
             const int P = (S + 1) / 2;
-            if (VMP_FWD1 && !a.mom && nt1 <= FWD1_MAX_TILES && P <= FWD1_MAX_PAIRS) {
+            if (VMP_FWD1 && fwd1_ok && !a.mom && nt1 <= FWD1_MAX_TILES && P <= FWD1_MAX_PAIRS) {
                 rc = -1;
                 VMP_DISPATCH_L(L, {
                     hipLaunchKernelGGL((svae_estep_fwd1_kernel<LL>), dim3((int)nt1), dim3(P * WAVE), 0, static_cast<hipStream_t>(stream), a);
@@ -2193,11 +2196,14 @@ int vmp_svae_rng_in_kernel(int K, int L, int S) {
     return (K >= 1 && K <= 64 && L >= 1 && L <= 8 && fwd4_plan(K, L, S, CS, lds4, true, &ps) >= 1) ? 1 : 0;
 }
 
-static int philox_noise_impl(uint64_t seed, const uint64_t* seed_dev, int64_t N, int K, int L, int S, float* noise, void* stream) {
+static int philox_noise_impl(uint64_t seed, const uint64_t* seed_dev, int64_t N, int K, int L, int S, float* noise, void* stream,
+                             int64_t row0 = 0) {
     int rc = check_sv(N, K, L, S);
     if (rc) return rc;
     if (!noise) { set_error("vmp_svae_philox_noise: null pointer"); return VMP_E_BADARG; }
-    NoiseArgs na{noise, (long long)N * K, L, S, (unsigned long long)seed, reinterpret_cast<const unsigned long long*>(seed_dev)};
+    if (row0 < 0) { set_error("vmp_svae_philox_noise_at: row0 < 0"); return VMP_E_BADARG; }
+    NoiseArgs na{noise, (long long)N * K, L, S, (unsigned long long)seed, reinterpret_cast<const unsigned long long*>(seed_dev),
+                 (long long)row0 * K};
     const long long total = na.cells * ((S + 1) / 2) * ((L + 3) / 4);
     long long blocks = (total + 255) / 256;
     if (blocks > 256 * 16) blocks = 256 * 16;
@@ -2230,6 +2236,36 @@ int vmp_svae_estep_fwd_rng(const float* eta1, const float* eta2d, const float* h
     }
     if (!noise_ws) { set_error("vmp_svae_estep_fwd_rng: this shape needs the (N,K,L,S) noise workspace"); return VMP_E_WS; }
     rc = vmp_svae_philox_noise(seed, N, K, L, S, noise_ws, stream);
+    if (rc) return rc;
+    a.noise = noise_ws;
+    a.vec_ok = al16(noise_ws) && al16(x);
+    return run_fwd(a, L, stream, false);
+}
+
+int vmp_svae_philox_noise_at(uint64_t seed, int64_t row0, int64_t N, int K, int L, int S, float* noise, void* stream) {
+    return philox_noise_impl(seed, nullptr, N, K, L, S, noise, stream, row0);
+}
+
+// Forward only, no epilogue, always the streaming kernels (never svae_estep_fwd1_kernel, whose T' sums its per-pair partial sums in
+// another order): x, lz, T' of a row do not depend on how many rows the launch holds, so a set walked in chunks == the set in one launch.
+int vmp_svae_estep_fwd_rng_at(const float* eta1, const float* eta2d, const float* hk, const float* Pk, const float* bias,
+                              uint64_t seed, int64_t row0, const float* mk, const float* Wk, const float* kappa, const float* nu,
+                              int64_t N, int K, int L, int S, float* x, float* lz, float* Tp, float* noise_ws, void* stream) {
+    int rc = check_sv(N, K, L, S);
+    if (rc) return rc;
+    if (!eta1 || !eta2d || !hk || !Pk || !bias || !mk || !Wk || !kappa || !x || !lz || !Tp) {
+        set_error("vmp_svae_estep_fwd_rng_at: null pointer");
+        return VMP_E_BADARG;
+    }
+    if (row0 < 0) { set_error("vmp_svae_estep_fwd_rng_at: row0 < 0"); return VMP_E_BADARG; }
+    EFwdArgs a{eta1, eta2d, hk, Pk, bias, nullptr, mk, Wk, kappa, nu, x, lz, Tp, N, K, S, 0, (unsigned long long)seed};
+    a.row0 = (long long)row0;
+    if (vmp_svae_rng_in_kernel(K, L, S)) {
+        a.vec_ok = al16(x);
+        return run_fwd(a, L, stream, true, false);
+    }
+    if (!noise_ws) { set_error("vmp_svae_estep_fwd_rng_at: this shape needs the (N,K,L,S) noise workspace"); return VMP_E_WS; }
+    rc = vmp_svae_philox_noise_at(seed, row0, N, K, L, S, noise_ws, stream);
     if (rc) return rc;
     a.noise = noise_ws;
     a.vec_ok = al16(noise_ws) && al16(x);

@@ -16,8 +16,14 @@ from .models import svae, vae
 from .training import SVAETrainer
 
 
-def evaluate(tr, y, labels, nb_samples, seed=0):
-    """experiments.py:270-304: inference on the evaluation set with nb_samples_te samples, then the metrics."""
+def evaluate(tr, y, labels, nb_samples, seed=0, streaming=False, max_workspace_bytes=losses.DEFAULT_EVAL_WORKSPACE):
+    """experiments.py:270-304: inference on the evaluation set with nb_samples_te samples, then the metrics.
+    streaming=True: the same measurement through losses.streaming_metrics - the set is walked in chunks whose buffers fit
+    max_workspace_bytes (any set size; in-kernel Philox noise keyed by `seed` instead of torch's generator)."""
+    if streaming:
+        m = losses.streaming_metrics(y, tr.phi_gmm, tr.encoder_layers, tr.decoder_layers, nb_samples, labels=labels,
+                                     stddev_init_nn=tr.stddev_init_nn, seed=seed, max_workspace_bytes=max_workspace_bytes)
+        return {k: m[k] for k in ('mse', 'loli', 'entropy', 'purity') if k in m}
     with torch.no_grad():
         y_rec, _, x_k, x_s, log_z, _, _ = svae.inference(y, tr.phi_gmm, tr.encoder_layers, tr.decoder_layers, nb_samples,
                                                          stddev_init_nn=tr.stddev_init_nn, seed=seed)
@@ -29,9 +35,16 @@ def evaluate(tr, y, labels, nb_samples, seed=0):
     return out
 
 
-def evaluate_imputation(tr, y, missing_data_mask, nb_samples_pert=20, nb_samples_te=100, seed=0):
+def evaluate_imputation(tr, y, missing_data_mask, nb_samples_pert=20, nb_samples_te=100, seed=0, streaming=False,
+                        max_workspace_bytes=losses.DEFAULT_EVAL_WORKSPACE):
     """experiments.py:361-377: missing entries are replaced by noise nb_samples_pert times, each perturbed set is pushed
-    through svae.inference with nb_samples_te samples, and the imputations are scored on the missing entries."""
+    through svae.inference with nb_samples_te samples, and the imputations are scored on the missing entries.
+    streaming=True: losses.streaming_imputation_losses (each perturbed set walked in chunks within max_workspace_bytes)."""
+    if streaming:
+        mse, lopr = losses.streaming_imputation_losses(y, missing_data_mask, tr.phi_gmm, tr.encoder_layers, tr.decoder_layers,
+                                                       nb_samples_pert, nb_samples_te, stddev_init_nn=tr.stddev_init_nn, seed=seed,
+                                                       max_workspace_bytes=max_workspace_bytes)
+        return {'imp_mse': float(mse), 'imp_logprob': float(lopr)}
     def impute(y_perturbed):                                          # experiments.py:365-372
         (y_k_mean, out2), _, _, _, log_r_nk, _, _ = svae.inference(
             y_perturbed.contiguous(), tr.phi_gmm, tr.encoder_layers, tr.decoder_layers, nb_samples_te,
@@ -104,7 +117,8 @@ def load_checkpoint(tr, path):
 
 def run(config, nb_iters=2000, size_minibatch=100, nb_samples=10, nb_samples_te=100, measurement_freq=500,
         path_dataset=None, device='cuda', verbose=True, ratio_tr=0.7, imputation_freq=None, nb_samples_pert=20,
-        ratio_missing_data=0.1, checkpoint_freq=None, checkpoint_dir=None, graph=True, group=None, steps_per_replay=1):
+        ratio_missing_data=0.1, checkpoint_freq=None, checkpoint_dir=None, graph=True, group=None, steps_per_replay=1,
+        eval_mode='materialised', max_workspace_bytes=losses.DEFAULT_EVAL_WORKSPACE):
     """One run of the reference driver (experiments.py:86-457).  Under torch.distributed (one process per GPU) every
     rank draws the same shuffled minibatch stream and trains on its tower_slice of each minibatch - the reference's
     tf.split over towers (data.py:174-175, experiments.py:196-244); SVAETrainer.step sums moments / ELBO and AVERAGES
@@ -120,7 +134,12 @@ def run(config, nb_iters=2000, size_minibatch=100, nb_samples=10, nb_samples_te=
     (_klinalg), but a caller's own GPU linalg after such a run is exposed.
     steps_per_replay = n > 1 (single-process graph runs whose step is the trainer's direct kernel sequence): up to n consecutive
     iterations that no measurement / imputation / checkpoint iteration interrupts run from ONE graph replay
-    (GraphedSVAEStep(steps_per_replay=n)); the same steps on the same minibatches, bit for bit - only the launches are batched."""
+    (GraphedSVAEStep(steps_per_replay=n)); the same steps on the same minibatches, bit for bit - only the launches are batched.
+    eval_mode: 'materialised' (the reference's measurement: svae.inference on the whole evaluation set) or 'streaming' (evaluate /
+    evaluate_imputation with streaming=True: chunks within max_workspace_bytes, any evaluation-set size).  Training is the same."""
+    if eval_mode not in ('materialised', 'streaming'):
+        raise ValueError("eval_mode must be 'materialised' or 'streaming'")
+    streaming = eval_mode == 'streaming'
     import torch.distributed as dist
     world = dist.get_world_size(group) if (dist.is_available() and dist.is_initialized()) else 1
     rank = dist.get_rank(group) if world > 1 else 0
@@ -178,11 +197,11 @@ def run(config, nb_iters=2000, size_minibatch=100, nb_samples=10, nb_samples_te=
             else:
                 out = tr.step(yb)
         if i % measurement_freq == 0 or i == nb_iters - 1:
-            m = evaluate(tr, Xte, Lte, nb_samples_te, seed=config.get('seed', 0))
+            m = evaluate(tr, Xte, Lte, nb_samples_te, seed=config.get('seed', 0), streaming=streaming, max_workspace_bytes=max_workspace_bytes)
             m['iter'], m['neg_normed_elbo'] = i, -float(out['elbo']) / size_minibatch      # experiments.py:318-320
             if imputation_freq and (i % imputation_freq == 0 or i == nb_iters - 1):       # experiments.py:446-452
                 m.update(evaluate_imputation(tr, Xte, missing_data_mask, nb_samples_pert, nb_samples_te,
-                                             seed=config.get('seed', 0)))
+                                             seed=config.get('seed', 0), streaming=streaming, max_workspace_bytes=max_workspace_bytes))
             history.append(m)
             if verbose and rank == 0:
                 print('Iteration %5d\t\t%.4fsec\t\t%.4f   %s' % (i, time.time() - t0, m['neg_normed_elbo'],

@@ -27,21 +27,33 @@ class PhiloxNoise(object):
     `seed`; include/vmp_hip.h vmp_svae_estep_fwd_rng).  The reference draws eps inside the step the same way
     (models/svae.py:113-114).  materialise() returns the identical stream as a tensor."""
 
-    def __init__(self, seed, nb_samples, seed_dev=None, epilogue=False):
+    def __init__(self, seed, nb_samples, seed_dev=None, epilogue=False, row0=0, at=None):
         """seed_dev: a one-element int64 device tensor that holds the key instead of `seed` - read by the kernel when it
         RUNS, so that a launch captured in a HIP graph draws fresh noise per replay (in-kernel shapes only).
         epilogue: ask the E-step kernel that consumes this object to also do what the step does next with a cell's values
         (vmp_svae_estep_fwd_rng_epi): the one-draw-per-row sub-sampling (svae.py:122-151, 514), r = exp(log_z) and - where the
         kernel covers it (K = 16, L = 8) - per-block partials of the M-step's raw moments; SvaeEStepFn leaves them in
-        .x_samples (N,L), .r_nk (N,K), .mom ((blocks,16,48) fp64 or None).  All three None when the shape is not in-kernel."""
+        .x_samples (N,L), .r_nk (N,K), .mom ((blocks,16,48) fp64 or None).  All three None when the shape is not in-kernel.
+        row0: row n of the tensor / launch draws the stream of global row row0 + n (a set walked in chunks: the chunk that starts at
+        row0 gets the noise it gets in one launch over the whole set; vmp_svae_philox_noise_at / vmp_svae_estep_fwd_rng_at - forward
+        only, by-value key, no epilogue).  at=True takes the _at E-step for row0 = 0 as well (every chunk through the same kernels)."""
         self.seed, self.S = int(seed) & 0xFFFFFFFFFFFFFFFF, int(nb_samples)
+        self.row0 = int(row0)
+        self.at = bool(self.row0) if at is None else bool(at)
+        if self.row0 < 0:
+            raise L.VmpError('PhiloxNoise: row0 must be >= 0')
+        if (self.row0 or self.at) and (seed_dev is not None or epilogue):
+            raise L.VmpError('PhiloxNoise: a row offset goes with a by-value key and no epilogue')
         self.seed_dev = seed_dev
         self.epilogue = bool(epilogue)
         self.x_samples = self.r_nk = self.mom = None
 
     def materialise(self, N, K, Ld, device):
         out = torch.empty(N, K, Ld, self.S, dtype=torch.float32, device=device)
-        if self.seed_dev is not None:
+        if self.row0:
+            L.check(L.lib().vmp_svae_philox_noise_at(self.seed, self.row0, N, K, Ld, self.S, L.ptr(out), L.stream()),
+                    'vmp_svae_philox_noise_at')
+        elif self.seed_dev is not None:
             L.check(L.lib().vmp_svae_philox_noise_dev(L.ptr(self.seed_dev), N, K, Ld, self.S, L.ptr(out), L.stream()),
                     'vmp_svae_philox_noise_dev')
         else:
@@ -93,6 +105,13 @@ class SvaeEStepFn(torch.autograd.Function):
                                                        L.ptr(rng.seed_dev), L.ptr(mk), L.ptr(Wk), L.ptr(kappa), L.ptr(nu), N, K,
                                                        Ld, S, L.ptr(x), L.ptr(lz), L.ptr(Tp), L.stream()),
                     'vmp_svae_estep_fwd_rng_dev')
+        elif rng is not None and rng.at:
+            ws = None
+            if not L.lib().vmp_svae_rng_in_kernel(K, Ld, S):
+                ws = torch.empty(N, K, Ld, S, **f32)
+            L.check(L.lib().vmp_svae_estep_fwd_rng_at(L.ptr(eta1), L.ptr(eta2d), L.ptr(hk), L.ptr(Pk), L.ptr(bias), rng.seed, rng.row0,
+                                                      L.ptr(mk), L.ptr(Wk), L.ptr(kappa), L.ptr(nu), N, K, Ld, S, L.ptr(x),
+                                                      L.ptr(lz), L.ptr(Tp), L.ptr(ws), L.stream()), 'vmp_svae_estep_fwd_rng_at')
         elif rng is not None:
             ws = None
             if not L.lib().vmp_svae_rng_in_kernel(K, Ld, S):     # shape outside the in-kernel path: same stream via a scratch tensor
@@ -544,6 +563,37 @@ def decoder_outputs(x, params):
     L.check(L.lib().vmp_decoder_loglike_fwd(L.ptr(x2), None, *[L.ptr(p) for p in params], R, 1, 1, Ld, Dy, U, None,
                                             L.ptr(mean), L.ptr(var), L.stream()), 'vmp_decoder_loglike_fwd')
     return mean.reshape(shape[:-1] + (Dy,)), var.reshape(shape[:-1] + (Dy,))
+
+
+def decoder_eval(x, y, params, logw=None, mask=None, mask_mse=False, want_mse=True, want_lse=True, ws=None):
+    """Per-cell evaluation metrics straight from the samples: (mse (N,K), lse (N,K)) of vmp_eval_cell_metrics on the decoder's
+    outputs for x (N,K,S,L), without those outputs (vmp_decoder_eval_fwd: fused forward + metric epilogue, then the S-reduction).
+    ws: a uint8 buffer of at least N*K*S*8 bytes for the per-row pairs (allocated when None).  No gradient."""
+    x = _c(x.detach(), 'x')
+    if x.dim() != 4:
+        raise L.VmpError('x must have shape (N,K,S,L)')
+    N, K, S, Ld = x.shape
+    params = [_c(p.detach(), n) for p, n in zip(params, DECODER_PARAM_NAMES)]
+    Ld, U, Dy = _decoder_dims(x, params)
+    y = _c(y, 'y', (N, Dy))
+    logw = None if logw is None else _c(logw, 'log_weights', (N, K))
+    m8 = None
+    if mask is not None:
+        if tuple(mask.shape) != (N, Dy):
+            raise L.VmpError('mask must have shape (N,Dy)')
+        m8 = mask.to(torch.uint8).contiguous()
+    need = N * K * S * 8
+    if ws is None:
+        ws = torch.empty(max(need, 8), dtype=torch.uint8, device=x.device)
+    elif ws.numel() < need or ws.dtype != torch.uint8 or not ws.is_cuda:
+        raise L.VmpError('decoder_eval: workspace of %d bytes needed' % need)
+    f32 = dict(dtype=torch.float32, device=x.device)
+    mse = torch.empty(N, K, **f32) if want_mse else None
+    lse = torch.empty(N, K, **f32) if want_lse else None
+    L.check(L.lib().vmp_decoder_eval_fwd(L.ptr(x), L.ptr(y), *[L.ptr(p) for p in params], L.ptr(m8), 1 if mask_mse else 0, L.ptr(logw),
+                                         N, K, S, Ld, Dy, U, L.ptr(mse), L.ptr(lse), L.ptr(ws), ws.numel(), L.stream()),
+            'vmp_decoder_eval_fwd')
+    return mse, lse
 
 
 class PhiPrepFn(torch.autograd.Function):

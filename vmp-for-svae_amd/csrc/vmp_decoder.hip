@@ -40,9 +40,6 @@ using namespace vmp;
 
 namespace {
 
-#ifndef VMP_DEC_FWD_TERMS_FOLLOW_BT
-#define VMP_DEC_FWD_TERMS_FOLLOW_BT 1      // the backward kernel's forward recompute uses its BT-term operands (0: always 3 terms, A/B builds)
-#endif
 constexpr int FWD_THREADS = 256;       // forward: 2+ blocks per CU
 constexpr int BWD_THREADS = 512;       // backward: 1 block per CU (8 waves share one set of operand images)
 constexpr int BWD_WAVES = BWD_THREADS / WAVE;
@@ -186,18 +183,9 @@ __device__ __forceinline__ f32x4 tanh4(f32x4 z) {
 // tanh of a pre-activation that arrives ALREADY scaled by TANH_PRESCALE = 2 log2(e): fill_images folds the factor into the two
 // hidden layers' forward weight images and biases (one multiply per weight per block instead of one per unit per row - 32 of a
 // tile's 605 VALU instructions), so e^(2z) is a bare v_exp_f32 of the accumulator.
-#ifndef VMP_DEC_TANH_FOLD
-#define VMP_DEC_TANH_FOLD 1
-#endif
-#if VMP_DEC_TANH_FOLD
 #define TANH_PRESCALE 2.8853900817779268f
-#define TANH_INSCALE 1.0f
-#else
-#define TANH_PRESCALE 1.0f
-#define TANH_INSCALE 2.8853900817779268f
-#endif
 __device__ __forceinline__ float tanh1(float x) {
-    const float e = __builtin_amdgcn_exp2f(x * TANH_INSCALE);              // e^(2z), x = z * 2 log2(e) when folded
+    const float e = __builtin_amdgcn_exp2f(x);                             // e^(2z), x = z * 2 log2(e)
     return fmaf(-2.0f, rcp_f(e + 1.0f), 1.0f);
 }
 __device__ __forceinline__ f32x4 tanh4(f32x4 z) { return f32x4{tanh1(z[0]), tanh1(z[1]), tanh1(z[2]), tanh1(z[3])}; }
@@ -497,7 +485,7 @@ __device__ __forceinline__ f32x4 gemm_slots(const float* __restrict__ img, int l
 // forward of one 16-row tile.  onev >= 0 on the lanes that own the free padding unit of the last tile: that unit's
 // activation is forced to 1 (its weights are zero everywhere), see the bias-gradient note at dec_bwd_kernel.
 // h0s / h1s = bf16 terms of the activations (the backward pass transposes them for the weight gradients).
-// TERMS = 2 (round 5: the backward kernel's recompute at >= 2^19 rows, VMP_DEC_FWD_TERMS_FOLLOW_BT): 2-term operands for the two
+// TERMS = 2 (round 5: the backward kernel's recompute at >= 2^19 rows follows its BT): 2-term operands for the two
 // hidden layers and the output layer as well - 2^-17 per product on activations whose every consumer is a sum over >= 2^19 rows or
 // the per-row dx.  profiles/r05_decoder_tile_breakdown.txt: the 3-term splits of h0 / h1 were 128 of the tile's 808 VALU
 // instructions and 60 of its 160 MFMAs carried their third-term products; same box 7.14 -> 6.29 ms per 4.2e7 rows.  Against the
@@ -792,29 +780,8 @@ __device__ __forceinline__ void wave_lds_order() {
 // the two half-rows of a write instruction (lanes c < 8 and c >= 8, 256 bytes apart = the same banks) land on different
 // banks; a read still covers each half's 256 bytes exactly once.
 __device__ __forceinline__ int trb_slot(int unit, int half) { return (unit & ~3) | ((unit + 2 * half) & 3); }
-// One ds_write_b32 per packed register instead of two ds_write_b16 (a 16-bit LDS write costs ~8 LDS cycles, a 32-bit one
-// ~4; with the b16 form the LDS pipe was 83 % busy, profiles/r02_decoder_pmc_summary.txt): neighbouring lanes (rows c, c^1)
-// first swap halves, so that the even lane holds (unit 2p: rows c, c+1) and the odd lane (unit 2p+1: rows c-1, c).
-template <int NT, int NTS>
-__device__ __forceinline__ void trb_write(unsigned char* __restrict__ T, int g, int c, const unsigned (&ts)[3][NTS]) {
-    const int half = c >> 3, odd = c & 1;
-    unsigned char* __restrict__ base = T + half * 256 + 2 * ((c & 7) - odd);
-    const unsigned sel = odd ? 0x03020706u : 0x05040100u;
-    int off[2];
-#pragma unroll
-    for (int p = 0; p < 2; ++p) off[p] = trb_slot(4 * g + 2 * p + odd, half) * 16;
-#pragma unroll
-    for (int term = 0; term < 2; ++term)
-#pragma unroll
-        for (int t = 0; t < NT; ++t)
-#pragma unroll
-            for (int p = 0; p < 2; ++p) {
-                const unsigned pk = ts[term][2 * t + p];
-                const unsigned nb = (unsigned)__builtin_amdgcn_update_dpp(0, (int)pk, 0xB1, 0xF, 0xF, true);   // quad_perm:[1,0,3,2]
-                *reinterpret_cast<unsigned*>(base + (term * NT + t) * 512 + off[p]) = __builtin_amdgcn_perm(nb, pk, sel);
-            }
-}
-__device__ __forceinline__ u32x4 trb_read(const unsigned char* __restrict__ p) { return *reinterpret_cast<const u32x4*>(p); }
+// (The x tile is written in this layout by the backward kernel itself - one ds_write_b32 per packed register after neighbouring
+// lanes swapped halves - and read back with one ds_read_b128; the P / Q scratch uses the transpose-read form below.)
 
 // Round 5: the same transposition by gfx950's LDS TRANSPOSE READ (ds_read_b64_tr_b16) instead of VALU lane exchanges.
 // Layout per (term, tile): the 16 rows x 16 units of bf16 ROW-major (512 bytes, as before): lane (g, c) writes its four units
@@ -824,9 +791,6 @@ __device__ __forceinline__ u32x4 trb_read(const unsigned char* __restrict__ p) {
 // "rows 8 (g & 1) .. + 7 of unit c" that one ds_read_b128 of the old layout delivered.  Bank spread: the chunks of a row are
 // XOR-swizzled by the row's bits 2..3 (lanes c, c + 4, .. of a write instruction hit different banks), and the block of rows
 // 8..15 is rotated by 128 bytes (the two 16-lane groups of a read cycle, rows 0..3 and 8..11, use different bank halves).
-#ifndef VMP_DEC_TR16
-#define VMP_DEC_TR16 1            // 0: A/B builds with the VALU transposition (trb_write / trb_read)
-#endif
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ int tr_row_off(int r) { return r < 8 ? 32 * r : 256 + ((32 * (r - 8) + 128) & 255); }
 // byte offset of lane (g, c)'s chunk inside a (term, tile) image
@@ -887,16 +851,13 @@ __global__ __launch_bounds__(BWD_THREADS, 2) void dec_bwd_kernel(DecArgs a) {
     }
     __syncthreads();
     const int rd_c = trb_slot(c, g & 1) * 16;
-    const int rd_hm = (((g >> 1) * UT) * 2 + (g & 1)) * 256 + rd_c;        // operand (h|m) of a UT-tile set: + tile * 512
     const int rd_hm1 = ((g >> 1) * 2 + (g & 1)) * 256 + rd_c;              // operand (h|m) of a 1-tile set
-    const int rd_xx = (g & 1) * 256 + rd_c;                               // operand (h|h): + tile * 512; (m|m): + (NT + tile) * 512
     // transpose-read form (P / Q scratch; the x tile keeps the VALU form): chunk offset of this lane's writes, offsets of its two
     // reads, and the image of its lane group's term for (h|m) operands
     const int tr_w = tr_write_off(g, c);
     int tr_o1, tr_o2;
     tr_read_offs(g, c, tr_o1, tr_o2);
     const int tr_hm = (g >> 1) * UT * 512;                                // (h|m) of a UT-tile set: + tile * 512
-    const int tr_hm1 = (g >> 1) * 512;                                    // (h|m) of a 1-tile set
     const unsigned ntiles = (a.R + 15u) / 16u;
     const int L = a.L, Dy = a.Dy, U = a.U;
     const float invS = 1.0f / (float)a.S, invK = 1.0f / (float)a.K;
@@ -983,9 +944,9 @@ __global__ __launch_bounds__(BWD_THREADS, 2) void dec_bwd_kernel(DecArgs a) {
         f32x4 h0[UT], h1[UT], O;
         {
             unsigned h0s[3][4 * KB], h1s[3][4 * KB];
-            dec_forward_tile<UT, FS, (VMP_DEC_FWD_TERMS_FOLLOW_BT ? BT : 3)>(sm, lane, xo, onev, h0, h0s, h1, h1s, O);
-            if constexpr (VMP_DEC_TR16) { trt_write<UT>(scrPb, tr_w, h0s); trt_write<UT>(scrQb, tr_w, h1s); }
-            else { trb_write<UT>(scrPb, g, c, h0s); trb_write<UT>(scrQb, g, c, h1s); }
+            dec_forward_tile<UT, FS, BT>(sm, lane, xo, onev, h0, h0s, h1, h1s, O);
+            trt_write<UT>(scrPb, tr_w, h0s);
+            trt_write<UT>(scrQb, tr_w, h1s);
         }
 
         DEC_TT(2);
@@ -1018,7 +979,7 @@ __global__ __launch_bounds__(BWD_THREADS, 2) void dec_bwd_kernel(DecArgs a) {
             split_bf16<3>(v2f{dO[2 * p], dO[2 * p + 1]}, t3);
             dOs[0][p] = t3[0]; dOs[1][p] = t3[1]; dOs[2][p] = t3[2];
         }
-        if constexpr (VMP_DEC_TR16) trt_write<1>(scrOb, tr_w, dOs); else trb_write<1>(scrOb, g, c, dOs);
+        trt_write<1>(scrOb, tr_w, dOs);
         const SOps so = slot_operands(dOs);
         DEC_TT(3);
         // ---- dh1 = W2 . dO
@@ -1044,12 +1005,12 @@ __global__ __launch_bounds__(BWD_THREADS, 2) void dec_bwd_kernel(DecArgs a) {
         wave_lds_order();
         u32x4 xT;
         {
-            const u32x4 dTh = VMP_DEC_TR16 ? trt_read(scrOb, tr_o1, tr_o2) : trb_read(scrOb + rd_xx);
-            const u32x4 dTm = VMP_DEC_TR16 ? trt_read(scrOb + 512, tr_o1, tr_o2) : trb_read(scrOb + rd_xx + 512);
-            xT = trb_read(scrXb + rd_hm1);
+            const u32x4 dTh = trt_read(scrOb, tr_o1, tr_o2);
+            const u32x4 dTm = trt_read(scrOb + 512, tr_o1, tr_o2);
+            xT = *reinterpret_cast<const u32x4*>(scrXb + rd_hm1);      // the x tile: written in operand layout (above), one ds_read_b128
 #pragma unroll
             for (int t = 0; t < UT; ++t) {
-                const u32x4 h1T = VMP_DEC_TR16 ? trt_read(scrQb + tr_hm + t * 512, tr_o1, tr_o2) : trb_read(scrQb + rd_hm + t * 512);
+                const u32x4 h1T = trt_read(scrQb + tr_hm + t * 512, tr_o1, tr_o2);
                 aW2[t] = mfma_bf(h1T, dTh, aW2[t]);
                 aW2[t] = mfma_bf(h1T, dTm, aW2[t]);
             }
@@ -1073,7 +1034,7 @@ __global__ __launch_bounds__(BWD_THREADS, 2) void dec_bwd_kernel(DecArgs a) {
         {
             unsigned d1s[3][4 * KB];
             split_tiles<UT, BT>(dh1, d1s);
-            if constexpr (VMP_DEC_TR16) trt_write<UT>(scrQb, tr_w, d1s); else trb_write<UT>(scrQb, g, c, d1s);
+            trt_write<UT>(scrQb, tr_w, d1s);
             gemm_units<UT, UT, BT>(sm + I::B2, lane, d1s, dh0);
         }
         DEC_TT(7);
@@ -1083,12 +1044,12 @@ __global__ __launch_bounds__(BWD_THREADS, 2) void dec_bwd_kernel(DecArgs a) {
             u32x4 dTh[UT], dTm[UT];
 #pragma unroll
             for (int t = 0; t < UT; ++t) {
-                dTh[t] = VMP_DEC_TR16 ? trt_read(scrQb + t * 512, tr_o1, tr_o2) : trb_read(scrQb + rd_xx + t * 512);
-                dTm[t] = VMP_DEC_TR16 ? trt_read(scrQb + (UT + t) * 512, tr_o1, tr_o2) : trb_read(scrQb + rd_xx + (UT + t) * 512);
+                dTh[t] = trt_read(scrQb + t * 512, tr_o1, tr_o2);
+                dTm[t] = trt_read(scrQb + (UT + t) * 512, tr_o1, tr_o2);
             }
 #pragma unroll
             for (int ti = 0; ti < UT; ++ti) {
-                const u32x4 h0T = VMP_DEC_TR16 ? trt_read(scrPb + tr_hm + ti * 512, tr_o1, tr_o2) : trb_read(scrPb + rd_hm + ti * 512);
+                const u32x4 h0T = trt_read(scrPb + tr_hm + ti * 512, tr_o1, tr_o2);
 #pragma unroll
                 for (int tj = 0; tj < UT; ++tj) aW1[ti][tj] = mfma_bf(h0T, dTh[tj], aW1[ti][tj]);
 #pragma unroll
@@ -1108,7 +1069,7 @@ __global__ __launch_bounds__(BWD_THREADS, 2) void dec_bwd_kernel(DecArgs a) {
         {
             unsigned d0s[3][4 * KB];
             split_tiles<UT, BT>(dh0, d0s);
-            if constexpr (VMP_DEC_TR16) trt_write<UT>(scrPb, tr_w, d0s); else trb_write<UT>(scrPb, g, c, d0s);
+            trt_write<UT>(scrPb, tr_w, d0s);
             const f32x4 ds_ = gemm_slots<BT>(sm + I::B3S, lane, so, zero4);
             const f32x4 dxv = gemm_units_1<UT, BT>(sm + I::B3, lane, d0s, zero4) + ds_;        // [dim 4g+v][row c]
             if (ok && a.dx) {
@@ -1126,8 +1087,8 @@ __global__ __launch_bounds__(BWD_THREADS, 2) void dec_bwd_kernel(DecArgs a) {
         wave_lds_order();
 #pragma unroll
         for (int tj = 0; tj < UT; ++tj) {
-            const u32x4 dTh = VMP_DEC_TR16 ? trt_read(scrPb + tj * 512, tr_o1, tr_o2) : trb_read(scrPb + rd_xx + tj * 512);
-            const u32x4 dTm = VMP_DEC_TR16 ? trt_read(scrPb + (UT + tj) * 512, tr_o1, tr_o2) : trb_read(scrPb + rd_xx + (UT + tj) * 512);
+            const u32x4 dTh = trt_read(scrPb + tj * 512, tr_o1, tr_o2);
+            const u32x4 dTm = trt_read(scrPb + (UT + tj) * 512, tr_o1, tr_o2);
             aW0[tj] = mfma_bf(xT, dTh, aW0[tj]);
             aW0[tj] = mfma_bf(xT, dTm, aW0[tj]);
         }

@@ -1672,11 +1672,8 @@ int launch_pass_dk(const PassArgs& a, const Plan& p, int flavour, bool estep, bo
     return check_launch("pass_kernel");
 }
 
-#ifndef VMP_T1_XDL
-#define VMP_T1_XDL 1          // 0: build without the XDL E-part (A/B measurements: tools/build_variant.sh)
-#endif
 // E-part on the XDL pipe: E-step launches with K <= 16 and no missing-data mask
-inline bool use_xdl(int K, bool estep, bool mask) { return VMP_T1_XDL && estep && !mask && K <= 16; }
+inline bool use_xdl(int K, bool estep, bool mask) { return estep && !mask && K <= 16; }
 
 #ifndef VMP_MOM2_ROWS
 #define VMP_MOM2_ROWS (1ll << 16)      // rows from which the moment GEMM of the XDL pass multiplies 2-term operands (pass_xdl_body, MT)

@@ -765,10 +765,7 @@ __device__ __forceinline__ void philox4x32(unsigned (&c)[4], unsigned k0, unsign
 // TAB: (cos, sin) of the 4096 directions come from an LDS table the block fills at start WITH THE SAME v_cos / v_sin instructions
 // (bit-identical to the direct form) - one ds_read_b64 instead of two quarter-rate transcendentals per pair: the sample loop of the
 // forward kernel is bound by VALU issue, and of its ~1.5 k cycles per sample pair 512 were v_log / v_sqrt / v_sin / v_cos.
-#ifndef VMP_FWD_SINCOS_TAB
-#define VMP_FWD_SINCOS_TAB 1
-#endif
-constexpr int SCT_WORDS = 2 * 4096;
+constexpr int SCT_WORDS = 2 * 4096;                  // the pair-staging forms of the forward kernel carry the table
 __device__ __forceinline__ float bm_angle(unsigned b12) { return __uint_as_float((b12 << 11) | 0x3F800000u); }   // 1 + b 2^-12 revolutions
 template <bool TAB>
 __device__ __forceinline__ v2f box_muller_word(unsigned w, const float* __restrict__ sct) {
@@ -834,33 +831,15 @@ __global__ __launch_bounds__(256) void philox_noise_kernel(NoiseArgs a) {
 // and 2.07 -> 1.91 ms, K = 10 1.36 -> 1.28, Student-t 2.50 -> 2.34; either bit alone: 0-3 %.  (The in-kernel-noise form keeps plain
 // stores: VALU-bound, and at minibatch sizes the decoder reads the samples microseconds later.  The ring backward is the opposite
 // case - the two halves of a 128-byte line are asked for by different DMA instructions and the second must hit in L2: nt there
-// cost 40 %, csrc/vmp_svae_ring.h VMP_RING_NT.)
-#ifndef VMP_T2_NT
-#define VMP_T2_NT 3
-#endif
+// cost 40 %, csrc/vmp_svae_ring.h RING_DMA_AUX.)
+constexpr int FWD4_NOISE_DMA_AUX = 2;                // nt on the noise DMA of the noise-tensor form (its sample stores: st_x4<true>)
 template <bool NT>
 __device__ __forceinline__ void st_x4(float4* p, const float4& v) {
     if constexpr (NT) __builtin_nontemporal_store(f32x4{v.x, v.y, v.z, v.w}, reinterpret_cast<f32x4*>(p));
     else *p = v;
 }
-#ifndef VMP_FWD_BC_TILE
-#define VMP_FWD_BC_TILE 1
-#endif
-#ifndef VMP_PST_NOSTORE
-#define VMP_PST_NOSTORE 0            // exploration builds: 1 = the pair-staging form without its global stores
-#endif
-#ifndef VMP_FWD_PAIR_STAGE_BELOW
-#define VMP_FWD_PAIR_STAGE_BELOW 7     // the pair-staging form where the tile buffer admits fewer waves than this (round 4: 8)
-#endif
-#ifndef VMP_FWD_PST2_ALWAYS
-#define VMP_FWD_PST2_ALWAYS 0         // exploration builds: the two-pair staging form also where the tile buffer admits eight waves
-#endif
-#ifndef VMP_FWD_PAIR_STAGE2
-#define VMP_FWD_PAIR_STAGE2 1         // 0: A/B builds without the two-pair staging form
-#endif
-#ifndef VMP_FWD_PAIR_STAGE
-#define VMP_FWD_PAIR_STAGE 1          // 0: A/B builds without the per-pair staging form
-#endif
+constexpr int FWD4_PST_BELOW_WAVES = 7;              // the pair-staging form where the tile buffer admits fewer waves than this (round 4: 8)
+constexpr int FWD4_HKS = 12;                         // pair-staging forms: words per component of the [h_k | bias_k | kappa_k] LDS table
 template <int L, int ST, bool RNG, bool PS = false>
 __global__ __launch_bounds__((RNG ? 8 : 4) * WAVE) void svae_estep_fwd4_kernel(EFwdArgs a, int CS_rt) {
     SV_TS(23);
@@ -880,8 +859,8 @@ __global__ __launch_bounds__((RNG ? 8 : 4) * WAVE) void svae_estep_fwd4_kernel(E
     constexpr bool PST_ = RNG && L == 8 && PS;
     // pair-staging forms: h_k, bias_k, kappa_k of the lane's component are used once per tile - they come from an LDS table
     // [K][HKS] instead of living in 10 VGPRs across the sample loop (the round-6 epilogue needs those registers)
-    constexpr int HKS = 12;
-    constexpr bool SCT = PST_ && VMP_FWD_SINCOS_TAB;     // (cos, sin) of the generator's 4096 directions in LDS (box_muller_word)
+    constexpr int HKS = FWD4_HKS;
+    constexpr bool SCT = PST_;     // (cos, sin) of the generator's 4096 directions in LDS (box_muller_word)
     const int tab0 = (K * PSTR + 3) & ~3;
     const int tab1 = tab0 + (PST_ ? K * HKS : 0);
     const int tab = tab1 + (SCT ? SCT_WORDS : 0);
@@ -892,17 +871,17 @@ __global__ __launch_bounds__((RNG ? 8 : 4) * WAVE) void svae_estep_fwd4_kernel(E
     // nothing is prefetched: ONE buffer, which lets 7 waves instead of 4 share the LDS of a CU
     constexpr int NBUF = RNG ? 1 : 2;
     // cells per tile buffer: the buffers are sized by the tile's CT = (64 / K) K cells, which at K = 10 (60 cells) lets a FOURTH
-    // wave of the noise-tensor form (an EIGHTH of the in-kernel-noise form) share the CU's 160 KB (host side: fwd4_plan, run_fwd)
-    const int BC = VMP_FWD_BC_TILE ? CT : WAVE;
+    // wave of the noise-tensor form (an EIGHTH of the in-kernel-noise form) share the CU's 160 KB (host side: fwd_plan)
+    const int BC = CT;
     // PST (in-kernel noise, L = 8): no tile buffer at all.  The samples of a pair leave through a 4 KB per-wave staging area in OUTPUT
     // order - lane = cell writes its four 16-byte pieces [sample][coordinates 0-3 | 4-7] with ds_write_b128, four adjacent lanes read
     // back the 64 contiguous bytes of ONE cell and store them (16 cells x 64 B per store instruction): 4 + 4 LDS instructions per pair
     // instead of 8 writes + 16 gathered 4-byte reads, and eight waves per CU where the tile buffer allows seven (K = 16, K = 9).
     // (Where the tile buffer already admits eight waves - K = 10, 12: 60-cell tiles - this form measured 0-5 % SLOWER, same box;
-    // the host picks it only when it adds a wave: fwd4_plan.)  Piece j of cell c lies at position
+    // the host picks it only when it adds a wave: fwd_plan.)  Piece j of cell c lies at position
     // j ^ ((c >> 1) & 3) of the cell's 64 bytes: every 8-lane group of both the writes and the reads covers all 32 banks.
     constexpr bool PST = PST_;
-    constexpr bool PST2 = PST && ST != 0 && (ST & 3) == 2 && VMP_FWD_PAIR_STAGE2;       // two pairs per flush (S / 2 odd), below
+    constexpr bool PST2 = PST && ST != 0 && (ST & 3) == 2;       // two pairs per flush (S / 2 odd), below
     // OIMG (in-kernel noise, L = 8, compile-time even S, tile-buffer form): the LDS image of the tile is written in OUTPUT order
     // [cell][s][l] - four ds_write_b128 per sample pair (the pair-staging form's pieces; conflict-free at the padded cell stride:
     // eight consecutive cells start at eight different 16-byte slots of the 128-byte bank window) - and leaves by ds_read_b128 +
@@ -1000,7 +979,7 @@ __global__ __launch_bounds__((RNG ? 8 : 4) * WAVE) void svae_estep_fwd4_kernel(E
 #pragma unroll
                 for (int w = 0; w < QSc; ++w)
                     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(g + dma_off[w]),
-                                                     (__attribute__((address_space(3))) void*)(buf + w * (4 * WAVE)), 16, 0, (VMP_T2_NT & 2) ? 2 : 0);
+                                                     (__attribute__((address_space(3))) void*)(buf + w * (4 * WAVE)), 16, 0, FWD4_NOISE_DMA_AUX);
                 return;
             }
         }
@@ -1011,7 +990,7 @@ __global__ __launch_bounds__((RNG ? 8 : 4) * WAVE) void svae_estep_fwd4_kernel(E
             const float* src = g + (long long)cc * LSn + 4 * ss;
             if (c < BC)                                     // slots past the buffer's last cell (BC < 64) are not written
                 __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                                 (__attribute__((address_space(3))) void*)(buf + w * (4 * WAVE)), 16, 0, (VMP_T2_NT & 2) ? 2 : 0);
+                                                 (__attribute__((address_space(3))) void*)(buf + w * (4 * WAVE)), 16, 0, FWD4_NOISE_DMA_AUX);
             c += dcs; sl += drs;
             if (sl >= QS) { sl -= QS; c += 1; }
         }
@@ -1389,7 +1368,7 @@ __global__ __launch_bounds__((RNG ? 8 : 4) * WAVE) void svae_estep_fwd4_kernel(E
 #pragma unroll
                 for (int it = 0; it < 4; ++it) {
                     const int cc = 16 * it + (lane >> 2);
-                    if (cc < ncell_t && pok && !(VMP_PST_NOSTORE)) {
+                    if (cc < ncell_t && pok) {
                         const unsigned ob = (unsigned)(cc * LSn + 4 * pc) * 4u;
                         if (a.vec_ok) {
                             asm volatile("global_store_dwordx4 %0, %1, %2" :: "v"(ob), "v"(ov[it]), "s"(gs) : "memory");
@@ -1493,7 +1472,7 @@ __global__ __launch_bounds__((RNG ? 8 : 4) * WAVE) void svae_estep_fwd4_kernel(E
                         }
 #pragma unroll
                         for (int u = 0; u < CB; ++u)
-                            if (it0 + u < Qc && (it0 + u) * WAVE + lane < nf4) st_x4<!RNG && (VMP_T2_NT & 1) != 0>(g4 + (it0 + u) * WAVE, v[u]);
+                            if (it0 + u < Qc && (it0 + u) * WAVE + lane < nf4) st_x4<!RNG>(g4 + (it0 + u) * WAVE, v[u]);
                     }
                 } else {
                     int c2 = o_first, rem = orem_first;
@@ -1511,7 +1490,7 @@ __global__ __launch_bounds__((RNG ? 8 : 4) * WAVE) void svae_estep_fwd4_kernel(E
                         }
 #pragma unroll
                         for (int u = 0; u < CB; ++u)
-                            if (it0 + u < Q && (it0 + u) * WAVE + lane < nf4) st_x4<!RNG && (VMP_T2_NT & 1) != 0>(g4 + (it0 + u) * WAVE, v[u]);
+                            if (it0 + u < Q && (it0 + u) * WAVE + lane < nf4) st_x4<!RNG>(g4 + (it0 + u) * WAVE, v[u]);
                     }
                 }
             }
@@ -1550,9 +1529,6 @@ __global__ __launch_bounds__((RNG ? 8 : 4) * WAVE) void svae_estep_fwd4_kernel(E
 // and the epilogue outputs (its pair holds sample 0, the one subsample_x keeps).  Same stream, same per-sample arithmetic as the
 // streaming forms (x bit-identical); T' differs from theirs in the last bits (partial sums per pair instead of one running sum).
 // ---------------------------------------------------------------------------------------------------------
-#ifndef VMP_FWD1
-#define VMP_FWD1 1                  // 0: A/B builds without the minibatch form
-#endif
 constexpr int FWD1_MAX_PAIRS = 8;        // block = S / 2 waves (S <= 16; 256 registers per lane)
 constexpr int FWD1_MAX_TILES = 256;      // beyond that the streaming forms take over (one block per CU is then no longer latency-bound)
 template <int L>
@@ -1939,15 +1915,6 @@ int check_sv(long long N, int K, int L, int S) {
 #ifdef VMP_DEBUG_TS
 static long long* g_dbg_svae = nullptr;
 #endif
-// Small latent dimensions (C1 / C2: L = 2) leave most of a SIMD's registers and of the CU's LDS idle at one block per CU, and their
-// tiles are short dependent chains: several blocks per CU (round 6; the big-L geometries stay as tuned).  Per-lane registers by L
-// (tools/kreg.py): forward 77 / 95 (L = 2 / 3), generic backward 71 / 95.
-inline int fwd4_blocks_per_cu(int L, size_t lds_block) {
-    const int by_regs = L <= 2 ? 3 : L == 3 ? 2 : 1;                 // 8-wave blocks: 6 / 4 / 2 waves per SIMD
-    const int by_lds = lds_block ? (int)(lds_budget() / lds_block) : 1;
-    const int b = by_regs < by_lds ? by_regs : by_lds;
-    return b < 1 ? 1 : b;
-}
 inline int sv_blocks_l(long long N, int K, int L) {
     const int RPT = WAVE / K;
     const long long ntiles = (N + RPT - 1) / RPT;
@@ -1959,6 +1926,7 @@ inline int sv_blocks_l(long long N, int K, int L) {
 }
 
 int sv_blocks(long long N, int K) {
+    if (N <= 0 || K < 1 || K > WAVE) return 0;
     const int RPT = WAVE / K;
     const long long ntiles = (N + RPT - 1) / RPT;
     long long b = (ntiles + SV_NW - 1) / SV_NW;
@@ -1971,26 +1939,189 @@ int sv_blocks(long long N, int K) {
 
 bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
-#define VMP_DISPATCH_L(Lv, CALL)           \
+#define VMP_DISPATCH_L(Lv, ...)            \
     switch (Lv) {                           \
-        case 1: { constexpr int LL = 1; CALL; } break; \
-        case 2: { constexpr int LL = 2; CALL; } break; \
-        case 3: { constexpr int LL = 3; CALL; } break; \
-        case 4: { constexpr int LL = 4; CALL; } break; \
-        case 5: { constexpr int LL = 5; CALL; } break; \
-        case 6: { constexpr int LL = 6; CALL; } break; \
-        case 7: { constexpr int LL = 7; CALL; } break; \
-        case 8: { constexpr int LL = 8; CALL; } break; \
+        case 1: { constexpr int LL = 1; __VA_ARGS__; } break; \
+        case 2: { constexpr int LL = 2; __VA_ARGS__; } break; \
+        case 3: { constexpr int LL = 3; __VA_ARGS__; } break; \
+        case 4: { constexpr int LL = 4; __VA_ARGS__; } break; \
+        case 5: { constexpr int LL = 5; __VA_ARGS__; } break; \
+        case 6: { constexpr int LL = 6; __VA_ARGS__; } break; \
+        case 7: { constexpr int LL = 7; __VA_ARGS__; } break; \
+        case 8: { constexpr int LL = 8; __VA_ARGS__; } break; \
         default: break;                     \
     }
 
-#ifndef VMP_BWD1
-#define VMP_BWD1 1                  // 0: A/B builds without the minibatch form of the backward kernel
-#endif
+// ---- launch plans.  Which kernel a shape runs, with what block, grid and LDS, is decided in two pure functions: fwd_plan and
+// bwd_plan.  Every launch and every size query of the ABI goes through them, so a buffer sized from a query and the launch that fills
+// it cannot disagree.
+inline long long sv_tiles(long long N, int K) { const int RPT = WAVE / K; return (N + RPT - 1) / RPT; }   // tiles of WAVE / K whole rows
+
+enum class FwdForm { none, fwd1, tile, pst, pst2, chunked, fwd3 };
+// none:    no in-kernel-noise form for the shape (or no in-kernel moments)
+// fwd1:    svae_estep_fwd1_kernel - minibatch sizes, in-kernel noise: one block per tile, one wave per sample pair
+// tile:    svae_estep_fwd4_kernel<L, ST, RNG>       - per-wave LDS tile buffers (two with a noise tensor, one with in-kernel noise)
+// pst:     svae_estep_fwd4_kernel<8, ST, true, true> - in-kernel noise, L = 8: per-pair staging, no S-sized buffer
+// pst2:    the same at S = 10: two pairs per flush, whole-line stores
+// chunked: svae_estep_fwd_chunked_kernel - noise tensor whose cell block does not fit the LDS tile: SC samples at a time
+// fwd3:    svae_estep_fwd3_kernel - noise tensor, register-staged: L*S not a multiple of 4, or a misaligned noise tensor
+struct FwdPlan {
+    FwdForm form = FwdForm::none;
+    int nw = 0;             // waves per block
+    int grid = 0;           // blocks
+    size_t lds = 0;         // dynamic LDS bytes
+    int cs = 0;             // tile / pst forms: the cell stride CS of the LDS tile; chunked: samples per chunk SC
+};
+constexpr int FWD4_MOM_RED_WORDS = 768;      // per wave: the block reduction of the in-kernel moments runs in the waves' staging areas
+
+// words of the fwd4 kernel's LDS tables: lower triangles of P_k ([K][TRI | 1], whole 16-byte pieces); the pair-staging forms add
+// [K][FWD4_HKS] of h_k | bias_k | kappa_k and the (cos, sin) table of the generator's directions
+inline size_t fwd4_table_bytes(int K, int L, bool pair_staging) {
+    return (size_t)(((K * ((L * (L + 1) / 2) | 1) + 3) & ~3) + (pair_staging ? K * FWD4_HKS + SCT_WORDS : 0)) * sizeof(float);
+}
+inline int waves_in(size_t budget, size_t table, size_t per_wave, int max_waves) {
+    const int nw = budget > table ? (int)((budget - table) / per_wave) : 0;
+    return nw > max_waves ? max_waves : nw;
+}
+// Small latent dimensions (C1 / C2: L = 2) leave most of a SIMD's registers and of the CU's LDS idle at one block per CU, and their
+// tiles are short dependent chains: several blocks per CU (round 6; the big-L geometries stay as tuned).  Per-lane registers by L
+// (tools/kreg.py): forward 77 / 95 (L = 2 / 3), generic backward 71 / 95.
+inline int fwd4_blocks_per_cu(int L, size_t lds_block) {
+    const int by_regs = L <= 2 ? 3 : L == 3 ? 2 : 1;                 // 8-wave blocks: 6 / 4 / 2 waves per SIMD
+    const int by_lds = lds_block ? (int)(lds_budget() / lds_block) : 1;
+    const int b = by_regs < by_lds ? by_regs : by_lds;
+    return b < 1 ? 1 : b;
+}
+
+// rng: in-kernel noise (else a noise tensor, noise_al16 = its 16-byte alignment); mom: in-kernel M-step moments wanted;
+// fwd1_ok: the minibatch form may be used (the _at entry points walk a set in chunks and must not: its T' sums in another order)
+FwdPlan fwd_plan(long long N, int K, int L, int S, bool rng, bool noise_al16, bool mom, bool fwd1_ok) {
+    FwdPlan p;
+    const long long ntiles = sv_tiles(N, K);
+    const size_t budget = lds_budget();
+    auto blocks = [&](int nw, long long cap) { const long long b = (ntiles + nw - 1) / nw; return (int)(b > cap ? cap : b); };
+    // a cell's noise / sample block inside a per-wave LDS tile
+    const bool tile_fits = (size_t)(L * S | 1) * WAVE * sizeof(float) <= 36 * 1024;
+    if (rng) {
+        if (mom && !(K == 16 && L == 8)) return p;                 // in-kernel moments: K = 16, L = 8 ...
+        if (ntiles <= FWD1_MAX_TILES && (S + 1) / 2 <= FWD1_MAX_PAIRS) {
+            if (mom) return p;                                     // ... and not at minibatch sizes: the minibatch form has none
+            if (fwd1_ok) { p.form = FwdForm::fwd1; p.nw = (S + 1) / 2; p.grid = (int)ntiles; return p; }
+        }
+    } else if (!tile_fits) {
+        // the cell's noise block does not fit the LDS tile: process the samples SC at a time
+        p.form = FwdForm::chunked;
+        p.cs = (32 * 1024 / (int)(WAVE * sizeof(float))) / L;      // L*SC*64*4 B <= 32 KiB per wave
+        p.nw = 4;
+        p.lds = (size_t)(WAVE * ((L * p.cs) | 1) + WAVE) * sizeof(float) * p.nw;
+        p.grid = blocks(p.nw, 1024);
+        return p;
+    }
+    // ---- the fwd4 forms.  Tile buffer: whole 16-byte pieces per cell, cell stride CS = L*S rounded so that CS/4 is odd; BC = the
+    // tile's (64 / K) K cells per buffer; the noise-tensor form double-buffers (the row-reduction scratch lies in the idle buffer)
+    const int CS = L * S + ((((L * S) >> 2) & 1) ? 0 : 4);
+    const int max_nw = rng ? 8 : 4;
+    size_t table = fwd4_table_bytes(K, L, false);
+    size_t per_wave = (size_t)((rng ? 1 : 2) * (WAVE / K) * K * CS) * sizeof(float);
+    p.form = FwdForm::tile;
+    p.nw = ((L * S) % 4 == 0 && tile_fits && (rng || noise_al16)) ? waves_in(budget, table, per_wave, max_nw) : 0;
+    if (rng && L == 8) {
+        // S = 10 (the compiled-in sample count): the two-pair staging form, eight waves, whole-line stores - where the tile buffer
+        // admits fewer than eight waves (K = 16, 7, 8, 9)
+        const bool pst2 = S == 10 && p.nw < 8;
+        if (p.nw < FWD4_PST_BELOW_WAVES || pst2) {
+            // in-kernel noise, and the tile buffer admits few waves or does not fit at all (large S: evaluation runs use S = 100,
+            // experiments.py:283): the per-pair staging form (PST), which has no S-sized buffer.  (Round 4 also chose it where the tile
+            // buffer admits seven waves - K = 16, 7, 8, 9 at S = 10.  With round 5's cheaper generator the ONE-pair form is bound by its
+            // 64-byte segment stores: same box, K = 16 1.78 -> 1.52 ms, K = 8 1.04 -> 0.90, K = 7 0.91 -> 0.84 with the seven-wave tile buffer.)
+            p.form = pst2 ? FwdForm::pst2 : FwdForm::pst;
+            table = fwd4_table_bytes(K, L, true);
+            per_wave = (size_t)(pst2 ? 2 * (WAVE * 16 + 16) : WAVE * 16) * sizeof(float);
+            p.nw = waves_in(budget, table, per_wave, max_nw);
+        }
+    }
+    if (p.nw >= 1) {
+        p.cs = CS;
+        p.lds = table + per_wave * p.nw;
+        if (mom) {
+            // the waves' drawn-sample records ([4 rows][XSEL]) in front of the staging areas; the block reduction needs its floor
+            if (p.form == FwdForm::tile) return FwdPlan{};
+            p.lds += (size_t)p.nw * 4 * XSEL * sizeof(float);
+            if (p.lds > budget || p.lds < table + (size_t)p.nw * FWD4_MOM_RED_WORDS * sizeof(float)) return FwdPlan{};
+        }
+        // one block per CU, more for small L (in-kernel moments: L = 8, one)
+        p.grid = blocks(p.nw, 256ll * fwd4_blocks_per_cu(L, p.lds));
+        return p;
+    }
+    if (rng) return FwdPlan{};
+    // ---- register-staged kernel: one block per CU, as many waves as 160 KiB of LDS hold
+    table = (size_t)K * ((L * (L + 1) / 2) | 1) * sizeof(float);
+    per_wave = (size_t)(WAVE * (L * S | 1) + WAVE) * sizeof(float);
+    p.form = FwdForm::fwd3;
+    p.nw = waves_in(budget - 10 * 1024, table, per_wave, SV_FWD_MAX_NW);
+    if (p.nw < 1) p.nw = 1;
+    p.lds = table + per_wave * p.nw;
+    p.grid = blocks(p.nw, 256);
+    return p;
+}
+
+// ---- forward: one launcher per kernel template, run_fwd switches on the plan's form
+template <int L, int ST, bool RNG, bool PS>
+int launch_fwd4(const EFwdArgs& a, const FwdPlan& p, void* stream) {
+    auto kern = svae_estep_fwd4_kernel<L, ST, RNG, PS>;
+    if (const int rc = set_dyn_lds(reinterpret_cast<const void*>(kern), p.lds, "svae_estep_fwd")) return rc;
+    hipLaunchKernelGGL(kern, dim3(p.grid), dim3(p.nw * WAVE), p.lds, static_cast<hipStream_t>(stream), a, p.cs);
+    return check_launch(RNG ? "svae_estep_fwd4_kernel<rng>" : "svae_estep_fwd4_kernel");
+}
+template <int L, int ST>
+int launch_fwd3(const EFwdArgs& a, const FwdPlan& p, void* stream) {
+    auto kern = svae_estep_fwd3_kernel<L, ST>;
+    if (p.lds > 64 * 1024)
+        if (const int rc = set_dyn_lds(reinterpret_cast<const void*>(kern), p.lds, "svae_estep_fwd")) return rc;
+    hipLaunchKernelGGL(kern, dim3(p.grid), dim3(p.nw * WAVE), p.lds, static_cast<hipStream_t>(stream), a);
+    return check_launch("svae_estep_fwd3_kernel");
+}
+
 constexpr int BWD1_MAX_PAIRS = 8, BWD1_MAX_TILES = 256;         // (kernel: vmp_svae_mini.hip)
-bool bwd1_applies(int64_t N, int K, int L, int S, bool student) {
-    const long long nt = (N + WAVE / K - 1) / (WAVE / K);
-    return VMP_BWD1 && !student && nt <= BWD1_MAX_TILES && (S + 1) / 2 <= BWD1_MAX_PAIRS;
+// Envelope of the minibatch form of the backward kernel (svae_estep_bwd1_kernel): <= 256 tiles, S <= 16.  with_tail: the form with the
+// ELBO's scalar tail inside (the direct step; Gaussian or Student-t theta).  Without it - the autograd path, vmp_svae_estep_bwd_n -
+// Student-t theta keeps the generic / ring kernels.
+bool bwd1_covers(long long N, int K, int L, int S, bool student, bool with_tail) {
+    if (N <= 0 || K < 1 || K > WAVE) return false;
+    if (with_tail ? (L < 1 || L > VMP_MAX_D || S < 1) : student) return false;
+    return sv_tiles(N, K) <= BWD1_MAX_TILES && (S + 1) / 2 <= BWD1_MAX_PAIRS;
+}
+
+enum class BwdForm { none, bwd1, ring, generic_one, generic_stream };
+// bwd1:           svae_estep_bwd1_kernel (vmp_svae_mini.hip): one block per tile, one wave per sample pair
+// ring:           svae_estep_bwd_ring_kernel (vmp_svae_ring.h): one block per CU, its own grid of at most 256 blocks; rows of the
+//                 partial buffer beyond its grid are zeroed by the kernel
+// generic_one:    svae_estep_bwd_kernel<L, true>:  every wave has at most one tile (latency form)
+// generic_stream: svae_estep_bwd_kernel<L, false>
+struct BwdPlan {
+    BwdForm form = BwdForm::none;
+    int blocks = 0;         // rows of the partial buffer (= the grid, except for the ring form)
+};
+// nblk: the rows of the caller's partial buffer - vmp_svae_bwd_blocks_for (what nblk = 0 asks for) or vmp_svae_bwd_blocks
+BwdPlan bwd_plan(long long N, int K, int L, int S, bool student, bool vec_ok, int nblk) {
+    BwdPlan p;
+    if (N <= 0 || K < 1 || K > WAVE) return p;
+    const long long ntiles = sv_tiles(N, K);
+    if (bwd1_covers(N, K, L, S, student, false) && (nblk == 0 || nblk == ntiles)) {
+        p.form = BwdForm::bwd1;
+        p.blocks = (int)ntiles;
+        return p;
+    }
+    const int wide = sv_blocks_l(N, K, L);                  // L <= 3 (generic kernel): more blocks per CU; otherwise = sv_blocks
+    if (nblk == 0) nblk = wide;
+    if (nblk != wide && nblk != sv_blocks(N, K)) return p;
+    p.blocks = nblk;
+    const bool one = ntiles <= (long long)nblk * SV_NW;     // every wave has at most one tile
+    // LDS-ring kernels: quad-coalesced LDS-DMA of sample pairs, two pairs in flight per wave, Gaussian or Student-t theta.  Batches of
+    // one tile per wave with K != 16 keep the generic kernel's latency form (tuned at the reference's minibatch size).
+    if ((K == 16 || !one) && svae_bwd_ring_covers(K, L, S, student, vec_ok)) p.form = BwdForm::ring;
+    else p.form = one ? BwdForm::generic_one : BwdForm::generic_stream;
+    return p;
 }
 
 }  // namespace
@@ -2009,191 +2140,84 @@ size_t vmp_svae_workspace_bytes(int64_t N, int K, int L) {
 
 int vmp_svae_bwd_blocks(int64_t N, int K) { return sv_blocks(N, K); }
 
-// LDS-DMA / in-kernel-noise forward kernel: launch geometry, or 0 waves when the shape is not covered
-static int fwd4_plan(int K, int L, int S, int& CS, size_t& lds4, bool rng = false, bool* pair_stage = nullptr) {
-    if (pair_stage) *pair_stage = false;
-    CS = L * S;
-    if (((CS >> 2) & 1) == 0) CS += 4;
-    size_t table = (size_t)((K * ((L * (L + 1) / 2) | 1) + 3) & ~3) * sizeof(float);
-    const int BC = VMP_FWD_BC_TILE ? (WAVE / K) * K : WAVE;      // cells per tile buffer (the kernel's BC)
-    size_t pw = (size_t)((rng ? 1 : 2) * BC * CS) * sizeof(float);
-    // the tile-buffer forms: whole 16-byte pieces per cell, and a cell's noise block inside the per-wave LDS tile
-    const bool fits = (L * S) % 4 == 0 && (size_t)(L * S | 1) * WAVE * sizeof(float) <= 36 * 1024;
-    const size_t budget = lds_budget();
-    int nw4 = (fits && budget > table) ? (int)((budget - table) / pw) : 0;
-    if (nw4 > (rng ? 8 : 4)) nw4 = rng ? 8 : 4;
-    // S = 10 (the compiled-in sample count): the two-pair staging form, eight waves, whole-line stores - where the tile buffer
-    // admits fewer than eight waves (K = 16, 7, 8, 9)
-    const bool pst2 = VMP_FWD_PAIR_STAGE2 && S == 10 && (nw4 < 8 || VMP_FWD_PST2_ALWAYS);
-    if (rng && L == 8 && VMP_FWD_PAIR_STAGE && (nw4 < VMP_FWD_PAIR_STAGE_BELOW || pst2) && pair_stage) {
-        // in-kernel noise, and the tile buffer admits few waves or does not fit at all (large S: evaluation runs use S = 100,
-        // experiments.py:283): the per-pair staging form (PST), which has no S-sized buffer.  (Round 4 also chose it where the tile
-        // buffer admits seven waves - K = 16, 7, 8, 9 at S = 10.  With round 5's cheaper generator the ONE-pair form is bound by its
-        // 64-byte segment stores: same box, K = 16 1.78 -> 1.52 ms, K = 8 1.04 -> 0.90, K = 7 0.91 -> 0.84 with the seven-wave tile buffer.)
-        *pair_stage = true;
-        table += (size_t)K * 12 * sizeof(float);             // the kernel's [K][HKS] table of h_k | bias_k | kappa_k
-        if (VMP_FWD_SINCOS_TAB) table += (size_t)SCT_WORDS * sizeof(float);   // and its (cos, sin) table of the generator's directions
-        pw = (size_t)(pst2 ? 2 * (WAVE * 16 + 16) : WAVE * 16) * sizeof(float);
-        nw4 = budget > table ? (int)((budget - table) / pw) : 0;
-        if (nw4 > 8) nw4 = 8;
-    }
-    if (nw4 < 1) return 0;
-    lds4 = table + pw * nw4;
-    return nw4;
-}
-
 static int run_fwd(EFwdArgs a, int L, void* stream, bool rng, bool fwd1_ok = true) {
 #ifdef VMP_DEBUG_TS
     a.dbg_t = g_dbg_svae;
 #endif
-    const long long N = a.N;
-    const int K = a.K, S = a.S;
-    const float* noise = a.noise;
-    int rc;
-    if (rng) {
-        int CS = 0;
-        size_t lds4 = 0;
-        bool ps = false;
-        {   // minibatch sizes: one block per tile, one wave per sample pair (svae_estep_fwd1_kernel)
-            const long long nt1 = (N + WAVE / K - 1) / (WAVE / K);
-            const int P = (S + 1) / 2;
-            if (VMP_FWD1 && fwd1_ok && !a.mom && nt1 <= FWD1_MAX_TILES && P <= FWD1_MAX_PAIRS) {
-                rc = -1;
-                VMP_DISPATCH_L(L, {
-                    hipLaunchKernelGGL((svae_estep_fwd1_kernel<LL>), dim3((int)nt1), dim3(P * WAVE), 0, static_cast<hipStream_t>(stream), a);
-                    rc = check_launch("svae_estep_fwd1_kernel");
-                });
-                return rc;
-            }
-        }
-        const int nw4 = fwd4_plan(K, L, S, CS, lds4, true, &ps);
-        if (nw4 < 1) { set_error("in-kernel noise covers L = 8, and L < 8 with L*S %% 4 == 0 tiles that fit the LDS (L=%d, S=%d)", L, S); return VMP_E_DIM; }
-        const int RPT4 = WAVE / K;
-        long long bl = ((N + RPT4 - 1) / RPT4 + nw4 - 1) / nw4;
-        const long long blcap = 256ll * fwd4_blocks_per_cu(L, lds4);
-        if (bl > blcap) bl = blcap;
-        if (a.mom) {
-            if (!(ps && K == 16 && L == 8)) { set_error("in-kernel moments cover K = 16, L = 8 (vmp_svae_fwd_mom_blocks)"); return VMP_E_DIM; }
-            lds4 += (size_t)nw4 * 4 * XSEL * sizeof(float);          // the waves' drawn-sample records
-            if (lds4 < (size_t)(((K * ((L * (L + 1) / 2) | 1) + 3) & ~3) + K * 12 + (VMP_FWD_SINCOS_TAB ? SCT_WORDS : 0)) * sizeof(float) + (size_t)nw4 * 768 * sizeof(float)) {
-                set_error("in-kernel moments: staging area smaller than the block reduction");
-                return VMP_E_WS;
-            }
-        }
-        rc = -1;
-        VMP_DISPATCH_L(L, {
-            if (LL == 8 && ps) {
-                if (S == 10) {
-                    if ((rc = set_dyn_lds(reinterpret_cast<const void*>(svae_estep_fwd4_kernel<8, 10, true, true>), lds4, "svae_estep_fwd")) != 0) return rc;
-                    hipLaunchKernelGGL((svae_estep_fwd4_kernel<8, 10, true, true>), dim3((int)bl), dim3(nw4 * WAVE), lds4, static_cast<hipStream_t>(stream), a, CS);
-                } else {
-                    if ((rc = set_dyn_lds(reinterpret_cast<const void*>(svae_estep_fwd4_kernel<8, 0, true, true>), lds4, "svae_estep_fwd")) != 0) return rc;
-                    hipLaunchKernelGGL((svae_estep_fwd4_kernel<8, 0, true, true>), dim3((int)bl), dim3(nw4 * WAVE), lds4, static_cast<hipStream_t>(stream), a, CS);
-                }
-            } else if (S == 10) {
-                if ((rc = set_dyn_lds(reinterpret_cast<const void*>(svae_estep_fwd4_kernel<LL, 10, true>), lds4, "svae_estep_fwd")) != 0) return rc;
-                hipLaunchKernelGGL((svae_estep_fwd4_kernel<LL, 10, true>), dim3((int)bl), dim3(nw4 * WAVE), lds4, static_cast<hipStream_t>(stream), a, CS);
-            } else {
-                if ((rc = set_dyn_lds(reinterpret_cast<const void*>(svae_estep_fwd4_kernel<LL, 0, true>), lds4, "svae_estep_fwd")) != 0) return rc;
-                hipLaunchKernelGGL((svae_estep_fwd4_kernel<LL, 0, true>), dim3((int)bl), dim3(nw4 * WAVE), lds4, static_cast<hipStream_t>(stream), a, CS);
-            }
-            rc = check_launch("svae_estep_fwd4_kernel<rng>");
-        });
-        return rc;
-    }
-    if ((size_t)(L * S | 1) * WAVE * sizeof(float) > 36 * 1024) {
-        // the cell's noise block does not fit the LDS tile: process the samples SC at a time
-        int SC = (32 * 1024 / (int)(WAVE * sizeof(float))) / L;   // L*SC*64*4 B <= 32 KiB per wave
-        const size_t pw = (size_t)(WAVE * ((L * SC) | 1) + WAVE) * sizeof(float);
-        const int nwc = 4;
-        const int RPTc = WAVE / K;
-        long long bl = ((N + RPTc - 1) / RPTc + nwc - 1) / nwc;
-        if (bl > 1024) bl = 1024;
-        rc = -1;
-        VMP_DISPATCH_L(L, {
-            if ((rc = set_dyn_lds(reinterpret_cast<const void*>(svae_estep_fwd_chunked_kernel<LL>), (pw * nwc), "svae_estep_fwd")) != 0) return rc;
-            hipLaunchKernelGGL((svae_estep_fwd_chunked_kernel<LL>), dim3((int)bl), dim3(nwc * WAVE), pw * nwc, static_cast<hipStream_t>(stream), a, SC);
-            rc = check_launch("svae_estep_fwd_chunked_kernel");
-        });
-        return rc;
-    }
-    if ((L * S) % 4 == 0 && al16(noise)) {
-        // LDS-DMA kernel: cell stride CS = L*S rounded so that CS/4 is odd
-        int CS = L * S;
-        if (((CS >> 2) & 1) == 0) CS += 4;
-        const size_t table = (size_t)((K * ((L * (L + 1) / 2) | 1) + 3) & ~3) * sizeof(float);
-        const int BC = VMP_FWD_BC_TILE ? (WAVE / K) * K : WAVE;   // cells per tile buffer (the kernel's BC)
-        const size_t pw = (size_t)(2 * BC * CS) * sizeof(float);      // (the row-reduction scratch lies in the idle buffer)
-        const size_t budget = lds_budget();
-        int nw4 = budget > table ? (int)((budget - table) / pw) : 0;
-        if (nw4 > 4) nw4 = 4;
-        if (nw4 >= 1) {
-            const size_t lds4 = table + pw * nw4;
-            const int RPT4 = WAVE / K;
-            long long bl = ((N + RPT4 - 1) / RPT4 + nw4 - 1) / nw4;
-            const long long blcap = 256ll * fwd4_blocks_per_cu(L, lds4);
-            if (bl > blcap) bl = blcap;
-            rc = -1;
+    const FwdPlan p = fwd_plan(a.N, a.K, L, a.S, rng, al16(a.noise), a.mom != nullptr, fwd1_ok);
+    const bool s10 = a.S == 10;                             // the compiled-in sample count (ST = 10; ST = 0: S at run time)
+    int rc = -1;
+    switch (p.form) {
+        case FwdForm::none:
+            if (a.mom) set_error("in-kernel moments cover K = 16, L = 8 beyond the minibatch form (vmp_svae_fwd_mom_blocks)");
+            else set_error("in-kernel noise covers L = 8, and L < 8 with L*S %% 4 == 0 tiles that fit the LDS (L=%d, S=%d)", L, a.S);
+            return VMP_E_DIM;
+        case FwdForm::fwd1:
             VMP_DISPATCH_L(L, {
-                if (S == 10) {
-                    if ((rc = set_dyn_lds(reinterpret_cast<const void*>(svae_estep_fwd4_kernel<LL, 10, false>), lds4, "svae_estep_fwd")) != 0) return rc;
-                    hipLaunchKernelGGL((svae_estep_fwd4_kernel<LL, 10, false>), dim3((int)bl), dim3(nw4 * WAVE), lds4, static_cast<hipStream_t>(stream), a, CS);
-                } else {
-                    if ((rc = set_dyn_lds(reinterpret_cast<const void*>(svae_estep_fwd4_kernel<LL, 0, false>), lds4, "svae_estep_fwd")) != 0) return rc;
-                    hipLaunchKernelGGL((svae_estep_fwd4_kernel<LL, 0, false>), dim3((int)bl), dim3(nw4 * WAVE), lds4, static_cast<hipStream_t>(stream), a, CS);
-                }
-                rc = check_launch("svae_estep_fwd4_kernel");
+                hipLaunchKernelGGL((svae_estep_fwd1_kernel<LL>), dim3(p.grid), dim3(p.nw * WAVE), 0, static_cast<hipStream_t>(stream), a);
+                rc = check_launch("svae_estep_fwd1_kernel");
             });
             return rc;
-        }
+        case FwdForm::pst:
+        case FwdForm::pst2:
+            return s10 ? launch_fwd4<8, 10, true, true>(a, p, stream) : launch_fwd4<8, 0, true, true>(a, p, stream);
+        case FwdForm::tile:
+            if (rng) { VMP_DISPATCH_L(L, rc = s10 ? launch_fwd4<LL, 10, true, false>(a, p, stream) : launch_fwd4<LL, 0, true, false>(a, p, stream)); }
+            else { VMP_DISPATCH_L(L, rc = s10 ? launch_fwd4<LL, 10, false, false>(a, p, stream) : launch_fwd4<LL, 0, false, false>(a, p, stream)); }
+            return rc;
+        case FwdForm::chunked:
+            VMP_DISPATCH_L(L, {
+                if ((rc = set_dyn_lds(reinterpret_cast<const void*>(svae_estep_fwd_chunked_kernel<LL>), p.lds, "svae_estep_fwd")) != 0) return rc;
+                hipLaunchKernelGGL((svae_estep_fwd_chunked_kernel<LL>), dim3(p.grid), dim3(p.nw * WAVE), p.lds, static_cast<hipStream_t>(stream), a, p.cs);
+                rc = check_launch("svae_estep_fwd_chunked_kernel");
+            });
+            return rc;
+        case FwdForm::fwd3:
+            VMP_DISPATCH_L(L, rc = s10 ? launch_fwd3<LL, 10>(a, p, stream) : launch_fwd3<LL, 0>(a, p, stream));
+            return rc;
     }
-    {   // register-staged kernel: L*S not a multiple of 4, or a misaligned noise tensor
-        const size_t table = (size_t)K * ((L * (L + 1) / 2) | 1) * sizeof(float);
-        const size_t pw = (size_t)(WAVE * (L * S | 1) + WAVE) * sizeof(float);
-        const size_t budget3 = lds_budget() - 10 * 1024;
-        int nw3 = budget3 > table ? (int)((budget3 - table) / pw) : 0;        // one block per CU, as many waves as 160 KiB of LDS hold
-        if (nw3 > SV_FWD_MAX_NW) nw3 = SV_FWD_MAX_NW;
-        if (nw3 < 1) nw3 = 1;
-        const size_t lds3 = table + pw * nw3;
-        const int RPT3 = WAVE / K;
-        long long bl = ((N + RPT3 - 1) / RPT3 + nw3 - 1) / nw3;
-        if (bl > 256) bl = 256;
-        rc = -1;
-        VMP_DISPATCH_L(L, {
-            if (S == 10) {
-                if (lds3 > 64 * 1024)
-                    if ((rc = set_dyn_lds(reinterpret_cast<const void*>(svae_estep_fwd3_kernel<LL, 10>), lds3, "svae_estep_fwd")) != 0) return rc;
-                hipLaunchKernelGGL((svae_estep_fwd3_kernel<LL, 10>), dim3((int)bl), dim3(nw3 * WAVE), lds3, static_cast<hipStream_t>(stream), a);
-            } else {
-                if (lds3 > 64 * 1024)
-                    if ((rc = set_dyn_lds(reinterpret_cast<const void*>(svae_estep_fwd3_kernel<LL, 0>), lds3, "svae_estep_fwd")) != 0) return rc;
-                hipLaunchKernelGGL((svae_estep_fwd3_kernel<LL, 0>), dim3((int)bl), dim3(nw3 * WAVE), lds3, static_cast<hipStream_t>(stream), a);
-            }
-            rc = check_launch("svae_estep_fwd3_kernel");
-        });
-        return rc;
+    return rc;
+}
+
+// a streaming in-kernel-noise form exists for (K, L, S), whatever N
+int vmp_svae_rng_in_kernel(int K, int L, int S) {
+    return (K >= 1 && K <= WAVE && L >= 1 && L <= VMP_MAX_D && fwd_plan(1, K, L, S, true, true, false, false).form != FwdForm::none) ? 1 : 0;
+}
+
+// blocks of the forward launch that writes in-kernel moments = rows (x 16 x 48 fp64) of the caller's moment buffer; 0: none
+int vmp_svae_fwd_mom_blocks(int64_t N, int K, int L, int S) {
+    if (N <= 0 || K < 1 || K > WAVE || L < 1 || L > VMP_MAX_D || S < 1) return 0;
+    return fwd_plan(N, K, L, S, true, true, true, true).grid;
+}
+
+// Prologue of the forward entry points: sizes, the pointers all of them need (`extra_ok`: the entry point's own), and the arguments
+// of the kernels with the in-kernel-noise fields left off.
+static int fwd_begin(const char* who, const float* eta1, const float* eta2d, const float* hk, const float* Pk, const float* bias,
+                     const float* mk, const float* Wk, const float* kappa, const float* nu, int64_t N, int K, int L, int S, float* x,
+                     float* lz, float* Tp, bool extra_ok, EFwdArgs& a) {
+    const int rc = check_sv(N, K, L, S);
+    if (rc) return rc;
+    if (!eta1 || !eta2d || !hk || !Pk || !bias || !mk || !Wk || !kappa || !x || !lz || !Tp || !extra_ok) {
+        set_error("%s: null pointer", who);
+        return VMP_E_BADARG;
     }
+    a = EFwdArgs{eta1, eta2d, hk, Pk, bias, nullptr, mk, Wk, kappa, nu, x, lz, Tp, N, K, S, al16(x), 0ull};
+    return 0;
+}
+static int fwd_need_in_kernel(const char* who, int K, int L, int S) {
+    if (vmp_svae_rng_in_kernel(K, L, S)) return 0;
+    set_error("%s: K=%d L=%d S=%d is outside the in-kernel generator's shapes (vmp_svae_rng_in_kernel)", who, K, L, S);
+    return VMP_E_DIM;
 }
 
 int vmp_svae_estep_fwd(const float* eta1, const float* eta2d, const float* hk, const float* Pk, const float* bias,
                        const float* noise, const float* mk, const float* Wk, const float* kappa, const float* nu,
                        int64_t N, int K, int L, int S, float* x, float* lz, float* Tp, void* stream) {
-    int rc = check_sv(N, K, L, S);
-    if (rc) return rc;
-    if (!eta1 || !eta2d || !hk || !Pk || !bias || !noise || !mk || !Wk || !kappa || !x || !lz || !Tp) {
-        set_error("vmp_svae_estep_fwd: null pointer");
-        return VMP_E_BADARG;
-    }
-    EFwdArgs a{eta1, eta2d, hk, Pk, bias, noise, mk, Wk, kappa, nu, x, lz, Tp, N, K, S, 0, 0ull};
+    EFwdArgs a;
+    if (const int rc = fwd_begin("vmp_svae_estep_fwd", eta1, eta2d, hk, Pk, bias, mk, Wk, kappa, nu, N, K, L, S, x, lz, Tp, noise != nullptr, a)) return rc;
+    a.noise = noise;
     a.vec_ok = al16(noise) && al16(x);
     return run_fwd(a, L, stream, false);
-}
-
-int vmp_svae_rng_in_kernel(int K, int L, int S) {
-    int CS = 0;
-    size_t lds4 = 0;
-    bool ps = false;
-    return (K >= 1 && K <= 64 && L >= 1 && L <= 8 && fwd4_plan(K, L, S, CS, lds4, true, &ps) >= 1) ? 1 : 0;
 }
 
 static int philox_noise_impl(uint64_t seed, const uint64_t* seed_dev, int64_t N, int K, int L, int S, float* noise, void* stream,
@@ -2220,30 +2244,28 @@ int vmp_svae_philox_noise_dev(const uint64_t* seed_dev, int64_t N, int K, int L,
     return philox_noise_impl(0, seed_dev, N, K, L, S, noise, stream);
 }
 
-int vmp_svae_estep_fwd_rng(const float* eta1, const float* eta2d, const float* hk, const float* Pk, const float* bias,
-                           uint64_t seed, const float* mk, const float* Wk, const float* kappa, const float* nu,
-                           int64_t N, int K, int L, int S, float* x, float* lz, float* Tp, float* noise_ws, void* stream) {
-    int rc = check_sv(N, K, L, S);
-    if (rc) return rc;
-    if (!eta1 || !eta2d || !hk || !Pk || !bias || !mk || !Wk || !kappa || !x || !lz || !Tp) {
-        set_error("vmp_svae_estep_fwd_rng: null pointer");
-        return VMP_E_BADARG;
-    }
-    EFwdArgs a{eta1, eta2d, hk, Pk, bias, nullptr, mk, Wk, kappa, nu, x, lz, Tp, N, K, S, 0, (unsigned long long)seed};
-    if (vmp_svae_rng_in_kernel(K, L, S)) {
-        a.vec_ok = al16(x);
-        return run_fwd(a, L, stream, true);
-    }
-    if (!noise_ws) { set_error("vmp_svae_estep_fwd_rng: this shape needs the (N,K,L,S) noise workspace"); return VMP_E_WS; }
-    rc = vmp_svae_philox_noise(seed, N, K, L, S, noise_ws, stream);
-    if (rc) return rc;
+int vmp_svae_philox_noise_at(uint64_t seed, int64_t row0, int64_t N, int K, int L, int S, float* noise, void* stream) {
+    return philox_noise_impl(seed, nullptr, N, K, L, S, noise, stream, row0);
+}
+
+// Host seed: the in-kernel generator where a streaming form exists; otherwise the same stream is drawn into the caller's noise
+// workspace and the noise-tensor form runs on it.
+static int run_fwd_seeded(const char* who, EFwdArgs a, int L, float* noise_ws, bool fwd1_ok, void* stream) {
+    if (vmp_svae_rng_in_kernel(a.K, L, a.S)) return run_fwd(a, L, stream, true, fwd1_ok);
+    if (!noise_ws) { set_error("%s: this shape needs the (N,K,L,S) noise workspace", who); return VMP_E_WS; }
+    if (const int rc = philox_noise_impl(a.seed, nullptr, a.N, a.K, L, a.S, noise_ws, stream, a.row0)) return rc;
     a.noise = noise_ws;
-    a.vec_ok = al16(noise_ws) && al16(x);
+    a.vec_ok = al16(noise_ws) && al16(a.x);
     return run_fwd(a, L, stream, false);
 }
 
-int vmp_svae_philox_noise_at(uint64_t seed, int64_t row0, int64_t N, int K, int L, int S, float* noise, void* stream) {
-    return philox_noise_impl(seed, nullptr, N, K, L, S, noise, stream, row0);
+int vmp_svae_estep_fwd_rng(const float* eta1, const float* eta2d, const float* hk, const float* Pk, const float* bias,
+                           uint64_t seed, const float* mk, const float* Wk, const float* kappa, const float* nu,
+                           int64_t N, int K, int L, int S, float* x, float* lz, float* Tp, float* noise_ws, void* stream) {
+    EFwdArgs a;
+    if (const int rc = fwd_begin("vmp_svae_estep_fwd_rng", eta1, eta2d, hk, Pk, bias, mk, Wk, kappa, nu, N, K, L, S, x, lz, Tp, true, a)) return rc;
+    a.seed = (unsigned long long)seed;
+    return run_fwd_seeded("vmp_svae_estep_fwd_rng", a, L, noise_ws, true, stream);
 }
 
 // Forward only, no epilogue, always the streaming kernels (never svae_estep_fwd1_kernel, whose T' sums its per-pair partial sums in
@@ -2251,83 +2273,39 @@ int vmp_svae_philox_noise_at(uint64_t seed, int64_t row0, int64_t N, int K, int 
 int vmp_svae_estep_fwd_rng_at(const float* eta1, const float* eta2d, const float* hk, const float* Pk, const float* bias,
                               uint64_t seed, int64_t row0, const float* mk, const float* Wk, const float* kappa, const float* nu,
                               int64_t N, int K, int L, int S, float* x, float* lz, float* Tp, float* noise_ws, void* stream) {
-    int rc = check_sv(N, K, L, S);
-    if (rc) return rc;
-    if (!eta1 || !eta2d || !hk || !Pk || !bias || !mk || !Wk || !kappa || !x || !lz || !Tp) {
-        set_error("vmp_svae_estep_fwd_rng_at: null pointer");
-        return VMP_E_BADARG;
-    }
+    EFwdArgs a;
+    if (const int rc = fwd_begin("vmp_svae_estep_fwd_rng_at", eta1, eta2d, hk, Pk, bias, mk, Wk, kappa, nu, N, K, L, S, x, lz, Tp, true, a)) return rc;
     if (row0 < 0) { set_error("vmp_svae_estep_fwd_rng_at: row0 < 0"); return VMP_E_BADARG; }
-    EFwdArgs a{eta1, eta2d, hk, Pk, bias, nullptr, mk, Wk, kappa, nu, x, lz, Tp, N, K, S, 0, (unsigned long long)seed};
+    a.seed = (unsigned long long)seed;
     a.row0 = (long long)row0;
-    if (vmp_svae_rng_in_kernel(K, L, S)) {
-        a.vec_ok = al16(x);
-        return run_fwd(a, L, stream, true, false);
-    }
-    if (!noise_ws) { set_error("vmp_svae_estep_fwd_rng_at: this shape needs the (N,K,L,S) noise workspace"); return VMP_E_WS; }
-    rc = vmp_svae_philox_noise_at(seed, row0, N, K, L, S, noise_ws, stream);
-    if (rc) return rc;
-    a.noise = noise_ws;
-    a.vec_ok = al16(noise_ws) && al16(x);
-    return run_fwd(a, L, stream, false);
+    return run_fwd_seeded("vmp_svae_estep_fwd_rng_at", a, L, noise_ws, false, stream);
 }
 
 int vmp_svae_estep_fwd_rng_dev(const float* eta1, const float* eta2d, const float* hk, const float* Pk, const float* bias,
                                const uint64_t* seed_dev, const float* mk, const float* Wk, const float* kappa, const float* nu,
                                int64_t N, int K, int L, int S, float* x, float* lz, float* Tp, void* stream) {
-    int rc = check_sv(N, K, L, S);
-    if (rc) return rc;
-    if (!eta1 || !eta2d || !hk || !Pk || !bias || !seed_dev || !mk || !Wk || !kappa || !x || !lz || !Tp) {
-        set_error("vmp_svae_estep_fwd_rng_dev: null pointer");
-        return VMP_E_BADARG;
-    }
-    if (!vmp_svae_rng_in_kernel(K, L, S)) {
-        set_error("vmp_svae_estep_fwd_rng_dev: K=%d L=%d S=%d is outside the in-kernel generator's shapes (vmp_svae_rng_in_kernel)", K, L, S);
-        return VMP_E_DIM;
-    }
-    EFwdArgs a{eta1, eta2d, hk, Pk, bias, nullptr, mk, Wk, kappa, nu, x, lz, Tp, N, K, S, 0, 0ull,
-               reinterpret_cast<const unsigned long long*>(seed_dev)};
-    a.vec_ok = al16(x);
+    EFwdArgs a;
+    if (int rc = fwd_begin("vmp_svae_estep_fwd_rng_dev", eta1, eta2d, hk, Pk, bias, mk, Wk, kappa, nu, N, K, L, S, x, lz, Tp, seed_dev != nullptr, a)) return rc;
+    if (int rc = fwd_need_in_kernel("vmp_svae_estep_fwd_rng_dev", K, L, S)) return rc;
+    a.seed_dev = reinterpret_cast<const unsigned long long*>(seed_dev);
     return run_fwd(a, L, stream, true);
-}
-
-int vmp_svae_fwd_mom_blocks(int64_t N, int K, int L, int S) {
-    int CS = 0;
-    size_t lds4 = 0;
-    bool ps = false;
-    if (N <= 0 || K != 16 || L != 8) return 0;
-    if (VMP_FWD1 && (N + 3) / 4 <= FWD1_MAX_TILES && (S + 1) / 2 <= FWD1_MAX_PAIRS) return 0;   // minibatch form (svae_estep_fwd1_kernel): no in-kernel moments
-    const int nw4 = fwd4_plan(K, L, S, CS, lds4, true, &ps);
-    if (nw4 < 1 || !ps) return 0;
-    if (lds4 + (size_t)nw4 * 4 * XSEL * sizeof(float) > lds_budget()) return 0;
-    const int RPT4 = WAVE / K;
-    long long bl = ((N + RPT4 - 1) / RPT4 + nw4 - 1) / nw4;
-    if (bl > 256) bl = 256;
-    return (int)bl;
 }
 
 int vmp_svae_estep_fwd_rng_epi(const float* eta1, const float* eta2d, const float* hk, const float* Pk, const float* bias,
                                uint64_t seed, const uint64_t* seed_dev, const float* mk, const float* Wk, const float* kappa,
                                const float* nu, int64_t N, int K, int L, int S, float* x, float* lz, float* Tp,
                                float* x_samples, float* r, double* mom, size_t mom_bytes, void* stream) {
-    int rc = check_sv(N, K, L, S);
-    if (rc) return rc;
-    if (!eta1 || !eta2d || !hk || !Pk || !bias || !mk || !Wk || !kappa || !x || !lz || !Tp || !x_samples) {
-        set_error("vmp_svae_estep_fwd_rng_epi: null pointer");
-        return VMP_E_BADARG;
-    }
-    if (!vmp_svae_rng_in_kernel(K, L, S)) {
-        set_error("vmp_svae_estep_fwd_rng_epi: K=%d L=%d S=%d is outside the in-kernel generator's shapes (vmp_svae_rng_in_kernel)", K, L, S);
-        return VMP_E_DIM;
-    }
+    EFwdArgs a;
+    if (int rc = fwd_begin("vmp_svae_estep_fwd_rng_epi", eta1, eta2d, hk, Pk, bias, mk, Wk, kappa, nu, N, K, L, S, x, lz, Tp, x_samples != nullptr, a)) return rc;
+    if (int rc = fwd_need_in_kernel("vmp_svae_estep_fwd_rng_epi", K, L, S)) return rc;
     if (mom) {
         const int nb = vmp_svae_fwd_mom_blocks(N, K, L, S);
         if (nb < 1) { set_error("vmp_svae_estep_fwd_rng_epi: no in-kernel moments for K=%d L=%d S=%d (vmp_svae_fwd_mom_blocks)", K, L, S); return VMP_E_DIM; }
         if (mom_bytes < (size_t)nb * 16 * MOMF * sizeof(double)) { set_error("vmp_svae_estep_fwd_rng_epi: moment buffer too small"); return VMP_E_WS; }
     }
-    EFwdArgs a{eta1, eta2d, hk, Pk, bias, nullptr, mk, Wk, kappa, nu, x, lz, Tp, N, K, S, 0, (unsigned long long)seed,
-               reinterpret_cast<const unsigned long long*>(seed_dev), x_samples, r, mom};
-    a.vec_ok = al16(x);
+    a.seed = (unsigned long long)seed;
+    a.seed_dev = reinterpret_cast<const unsigned long long*>(seed_dev);
+    a.xs = x_samples; a.r = r; a.mom = mom;
     return run_fwd(a, L, stream, true);
 }
 
@@ -2336,45 +2314,47 @@ int vmp_svae_estep_fwd_rng_epi(const float* eta1, const float* eta2d, const floa
 // of vmp_decoder_elbo) + vmp_svae_estep_bwd_n: dLoss/dlog_z, dLoss/dT' never reach memory.  Outputs as vmp_svae_estep_bwd_n
 // (partials: one row per tile = vmp_svae_bwd_blocks_for) plus r = exp(log_z) (N,K) and tail_part (tiles, 2) fp64 - the per-tile
 // terms of [sum w A, sum r (T' + log z)], summed by vmp_svae_step_final.
-int vmp_svae_bwd_tail_applies(int64_t N, int K, int L, int S) {
-    return N > 0 && K >= 1 && K <= WAVE && L >= 1 && L <= 8 && S >= 1 && bwd1_applies(N, K, L, S, false) ? 1 : 0;
+// The SMM-SVAE's minibatch step (_t): the same with Student-t theta (svae_estep_bwd1_kernel<L, true, true>) and the same envelope
+// (<= 256 tiles, S <= 16): the kernel's per-pair theta sums take a second round through the LDS area of the first, so the block's
+// LDS is the Gaussian form's.  (vmp_svae_bwd_blocks_for(..., student = 1) and vmp_svae_estep_bwd_n keep their generic-kernel answer:
+// the autograd SMM step is unchanged.)
+int vmp_svae_bwd_tail_applies(int64_t N, int K, int L, int S) { return bwd1_covers(N, K, L, S, false, true) ? 1 : 0; }
+int vmp_svae_bwd_tail_applies_t(int64_t N, int K, int L, int S) { return bwd1_covers(N, K, L, S, true, true) ? 1 : 0; }
+
+static int bwd_tail_impl(const char* who, bool student, const float* eta1, const float* eta2d, const float* hk, const float* Pk,
+                         const float* bias, const float* mk, const float* Wk, const float* nu, const float* x, const float* lz,
+                         const float* T_prime, const float* ll, float sigma, const float* Gx, int64_t N, int K, int L, int S,
+                         float* g_eta1, float* g_eta2d, float* partials, size_t partial_bytes, float* r, double* tail_part,
+                         size_t tail_bytes, void* stream) {
+    int rc = check_sv(N, K, L, S);
+    if (rc) return rc;
+    if (!eta1 || !eta2d || !hk || !Pk || !bias || !mk || !Wk || (student && !nu) || !x || !lz || !T_prime || !ll || !Gx || !g_eta1 ||
+        !g_eta2d || !partials || !r || !tail_part || sigma == 0.f) {
+        set_error("%s: null pointer or sigma == 0", who);
+        return VMP_E_BADARG;
+    }
+    if (!bwd1_covers(N, K, L, S, student, true)) {
+        set_error("%s: N=%lld K=%d L=%d S=%d outside the minibatch form (<= %d tiles, S <= %d)", who, (long long)N, K, L, S,
+                  BWD1_MAX_TILES, 2 * BWD1_MAX_PAIRS);
+        return VMP_E_DIM;
+    }
+    const int nt = (int)sv_tiles(N, K);
+    const int PW = vmp_svae_bwd_partial_words(L);
+    if (partial_bytes < (size_t)nt * K * PW * sizeof(float) || tail_bytes < (size_t)nt * 2 * sizeof(double)) {
+        set_error("%s: partials / tail_part buffer too small for %d tiles", who, nt);
+        return VMP_E_WS;
+    }
+    EBwdArgs a{eta1, eta2d, hk, Pk, bias, mk, Wk, student ? nu : nullptr, x, lz, Gx, nullptr, nullptr, g_eta1, g_eta2d, partials, N, K, S, 0};
+    a.Tp = T_prime; a.ll = ll; a.r_out = r; a.tail_part = tail_part; a.sigma = sigma;
+    return svae_bwd1_launch(a, L, nt, (S + 1) / 2, true, student, stream);
 }
 
 int vmp_svae_estep_bwd_tail(const float* eta1, const float* eta2d, const float* hk, const float* Pk, const float* bias,
                             const float* mk, const float* Wk, const float* x, const float* lz, const float* T_prime, const float* ll,
                             float sigma, const float* Gx, int64_t N, int K, int L, int S, float* g_eta1, float* g_eta2d,
                             float* partials, size_t partial_bytes, float* r, double* tail_part, size_t tail_bytes, void* stream) {
-    int rc = check_sv(N, K, L, S);
-    if (rc) return rc;
-    if (!eta1 || !eta2d || !hk || !Pk || !bias || !mk || !Wk || !x || !lz || !T_prime || !ll || !Gx || !g_eta1 || !g_eta2d || !partials ||
-        !r || !tail_part || sigma == 0.f) {
-        set_error("vmp_svae_estep_bwd_tail: null pointer or sigma == 0");
-        return VMP_E_BADARG;
-    }
-    if (!vmp_svae_bwd_tail_applies(N, K, L, S)) {
-        set_error("vmp_svae_estep_bwd_tail: N=%lld K=%d L=%d S=%d outside the minibatch form (<= %d tiles, S <= %d)", (long long)N, K, L, S,
-                  BWD1_MAX_TILES, 2 * BWD1_MAX_PAIRS);
-        return VMP_E_DIM;
-    }
-    const int nt = (int)((N + WAVE / K - 1) / (WAVE / K));
-    const int PW = vmp_svae_bwd_partial_words(L);
-    if (partial_bytes < (size_t)nt * K * PW * sizeof(float) || tail_bytes < (size_t)nt * 2 * sizeof(double)) {
-        set_error("vmp_svae_estep_bwd_tail: partials / tail_part buffer too small for %d tiles", nt);
-        return VMP_E_WS;
-    }
-    EBwdArgs a{eta1, eta2d, hk, Pk, bias, mk, Wk, nullptr, x, lz, Gx, nullptr, nullptr, g_eta1, g_eta2d, partials, N, K, S, 0};
-    a.Tp = T_prime; a.ll = ll; a.r_out = r; a.tail_part = tail_part; a.sigma = sigma;
-    return svae_bwd1_launch(a, L, nt, (S + 1) / 2, true, stream);
-}
-
-// ---- the SMM-SVAE's minibatch step: vmp_svae_estep_bwd_tail with Student-t theta (svae_estep_bwd1_kernel<L, true, true>).  The same
-// envelope as the Gaussian form (<= 256 tiles, S <= 16): the kernel's per-pair theta sums take a second round through the LDS area of
-// the first, so the block's LDS is the Gaussian form's.  (vmp_svae_bwd_blocks_for(..., student = 1) and vmp_svae_estep_bwd_n keep
-// their generic-kernel answer: the autograd SMM step is unchanged.)
-int vmp_svae_bwd_tail_applies_t(int64_t N, int K, int L, int S) {
-    if (!(N > 0 && K >= 1 && K <= WAVE && L >= 1 && L <= 8 && S >= 1)) return 0;
-    const long long nt = (N + WAVE / K - 1) / (WAVE / K);
-    return VMP_BWD1 && nt <= BWD1_MAX_TILES && (S + 1) / 2 <= BWD1_MAX_PAIRS ? 1 : 0;
+    return bwd_tail_impl("vmp_svae_estep_bwd_tail", false, eta1, eta2d, hk, Pk, bias, mk, Wk, nullptr, x, lz, T_prime, ll, sigma, Gx, N, K,
+                         L, S, g_eta1, g_eta2d, partials, partial_bytes, r, tail_part, tail_bytes, stream);
 }
 
 int vmp_svae_estep_bwd_tail_t(const float* eta1, const float* eta2d, const float* hk, const float* Pk, const float* bias,
@@ -2382,34 +2362,12 @@ int vmp_svae_estep_bwd_tail_t(const float* eta1, const float* eta2d, const float
                               const float* ll, float sigma, const float* Gx, int64_t N, int K, int L, int S, float* g_eta1,
                               float* g_eta2d, float* partials, size_t partial_bytes, float* r, double* tail_part, size_t tail_bytes,
                               void* stream) {
-    int rc = check_sv(N, K, L, S);
-    if (rc) return rc;
-    if (!eta1 || !eta2d || !hk || !Pk || !bias || !mk || !Wk || !nu || !x || !lz || !T_prime || !ll || !Gx || !g_eta1 || !g_eta2d ||
-        !partials || !r || !tail_part || sigma == 0.f) {
-        set_error("vmp_svae_estep_bwd_tail_t: null pointer or sigma == 0");
-        return VMP_E_BADARG;
-    }
-    if (!vmp_svae_bwd_tail_applies_t(N, K, L, S)) {
-        set_error("vmp_svae_estep_bwd_tail_t: N=%lld K=%d L=%d S=%d outside the minibatch form (<= %d tiles, S <= %d)", (long long)N, K, L,
-                  S, BWD1_MAX_TILES, 2 * BWD1_MAX_PAIRS);
-        return VMP_E_DIM;
-    }
-    const int nt = (int)((N + WAVE / K - 1) / (WAVE / K));
-    const int PW = vmp_svae_bwd_partial_words(L);
-    if (partial_bytes < (size_t)nt * K * PW * sizeof(float) || tail_bytes < (size_t)nt * 2 * sizeof(double)) {
-        set_error("vmp_svae_estep_bwd_tail_t: partials / tail_part buffer too small for %d tiles", nt);
-        return VMP_E_WS;
-    }
-    EBwdArgs a{eta1, eta2d, hk, Pk, bias, mk, Wk, nu, x, lz, Gx, nullptr, nullptr, g_eta1, g_eta2d, partials, N, K, S, 0};
-    a.Tp = T_prime; a.ll = ll; a.r_out = r; a.tail_part = tail_part; a.sigma = sigma;
-    return svae_bwd1_t_launch(a, L, nt, (S + 1) / 2, stream);
+    return bwd_tail_impl("vmp_svae_estep_bwd_tail_t", true, eta1, eta2d, hk, Pk, bias, mk, Wk, nu, x, lz, T_prime, ll, sigma, Gx, N, K, L,
+                         S, g_eta1, g_eta2d, partials, partial_bytes, r, tail_part, tail_bytes, stream);
 }
 
-int vmp_svae_bwd_blocks_for(int64_t N, int K, int L, int S, int student) {
-    if (N <= 0 || K < 1 || K > WAVE) return 0;
-    if (bwd1_applies(N, K, L, S, student != 0)) return (int)((N + WAVE / K - 1) / (WAVE / K));
-    return sv_blocks_l(N, K, L);                              // L <= 3 (generic kernel): more blocks per CU; otherwise vmp_svae_bwd_blocks
-}
+// rows of the partial buffer the backward pass prefers for the shape (one per tile at minibatch sizes)
+int vmp_svae_bwd_blocks_for(int64_t N, int K, int L, int S, int student) { return bwd_plan(N, K, L, S, student != 0, true, 0).blocks; }
 
 int vmp_svae_estep_bwd_n(const float* eta1, const float* eta2d, const float* hk, const float* Pk, const float* bias,
                          const float* mk, const float* Wk, const float* nu, const float* x, const float* lz, const float* Gx,
@@ -2421,47 +2379,27 @@ int vmp_svae_estep_bwd_n(const float* eta1, const float* eta2d, const float* hk,
         set_error("vmp_svae_estep_bwd: null pointer");
         return VMP_E_BADARG;
     }
-    const int blocks = sv_blocks(N, K);
-    const int PW = vmp_svae_bwd_partial_words(L);
-    const bool use1 = bwd1_applies(N, K, L, S, nu != nullptr) && nblk == vmp_svae_bwd_blocks_for(N, K, L, S, nu != nullptr);
-    const bool wide = !use1 && L <= 3 && nblk == sv_blocks_l(N, K, L);        // small L: the generic kernel on more blocks per CU
-    if (!use1 && !wide && nblk != blocks) {
-        set_error("vmp_svae_estep_bwd_n: nblk = %d is neither vmp_svae_bwd_blocks_for (%d) nor vmp_svae_bwd_blocks (%d)", nblk,
-                  vmp_svae_bwd_blocks_for(N, K, L, S, nu != nullptr), blocks);
-        return VMP_E_BADARG;
-    }
-    if (partial_bytes < (size_t)nblk * K * PW * sizeof(float)) { set_error("vmp_svae_estep_bwd: partials buffer too small"); return VMP_E_WS; }
     EBwdArgs a{eta1, eta2d, hk, Pk, bias, mk, Wk, nu, x, lz, Gx, Glz, GT, g_eta1, g_eta2d, partials, N, K, S, 0};
     a.vec_ok = al16(x) && al16(Gx);
 #ifdef VMP_DEBUG_TS
     a.dbg_t = g_dbg_svae;
 #endif
-#ifndef VMP_T2_RING
-#define VMP_T2_RING 1         // 0: build without the LDS-ring backward kernel (A/B measurements: tools/build_variant.sh)
-#endif
-    const long long ntiles_g = (N + WAVE / K - 1) / (WAVE / K);
-    if (use1) {
-        // minibatch sizes, Gaussian theta: one block per tile, one wave per sample pair (svae_estep_bwd1_kernel)
-        const int P = (S + 1) / 2;
-        rc = -1;
-        rc = svae_bwd1_launch(a, L, (int)ntiles_g, P, false, stream);
-        return rc;
+    const BwdPlan p = bwd_plan(N, K, L, S, nu != nullptr, a.vec_ok != 0, nblk > 0 ? nblk : -1);
+    if (p.form == BwdForm::none) {
+        set_error("vmp_svae_estep_bwd_n: nblk = %d is neither vmp_svae_bwd_blocks_for (%d) nor vmp_svae_bwd_blocks (%d)", nblk,
+                  vmp_svae_bwd_blocks_for(N, K, L, S, nu != nullptr), sv_blocks(N, K));
+        return VMP_E_BADARG;
     }
-    const int gblocks = wide ? nblk : blocks;
-    const bool one = ntiles_g <= (long long)gblocks * SV_NW;      // every wave has at most one tile: latency form
-    if (VMP_T2_RING && (K == 16 || !one)) {
-        // LDS-ring kernels (vmp_svae_ring.hip: quad-coalesced LDS-DMA of sample pairs, two pairs in flight per wave; 8 <= K <= 16,
-        // even L >= 4, even S >= 4, Gaussian or Student-t theta).  Batches of one tile per wave with K != 16 keep the generic
-        // kernel's latency form (tuned at the reference's minibatch size).
-        rc = svae_bwd_ring_launch(a, L, blocks, stream);
-        if (rc != -2) return rc;
-    }
+    const int PW = vmp_svae_bwd_partial_words(L);
+    if (partial_bytes < (size_t)nblk * K * PW * sizeof(float)) { set_error("vmp_svae_estep_bwd: partials buffer too small"); return VMP_E_WS; }
+    if (p.form == BwdForm::bwd1) return svae_bwd1_launch(a, L, p.blocks, (S + 1) / 2, false, false, stream);
+    if (p.form == BwdForm::ring) return svae_bwd_ring_launch(a, L, p.blocks, stream);
     const int PWa = nu ? PW : PW / 2;
     const size_t lds = (size_t)(K * ((L * (L + 1) / 2) | 1) + SV_NW * WAVE + SV_NW * 2 * L * SV_AST + SV_NW * PWa * SV_AST) * sizeof(float);
     rc = -1;
     VMP_DISPATCH_L(L, {
-        if (one) hipLaunchKernelGGL((svae_estep_bwd_kernel<LL, true>), dim3(gblocks), dim3(SV_NW * WAVE), lds, static_cast<hipStream_t>(stream), a);
-        else hipLaunchKernelGGL((svae_estep_bwd_kernel<LL, false>), dim3(gblocks), dim3(SV_NW * WAVE), lds, static_cast<hipStream_t>(stream), a);
+        if (p.form == BwdForm::generic_one) hipLaunchKernelGGL((svae_estep_bwd_kernel<LL, true>), dim3(p.blocks), dim3(SV_NW * WAVE), lds, static_cast<hipStream_t>(stream), a);
+        else hipLaunchKernelGGL((svae_estep_bwd_kernel<LL, false>), dim3(p.blocks), dim3(SV_NW * WAVE), lds, static_cast<hipStream_t>(stream), a);
         rc = check_launch("svae_estep_bwd_kernel");
     });
     return rc;
@@ -2472,7 +2410,7 @@ int vmp_svae_estep_bwd(const float* eta1, const float* eta2d, const float* hk, c
                        const float* Glz, const float* GT, int64_t N, int K, int L, int S, float* g_eta1, float* g_eta2d,
                        float* partials, size_t partial_bytes, void* stream) {
     return vmp_svae_estep_bwd_n(eta1, eta2d, hk, Pk, bias, mk, Wk, nu, x, lz, Gx, Glz, GT, N, K, L, S, g_eta1, g_eta2d, partials,
-                                partial_bytes, N > 0 && K >= 1 && K <= WAVE ? sv_blocks(N, K) : 0, stream);
+                                partial_bytes, sv_blocks(N, K), stream);
 }
 
 static int subsample_impl(const char* what, const float* x, const float* lz, const float* u, const int64_t* z, int rng, uint64_t seed,

@@ -143,10 +143,13 @@ template <int L> constexpr int svr_stage_floats() { return 2 * WAVE * 2 * L; }  
 }  // namespace
 
 namespace vmp {
-// LDS-ring backward (vmp_svae_ring.hip): returns -2 when the shape is not covered (the caller takes the generic kernel),
-// otherwise the launch status.  nblk_abi = number of partial rows the ABI sized the buffer for (rows the ring grid does not
-// write are zeroed by the kernel).
+// LDS-ring backward (vmp_svae_ring.hip).  svae_bwd_ring_covers: the shapes the ring kernels run - 8 <= K <= 16, even 4 <= L <= 8, even
+// S >= 4, 16-byte aligned x and dL/dx, and at least four waves' rings in the device's LDS; the backward plan (bwd_plan, vmp_svae.hip)
+// asks before it chooses the form.  nblk_abi = number of partial rows the ABI sized the buffer for (rows the ring grid does not write
+// are zeroed by the kernel).
+bool svae_bwd_ring_covers(int K, int L, int S, bool student, bool vec_ok);
 int svae_bwd_ring_launch(const EBwdArgs& a, int L, int nblk_abi, void* stream);
-int svae_bwd1_launch(const EBwdArgs& a, int L, int ntiles, int P, bool tail, void* stream);      // vmp_svae_mini.hip: one block per tile, one wave per sample pair
-int svae_bwd1_t_launch(const EBwdArgs& a, int L, int ntiles, int P, void* stream);                // the same with Student-t theta and the tail
+// vmp_svae_mini.hip: one block per tile, one wave per sample pair; tail: with the ELBO's scalar tail inside; student: Student-t theta
+// (compiled with the tail only)
+int svae_bwd1_launch(const EBwdArgs& a, int L, int ntiles, int P, bool tail, bool student, void* stream);
 }

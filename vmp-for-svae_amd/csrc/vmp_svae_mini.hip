@@ -352,21 +352,15 @@ int launch_bwd1(const EBwdArgs& a, int ntiles, int P, void* stream) {
 }  // namespace
 
 namespace vmp {
-int svae_bwd1_launch(const EBwdArgs& a, int L, int ntiles, int P, bool tail, void* stream) {
-#define BWD1_CASE(LL) case LL: return tail ? launch_bwd1<LL, true>(a, ntiles, P, stream) : launch_bwd1<LL, false>(a, ntiles, P, stream)
+int svae_bwd1_launch(const EBwdArgs& a, int L, int ntiles, int P, bool tail, bool student, void* stream) {
+    if (student && !tail) { set_error("svae_estep_bwd1_kernel: Student-t theta is compiled with the tail only"); return VMP_E_BADARG; }
+    // student: the theta half of every partial row is written
+#define BWD1_CASE(LL) case LL: return student ? launch_bwd1<LL, true, true>(a, ntiles, P, stream) \
+                                   : tail ? launch_bwd1<LL, true>(a, ntiles, P, stream) : launch_bwd1<LL, false>(a, ntiles, P, stream)
     switch (L) {
         BWD1_CASE(1); BWD1_CASE(2); BWD1_CASE(3); BWD1_CASE(4); BWD1_CASE(5); BWD1_CASE(6); BWD1_CASE(7); BWD1_CASE(8);
         default: return -1;
     }
 #undef BWD1_CASE
-}
-// Student-t theta, with the ELBO's scalar tail (vmp_svae_estep_bwd_tail_t): the theta half of every partial row is written
-int svae_bwd1_t_launch(const EBwdArgs& a, int L, int ntiles, int P, void* stream) {
-#define BWD1T_CASE(LL) case LL: return launch_bwd1<LL, true, true>(a, ntiles, P, stream)
-    switch (L) {
-        BWD1T_CASE(1); BWD1T_CASE(2); BWD1T_CASE(3); BWD1T_CASE(4); BWD1T_CASE(5); BWD1T_CASE(6); BWD1T_CASE(7); BWD1T_CASE(8);
-        default: return -1;
-    }
-#undef BWD1T_CASE
 }
 }  // namespace vmp

@@ -84,12 +84,9 @@ __device__ __forceinline__ void wait_vmcnt(int n) {
 //           requested four pairs ahead; no form is register-starved (the Student-t theta keeps W and all its sums in registers and
 //           runs the packed sample loop), and every memory operation inside the tile loop sits on a COUNTED wait: the tile's small
 //           inputs come by DMA one tile ahead, the row sums leave with one store per tile (see below).
-#ifndef VMP_RING_NT
-#define VMP_RING_NT 0        // A/B: 2 = the sample DMA carries nt
-#endif
-#ifndef VMP_RING_INPUTS_AHEAD
-#define VMP_RING_INPUTS_AHEAD 0   // A/B: 1 = the tile's small inputs are loaded one tile ahead into registers (round 5: no gain, see below)
-#endif
+// The sample DMA carries no nt bit: the two halves of a 128-byte line are asked for by different DMA instructions and the second must
+// hit in L2 (with nt the kernel measured 40 % slower).
+constexpr int RING_DMA_AUX = 0;
 #ifdef VMP_DEBUG_TS
 // exploration builds: clock64 stamps of ONE tile (the 9th of block 0, wave 0) - tools/ring_ts.py
 #define RG_TS(i) do { if (a.dbg_t && blockIdx.x == 0 && wave == 0 && tile_it == 8 && lane == 0) a.dbg_t[i] = clock64(); } while (0)
@@ -371,9 +368,9 @@ __global__ __launch_bounds__((NSTG == 2 ? SVR_NW : 4) * WAVE) void svae_estep_bw
                 if (rotate) { pe = (unsigned)pp + (cpar[j] ^ par0); pe = pe >= (unsigned)NP ? pe - (unsigned)NP : pe; }
                 const unsigned ob = cbyte[j] + pe * (unsigned)(2 * L * 4);
                 __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(xb + ob),
-                                                 (__attribute__((address_space(3))) void*)(stage + j * (4 * WAVE)), 16, 0, VMP_RING_NT);
+                                                 (__attribute__((address_space(3))) void*)(stage + j * (4 * WAVE)), 16, 0, RING_DMA_AUX);
                 __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(gb + ob),
-                                                 (__attribute__((address_space(3))) void*)(stage + WAVE * 2 * L + j * (4 * WAVE)), 16, 0, VMP_RING_NT);
+                                                 (__attribute__((address_space(3))) void*)(stage + WAVE * 2 * L + j * (4 * WAVE)), 16, 0, RING_DMA_AUX);
             }
             return;
         }
@@ -388,9 +385,9 @@ __global__ __launch_bounds__((NSTG == 2 ? SVR_NW : 4) * WAVE) void svae_estep_bw
             if (rotate) { pe = pp + ((cc + (int)par0) & 1); pe = pe >= NP ? pe - NP : pe; }
             const long long off = tile0 + (long long)cc * LSn + pe * 2 * L + 4 * dp;
             __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(a.x + off),
-                                             (__attribute__((address_space(3))) void*)(stage + j * (4 * WAVE)), 16, 0, VMP_RING_NT);
+                                             (__attribute__((address_space(3))) void*)(stage + j * (4 * WAVE)), 16, 0, RING_DMA_AUX);
             __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(a.Gx + off),
-                                             (__attribute__((address_space(3))) void*)(stage + WAVE * 2 * L + j * (4 * WAVE)), 16, 0, VMP_RING_NT);
+                                             (__attribute__((address_space(3))) void*)(stage + WAVE * 2 * L + j * (4 * WAVE)), 16, 0, RING_DMA_AUX);
         }
     };
 
@@ -434,28 +431,6 @@ __global__ __launch_bounds__((NSTG == 2 ? SVR_NW : 4) * WAVE) void svae_estep_bw
         const int younger = outst - 1;
         return younger * (2 * PP) + ((PF && p + younger >= NP) ? 5 : 0);
     };
-    // Round 5 (two-stage form): the small inputs of a tile - its RPT rows of eta1 / eta2d and the three (N, K) values of every cell -
-    // are loaded ONE TILE AHEAD into five registers per lane, right after the tile's last pair was re-requested: lane e holds element
-    // e of the tile's RPT L eta floats (coalesced), a lane's own row is read back with 2 L ds_bpermute.  Loaded at the top of the
-    // tile they cost an exposed memory round trip per tile behind the two stage requests already queued (vmcnt returns in order):
-    // the stage stamps put 2.3 k (K = 16) to 8.3 k (K = 10) cycles on "eta, P_k table, Cholesky, mean", of which ~2 k is arithmetic.
-    constexpr bool NX = VMP_RING_INPUTS_AHEAD && !PF;
-    float nx_e1 = 0.f, nx_e2 = -0.5f, nx_gT = 0.f, nx_glz = 0.f, nx_lz = 0.f;
-    auto load_inputs = [&](long long tt) {
-        if constexpr (NX) {
-            if (tt < ntiles) {
-                const long long rows_left = a.N - tt * RPT;
-                const int ne = (rows_left < RPT ? (int)rows_left : RPT) * L;
-                const long long e0 = tt * (long long)RPT * L;
-                const int le = lane < ne ? lane : ne - 1;                      // clamped: always a valid element
-                nx_e1 = a.eta1[e0 + le]; nx_e2 = a.eta2d[e0 + le];
-                const long long rw = tt * RPT + r;
-                const long long cid = (lane_on && rw < a.N ? rw : tt * RPT) * K + kc;
-                nx_gT = a.GT[cid]; nx_glz = a.Glz[cid]; nx_lz = a.lz[cid];
-            }
-        }
-    };
-    load_inputs(t);
     int tile_it = -1;
     for (; t < ntiles; t += tstride) {
         ++tile_it;
@@ -474,10 +449,7 @@ __global__ __launch_bounds__((NSTG == 2 ? SVR_NW : 4) * WAVE) void svae_estep_bw
         for (int i = 0; i < L; ++i) {
             float e1v, e2v;
             if constexpr (PF) { e1v = pfb[ro + i]; e2v = pfb[WAVE + ro + i]; }
-            else if constexpr (NX) {
-                e1v = __uint_as_float(__builtin_amdgcn_ds_bpermute(4 * (ro + i), __float_as_uint(nx_e1)));
-                e2v = __uint_as_float(__builtin_amdgcn_ds_bpermute(4 * (ro + i), __float_as_uint(nx_e2)));
-            } else { e1v = a.eta1[rowc * L + i]; e2v = a.eta2d[rowc * L + i]; }
+            else { e1v = a.eta1[rowc * L + i]; e2v = a.eta2d[rowc * L + i]; }
             const float e1 = on ? e1v : 0.f;
             const float e2 = on ? e2v : -0.5f;
             Lm[tri(i, i)] = fmaf(-2.f, e2, lane_on ? Lm[tri(i, i)] : 0.f);
@@ -486,7 +458,6 @@ __global__ __launch_bounds__((NSTG == 2 ? SVR_NW : 4) * WAVE) void svae_estep_bw
         }
         float glzv, gTv, lzv;
         if constexpr (PF) { const int pl = lane_on ? r * K + k : 0; gTv = pfb[2 * WAVE + pl]; glzv = pfb[3 * WAVE + pl]; lzv = pfb[4 * WAVE + pl]; }
-        else if constexpr (NX) { glzv = nx_glz; gTv = nx_gT; lzv = nx_lz; }
         else { glzv = a.Glz[cellid]; gTv = a.GT[cellid]; lzv = a.lz[cellid]; }
         float ld;
         cell_cholesky<L>(Lm, ld);
@@ -734,7 +705,6 @@ __global__ __launch_bounds__((NSTG == 2 ? SVR_NW : 4) * WAVE) void svae_estep_bw
             if constexpr (ST) { RG_USE(M[0]); } else { RG_USE(M2[0]); }
             RG_TS(6 + 4 * p);
         }
-        load_inputs(t + tstride);                            // (every value of this tile's inputs has been consumed above)
         auto MM = [&](int i, int j) -> float {               // i >= j
             if constexpr (ST) return M[tri(i, j)];
             else return M2[RO(i) + j / 2][j & 1];
@@ -931,32 +901,42 @@ __global__ __launch_bounds__((NSTG == 2 ? SVR_NW : 4) * WAVE) void svae_estep_bw
     }
 }
 
-template <int L, int KS, bool STUDENT, int NSTG>
-int launch_n(const EBwdArgs& a, int nblk_abi, void* stream) {
-    constexpr int TRI = L * (L + 1) / 2, TH = L + TRI + 1, PWa = STUDENT ? 2 * TH : TH;
-    const int K = a.K, RPT = WAVE / K;
-    const int tab = ((K * (TRI | 1) + 3) & ~3) + ((STUDENT && NSTG == 2) ? K * SvRingTab<L>::TST : 0);
-    const int per_wave = NSTG * svr_stage_floats<L>() + PWa * 16 + (NSTG == 4 ? 5 * WAVE : 0);
-    const int maxw = NSTG == 2 ? SVR_NW : 4;
+// LDS words of the shipped (two-stage) form: tables, and per wave the ring plus the per-component accumulators
+inline int svr_table_words(int K, int L, bool student) {
+    const int tst = L == 4 ? SvRingTab<4>::TST : L == 6 ? SvRingTab<6>::TST : SvRingTab<8>::TST;
+    return ((K * ((L * (L + 1) / 2) | 1) + 3) & ~3) + (student ? K * tst : 0);
+}
+inline int svr_wave_words(int L, bool student) {
+    const int TH = L + L * (L + 1) / 2 + 1;
+    return 2 * (2 * WAVE * 2 * L) + (student ? 2 * TH : TH) * 16;
+}
+// waves per block: as many as the device's LDS holds, at most SVR_NW (fewer than four: the shape is not covered)
+inline int svr_waves(int K, int L, bool student) {
     const size_t budget = vmp::lds_budget() / sizeof(float);
-    int nw = budget > (size_t)tab ? (int)((budget - tab) / per_wave) : 0;
-    if (nw > maxw) nw = maxw;
-    if (nw < 4) return -2;
-    const long long ntiles = (a.N + RPT - 1) / RPT;
-    long long bl = (ntiles + nw - 1) / nw;
-    if (bl > 256) bl = 256;                                  // one block per CU
-    const size_t lds = (size_t)(tab + nw * per_wave) * sizeof(float);
-    auto kern = svae_estep_bwd_ring_kernel<L, KS, STUDENT, NSTG>;
-    if (const int rc = vmp::set_dyn_lds(reinterpret_cast<const void*>(kern), lds, "svae_estep_bwd_ring_kernel")) return rc;
-    hipLaunchKernelGGL(kern, dim3((int)bl), dim3(nw * WAVE), lds, static_cast<hipStream_t>(stream), a, nblk_abi);
-    return check_launch("svae_estep_bwd_ring_kernel");
+    const int tab = svr_table_words(K, L, student);
+    const int nw = budget > (size_t)tab ? (int)((budget - tab) / svr_wave_words(L, student)) : 0;
+    return nw > SVR_NW ? SVR_NW : nw;
+}
+inline bool svr_covers(int K, int L, int S, bool student, bool vec_ok) {
+    return K >= 8 && K <= 16 && !(L & 1) && L >= 4 && L <= 8 && !(S & 1) && S >= 4 && vec_ok && svr_waves(K, L, student) >= 4;
 }
 
 // (The kernel template still carries NSTG: the four-stage, one-wave-per-SIMD form measured SLOWER in round 4 - profiles/NOTES_r01-r04.md -
 //  and is no longer instantiated or selectable; the shipped form is NSTG = 2: eight waves per CU, two stages each.)
 template <int L, int KS, bool STUDENT>
 int launch(const EBwdArgs& a, int nblk_abi, void* stream) {
-    return launch_n<L, KS, STUDENT, 2>(a, nblk_abi, stream);
+    static_assert(svr_stage_floats<L>() == 2 * WAVE * 2 * L, "svr_wave_words");
+    const int K = a.K, RPT = WAVE / K;
+    const int nw = svr_waves(K, L, STUDENT);
+    if (nw < 4) { set_error("svae_estep_bwd_ring_kernel: shape not covered (svae_bwd_ring_covers)"); return VMP_E_DIM; }
+    const long long ntiles = (a.N + RPT - 1) / RPT;
+    long long bl = (ntiles + nw - 1) / nw;
+    if (bl > 256) bl = 256;                                  // one block per CU
+    const size_t lds = (size_t)(svr_table_words(K, L, STUDENT) + nw * svr_wave_words(L, STUDENT)) * sizeof(float);
+    auto kern = svae_estep_bwd_ring_kernel<L, KS, STUDENT, 2>;
+    if (const int rc = vmp::set_dyn_lds(reinterpret_cast<const void*>(kern), lds, "svae_estep_bwd_ring_kernel")) return rc;
+    hipLaunchKernelGGL(kern, dim3((int)bl), dim3(nw * WAVE), lds, static_cast<hipStream_t>(stream), a, nblk_abi);
+    return check_launch("svae_estep_bwd_ring_kernel");
 }
 
 }  // namespace

@@ -7,8 +7,10 @@
 namespace vmp {
 int svae_bwd_ring_launch_t(const EBwdArgs& a, int L, int nblk_abi, void* stream);     // vmp_svae_ring_t.hip
 
+bool svae_bwd_ring_covers(int K, int L, int S, bool student, bool vec_ok) { return svr_covers(K, L, S, student, vec_ok); }
+
 int svae_bwd_ring_launch(const EBwdArgs& a, int L, int nblk_abi, void* stream) {
-    if (a.K < 8 || a.K > 16 || (L & 1) || L < 4 || L > 8 || (a.S & 1) || a.S < 4 || !a.vec_ok) return -2;
+    if (!svr_covers(a.K, L, a.S, a.nu != nullptr, a.vec_ok != 0)) { set_error("svae_estep_bwd_ring_kernel: shape not covered (svae_bwd_ring_covers)"); return VMP_E_DIM; }
     if (a.nu != nullptr) return svae_bwd_ring_launch_t(a, L, nblk_abi, stream);
     // K = 16 and the reference's K = 10 (experiments.py: nb_components of the Auto / pinwheel schedules) have their own instances
     // (compile-time lane maps); any other 8 <= K <= 15 runs the run-time-K form
@@ -17,7 +19,7 @@ int svae_bwd_ring_launch(const EBwdArgs& a, int L, int nblk_abi, void* stream) {
         case 4: return ks == 16 ? launch<4, 16, false>(a, nblk_abi, stream) : launch<4, 0, false>(a, nblk_abi, stream);
         case 6: return ks == 16 ? launch<6, 16, false>(a, nblk_abi, stream) : launch<6, 0, false>(a, nblk_abi, stream);
         case 8: return ks == 16 ? launch<8, 16, false>(a, nblk_abi, stream) : ks == 10 ? launch<8, 10, false>(a, nblk_abi, stream) : launch<8, 0, false>(a, nblk_abi, stream);
-        default: return -2;
+        default: return VMP_E_DIM;
     }
 }
 }  // namespace vmp

@@ -11,7 +11,7 @@ int svae_bwd_ring_launch_t(const EBwdArgs& a, int L, int nblk_abi, void* stream)
         case 4: return ks == 16 ? launch<4, 16, true>(a, nblk_abi, stream) : launch<4, 0, true>(a, nblk_abi, stream);
         case 6: return ks == 16 ? launch<6, 16, true>(a, nblk_abi, stream) : launch<6, 0, true>(a, nblk_abi, stream);
         case 8: return ks == 16 ? launch<8, 16, true>(a, nblk_abi, stream) : ks == 10 ? launch<8, 10, true>(a, nblk_abi, stream) : launch<8, 0, true>(a, nblk_abi, stream);
-        default: return -2;
+        default: return VMP_E_DIM;
     }
 }
 }  // namespace vmp

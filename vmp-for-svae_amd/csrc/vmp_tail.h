@@ -47,10 +47,7 @@ __device__ __forceinline__ void tail_cell(const float lz, const float tp, const 
 __device__ __forceinline__ void elbo_tail_body(const TailArgs& a, const unsigned tb, const unsigned ntb) {
     __shared__ double sm[2][TAIL_MAX_WAVES];
     const float hs = 0.5f / (float)a.S;
-#ifndef VMP_TAIL_LL2
-#define VMP_TAIL_LL2 1
-#endif
-    const bool ll2 = VMP_TAIL_LL2 && (a.S & 1) == 0 && (reinterpret_cast<uintptr_t>(a.ll) & 7) == 0;
+    const bool ll2 = (a.S & 1) == 0 && (reinterpret_cast<uintptr_t>(a.ll) & 7) == 0;
     double wa = 0.0, rg = 0.0;
     for (long long c = (long long)tb * blockDim.x + threadIdx.x; c < a.NK; c += (long long)ntb * blockDim.x) {
         const float lz = a.lz[c], tp = a.Tp[c];

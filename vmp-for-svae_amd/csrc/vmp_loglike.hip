@@ -146,8 +146,8 @@ __global__ __launch_bounds__(256) void eval_kernel(EvArgs a) {
                 sq += q;
                 if (a.var) {
                     if (a.logw) lp += a.logw_per_sample ? a.logw[cc * S + s] : a.logw[cc];
-                    const float nm = fmaxf(mx, lp);                 // online log-sum-exp
-                    se = se * __expf(mx - nm) + __expf(lp - nm);
+                    const float nm = fmaxf(mx, lp);                 // online log-sum-exp; a term of -inf (logw = -inf) adds nothing
+                    if (nm > -INFINITY) se = se * __expf(mx - nm) + __expf(lp - nm);
                     mx = nm;
                 }
             }

@@ -150,6 +150,38 @@ int    vmp_mix_iterate(const float* x, int64_t N, int D, int K, int flavour,
                        float* pack, void* ws, size_t ws_bytes, int iterations, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Mixture scoring (csrc/vmp_score.hip): held-out log predictive density of the pure mixtures in one streaming pass
+ * ------------------------------------------------------------------------------------------------
+ *   log p(x_n) = logsumexp_k [ c_k - h_k log1p(a_k q_nk) ],   q_nk = || W_k (x_n - m_k) ||^2,  W_k lower-triangular.
+ * Score pack: (K, vmp_mix_pack_words(D)) fp32 = [ m_k (D) | W_k packed lower-triangular, row-major (D(D+1)/2) | c | h | a | 0 ]
+ * (natural-log units; NOT interchangeable with the E-step pack of vmp_mix_finalize).  A component whose matrix is not
+ * symmetric positive definite, or whose degrees of freedom are not positive, gets NaN in W, c, h, a: every row scores NaN.
+ *
+ * vmp_mix_score_pack_niw: the posterior predictive of a variational GMM (Bishop, PRML 10.81-10.82) from the NIW posterior
+ *   (alpha (K), beta (K), m (K,D), C (K,D,D), v (K)) - the theta of gmm.inference (models/gmm.py:230-269); C is the inverse
+ *   scale (P_k = C_k^-1, gmm.py:260) and (v_k, P_k) the Wishart (nu, W) pair as gmm.py:84-94 reads it:
+ *   nu' = v + 1 - D,  C = L L^T,  W = L^-1,  a = beta / (1 + beta),  h = (nu' + D) / 2,
+ *   c = log(alpha / sum alpha) + lgamma(h) - lgamma(nu' / 2) - D/2 log(pi nu') + D/2 log(nu' beta / (1 + beta)) - sum_i log L_ii.
+ * vmp_mix_score_pack_t: explicit Student-t mixture (log_w (K), mu (K,D), sigma (K,D,D), nu (K)): student_t.log_probability
+ *   (distributions/student_t.py:31-37) + log_w, i.e. the (N,K) terms of logprob_smm_mixture (student_t.py:42-56):
+ *   sigma = L L^T,  W = L^-1,  a = 1 / nu,  h = (nu + D) / 2,  c = log_w + lgamma(h) - lgamma(nu / 2) - D/2 log(pi nu) - sum_i log L_ii. */
+int    vmp_mix_score_pack_niw(int D, int K, const float* alpha, const float* beta, const float* m, const float* C,
+                              const float* v, float* pack, void* stream);
+int    vmp_mix_score_pack_t(int D, int K, const float* log_w, const float* mu, const float* sigma, const float* nu,
+                            float* pack, void* stream);
+/* The streaming pass: the log-sum-exp over k the reference leaves to its caller after student_t.py:42-56 (and, for the GMM,
+ * the predictive density its models/gmm.py does not have).  x (N,D) (any alignment), pack from one of the builders above.
+ * Outputs, each optional but not all NULL: logp_out (N); resp_out (N,K) = exp(term_nk - logp_n), the predictive
+ * responsibilities (0 in a row whose every term is -inf, where logp = -inf); sum_out = sum_n logp_n, one fp64 word:
+ * per-block fp64 partials in `ws` (vmp_mix_score_workspace_bytes, needed only with sum_out) added in a fixed order by a
+ * second one-wave launch - no atomics, bit-identical from run to run and whichever other outputs are requested.
+ * Errors (decided before any launch): VMP_E_DIM (D, K outside 1..VMP_MAX_D / 1..VMP_MAX_K), VMP_E_BADARG (N < 1, x or pack
+ * NULL, no output), VMP_E_WS.                                                                                        */
+size_t vmp_mix_score_workspace_bytes(int64_t N, int D, int K);
+int    vmp_mix_score(const float* x, int64_t N, int D, int K, const float* pack, float* logp_out, float* resp_out,
+                     double* sum_out, void* ws, size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * T2: SVAE E-step fused with the ELBO regulariser (models/svae.py:14-119 and :229-252)
  * ------------------------------------------------------------------------------------------------
  * Per (n,k) cell:  Pt = diag(-2 eta2d_n) + P_k,  ht = eta1_n + h_k,  Lt = chol(Pt),

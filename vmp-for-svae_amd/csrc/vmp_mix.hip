@@ -20,6 +20,7 @@
 // and are reduced in a fixed order by the finalize kernel (deterministic, no atomics).
 // See vmp_common.h for the packed-fp32 op_sel erratum the bf16 MFMAs expose.
 #include "vmp_common.h"
+#include "vmp_linalg.h"
 #include <stdlib.h>
 #include <type_traits>
 
@@ -65,31 +66,6 @@ struct PassArgs {
 #define PASS_TS(i) do { } while (0)
 #endif
 
-template <int D>
-__device__ __forceinline__ void load_row(const float* __restrict__ p, float (&o)[D], bool vec) {
-    if constexpr (D % 4 == 0) {
-        if (vec) {
-#pragma unroll
-            for (int j = 0; j < D / 4; ++j) {
-                float4 v = reinterpret_cast<const float4*>(p)[j];
-                o[4 * j] = v.x; o[4 * j + 1] = v.y; o[4 * j + 2] = v.z; o[4 * j + 3] = v.w;
-            }
-            return;
-        }
-    } else if constexpr (D % 2 == 0) {
-        if (vec) {
-#pragma unroll
-            for (int j = 0; j < D / 2; ++j) {
-                float2 v = reinterpret_cast<const float2*>(p)[j];
-                o[2 * j] = v.x; o[2 * j + 1] = v.y;
-            }
-            return;
-        }
-    }
-#pragma unroll
-    for (int j = 0; j < D; ++j) o[j] = p[j];
-}
-
 // all-reduce over the 16 lanes of a DPP row (= the 16 components of one data row) by row rotations.
 // Hand-written DPP: one instruction per butterfly step.  The two wait states a DPP read needs after a VALU
 // write of the same VGPR are explicit (hipcc's hazard recogniser does not look inside asm).
@@ -122,13 +98,6 @@ constexpr int MOM_TERMS = 3;
 #ifndef VMP_MOM_FLUSH
 #define VMP_MOM_FLUSH 2       // tiles of 64 rows between two fp32 -> fp64 flushes of the moment accumulators (both pass kernels)
 #endif
-
-__device__ __forceinline__ double readlane_d(double v, int src_lane) {
-    int lo = __double2loint(v), hi = __double2hiint(v);
-    lo = __builtin_amdgcn_readlane(lo, src_lane);
-    hi = __builtin_amdgcn_readlane(hi, src_lane);
-    return __hiloint2double(hi, lo);
-}
 
 // Block reduction of the fp64 moment accumulators (waves summed in a fixed order) and the per-block partial: shared by
 // the two pass kernels below.
@@ -1100,53 +1069,6 @@ __device__ void write_pack(float* pack, int k, const double* m, const double* W 
     const double LOG2E = 1.4426950408889634074;          // the pass kernel evaluates 2^(c - h q)
     p[idx++] = (float)(c * LOG2E); p[idx++] = (float)(h * LOG2E); p[idx++] = (float)ua; p[idx++] = (float)ub;
 }
-
-// Cholesky of SPD A (DxD, row-major) -> lower L (in place, upper zeroed).  Returns false if not SPD.
-// Fully unrolled so that the matrix lives in registers (runtime-indexed local arrays would go to scratch).
-template <int D>
-__device__ __forceinline__ bool chol_lower(double (&A)[D * D]) {
-    bool ok = true;
-#pragma unroll
-    for (int j = 0; j < D; ++j) {
-        double s = A[j * D + j];
-#pragma unroll
-        for (int p = 0; p < j; ++p) s -= A[j * D + p] * A[j * D + p];
-        ok = ok && (s > 0.0);
-        const double d = sqrt(s);
-        const double rd = 1.0 / d;
-        A[j * D + j] = d;
-#pragma unroll
-        for (int i = j + 1; i < D; ++i) {
-            double t = A[i * D + j];
-#pragma unroll
-            for (int p = 0; p < j; ++p) t -= A[i * D + p] * A[j * D + p];
-            A[i * D + j] = t * rd;
-        }
-#pragma unroll
-        for (int i = 0; i < j; ++i) A[i * D + j] = 0.0;
-    }
-    return ok;
-}
-
-// inverse of lower-triangular L -> Li (lower)
-template <int D>
-__device__ __forceinline__ void tri_inv_lower(const double (&L)[D * D], double (&Li)[D * D]) {
-#pragma unroll
-    for (int i = 0; i < D * D; ++i) Li[i] = 0.0;
-#pragma unroll
-    for (int j = 0; j < D; ++j) {
-        Li[j * D + j] = 1.0 / L[j * D + j];
-#pragma unroll
-        for (int i = j + 1; i < D; ++i) {
-            double s = 0.0;
-#pragma unroll
-            for (int p = j; p < i; ++p) s += L[i * D + p] * Li[p * D + j];
-            Li[i * D + j] = -s / L[i * D + i];
-        }
-    }
-}
-
-
 
 // 1/sqrt(x) for a positive, normal x: the hardware estimate (v_rsq_f64, ~2^-26) and two Newton steps - 8 dependent
 // operations on the serial chain of the factorisation instead of the library routine's range handling.

@@ -19,3 +19,15 @@ def logprob_smm_mixture(y, mu, sigma, v, log_pi, name='student_t_logprob'):
     K = mu.shape[0]
     yk = y[:, None, None, :].expand(N, K, 1, D).contiguous()
     return log_probability_per_samp(yk, mu, sigma, v).reshape(N, K) + log_pi[None, :]
+
+
+def mixture_logprob(y, mu, sigma, v, log_pi, return_resp=False):
+    """log sum_k pi_k S(y_n | mu_k, sigma_k, v_k): y (N,D) -> (N,), equal to logsumexp(logprob_smm_mixture(...), dim=1)
+    (reference student_t.py:42-56 followed by the log-sum-exp its caller takes) without the (N,K,1,D) expansion or the (N,K)
+    intermediate: one streaming HIP pass over y (vmp_mix_score_pack_t + vmp_mix_score).  return_resp=True also returns the
+    (N,K) responsibilities exp(term_nk - logp_n)."""
+    from ..models import _mix
+    _mix._score_dims(y, mu, 'mixture_logprob')
+    pack = _mix.score_pack_t(log_pi, mu, sigma, v)
+    logp, resp, _ = _mix.mixture_score(y, pack, want_resp=return_resp, want_sum=False)
+    return (logp, resp) if return_resp else logp

@@ -122,6 +122,67 @@ def estep(x, pack, flavour, miss_mask=None, want_logr=False, want_stats=False, r
     return r, u, logr, stats
 
 
+def _kd(t, name, shape):
+    """shape check of a K-sized operand BEFORE the library or the device is touched (CPU tensors fail here too)"""
+    if not torch.is_tensor(t) or tuple(t.shape) != tuple(shape):
+        raise L.VmpError('%s has shape %s, expected %s' % (name, tuple(t.shape) if torch.is_tensor(t) else type(t), tuple(shape)))
+    return t
+
+
+def _score_dims(x, m, what):
+    if not torch.is_tensor(x) or x.dim() != 2:
+        raise L.VmpError('%s: x must be (N,D)' % what)
+    if not torch.is_tensor(m) or m.dim() != 2 or m.shape[1] != x.shape[1]:
+        raise L.VmpError('%s: the component locations must be (K,%d), got %s' % (what, x.shape[1], tuple(m.shape) if torch.is_tensor(m) else type(m)))
+    K = m.shape[0]
+    N, D = _dims(x, K)
+    if N < 1:
+        raise L.VmpError('%s: x has no rows' % what)
+    return N, D, K
+
+
+def score_pack_niw(alpha_k, beta_k, m_k, C_k, v_k):
+    """Score pack of the GMM posterior predictive (vmp_mix_score_pack_niw; Bishop 10.81-10.82) from the NIW posterior
+    (alpha (K), beta (K), m (K,D), C (K,D,D), v (K)) = gmm.inference's theta."""
+    K, D = m_k.shape
+    ops = [_kd(t, n, shp) for t, n, shp in ((alpha_k, 'alpha_k', (K,)), (beta_k, 'beta_k', (K,)), (m_k, 'm_k', (K, D)),
+                                            (C_k, 'C_k', (K, D, D)), (v_k, 'v_k', (K,)))]
+    ops = [L.dev_f32(t.detach().to(torch.float32), n) for t, n in zip(ops, ('alpha_k', 'beta_k', 'm_k', 'C_k', 'v_k'))]
+    pack = torch.empty(K, L.lib().vmp_mix_pack_words(D), dtype=torch.float32, device=m_k.device)
+    L.check(L.lib().vmp_mix_score_pack_niw(D, K, *[L.ptr(t) for t in ops], L.ptr(pack), L.stream()), 'vmp_mix_score_pack_niw')
+    return pack
+
+
+def score_pack_t(log_w, mu, sigma, nu):
+    """Score pack of an explicit Student-t mixture (vmp_mix_score_pack_t; reference student_t.py:31-37): log_w (K), mu (K,D),
+    sigma (K,D,D) scale matrices, nu (K) degrees of freedom."""
+    K, D = mu.shape
+    ops = [_kd(t, n, shp) for t, n, shp in ((log_w, 'log_w', (K,)), (mu, 'mu', (K, D)), (sigma, 'sigma', (K, D, D)), (nu, 'nu', (K,)))]
+    ops = [L.dev_f32(t.detach().to(torch.float32), n) for t, n in zip(ops, ('log_w', 'mu', 'sigma', 'nu'))]
+    pack = torch.empty(K, L.lib().vmp_mix_pack_words(D), dtype=torch.float32, device=mu.device)
+    L.check(L.lib().vmp_mix_score_pack_t(D, K, *[L.ptr(t) for t in ops], L.ptr(pack), L.stream()), 'vmp_mix_score_pack_t')
+    return pack
+
+
+def mixture_score(x, pack, want_logp=True, want_resp=False, want_sum=True):
+    """One streaming pass (vmp_mix_score): (logp (N,) fp32, resp (N,K) fp32, total 0-dim fp64) of the rows of x under a score
+    pack; outputs that are not wanted are None.  Everything stays on the device: no host synchronisation."""
+    x = L.dev_f32(x, 'x')
+    K = pack.shape[0]
+    N, D = _dims(x, K)
+    dev = x.device
+    logp = torch.empty(N, dtype=torch.float32, device=dev) if want_logp else None
+    resp = torch.empty(N, K, dtype=torch.float32, device=dev) if want_resp else None
+    total, ws, nb = None, None, 0
+    if want_sum:
+        total = torch.empty((), dtype=torch.float64, device=dev)
+        nb = L.lib().vmp_mix_score_workspace_bytes(N, D, K)
+        ws = L.workspace(dev, nb)
+    L.check(L.lib().vmp_mix_score(L.ptr(x), N, D, K, L.ptr(pack), L.ptr(logp), L.ptr(resp), L.ptr(total), L.ptr(ws), nb,
+                                  L.stream()), 'vmp_mix_score')
+    return logp, resp, total
+
+
 def default_prior(K, D, device):
     """The prior gmm.inference / smm.inference hard-code (reference gmm.py:252-256): init_mm_params(K, D,
     alpha_scale=0.05/K, beta_scale=0.5, m_scale=0, C_scale=D+0.5, v_init=D+0.5), in standard form."""
@@ -237,6 +298,42 @@ class VMPLoop(object):
                 'vmp_mix_iterate')
         self.iterations += int(iterations)
         return self.r
+
+    def score_pack(self):
+        """Score pack of the CURRENT posterior (self.post: needs one iteration).  GMM: the posterior predictive (score_pack_niw); SMM: the plug-in Student-t mixture with mu = m_k,
+        sigma = C_k / v_k, nu = kappa, log_w = log(alpha_k / sum alpha) (score_pack_t; see smm.heldout_logprob)."""
+        if self.iterations == 0:
+            raise L.VmpError('no posterior to score yet: run at least one iteration')
+        al, be, m, C, v = self.theta()
+        if self.flavour == L.VMP_SMM:
+            return score_pack_t(torch.log(al / al.sum()), m, C / v[:, None, None], self.kappa)
+        return score_pack_niw(al, be, m, C, v)
+
+    def score(self, x_val):
+        """Mean log score (nats per row) of the rows of x_val (M,D) under the current posterior: the GMM's log posterior
+        predictive density, the SMM's plug-in log density.  One streaming launch over x_val, one scalar read-back."""
+        x_val = L.dev_f32(x_val, 'x_val')
+        if x_val.dim() != 2 or x_val.shape[1] != self.D or x_val.shape[0] < 1:
+            raise L.VmpError('x_val has shape %s, expected (M >= 1, %d)' % (tuple(x_val.shape), self.D))
+        _, _, total = mixture_score(x_val, self.score_pack(), want_logp=False)
+        return total.item() / x_val.shape[0]
+
+    def run_until(self, x_val, tol, check_every=5, max_iterations=1000):
+        """run(check_every) and score(x_val) in turn until the score improves by less than `tol` (absolute, nats per row) over
+        the previous check, or `max_iterations` iterations of this call are done.  Returns [(iterations, score), ...] with
+        `iterations` the loop's running count.  A plain host loop: one scalar read-back per check."""
+        check_every = int(check_every)
+        if check_every < 1:
+            raise L.VmpError('check_every must be >= 1')
+        hist, done = [], 0
+        while done < max_iterations:
+            n = min(check_every, max_iterations - done)
+            self.run(n)
+            done += n
+            hist.append((self.iterations, self.score(x_val)))
+            if len(hist) > 1 and hist[-1][1] - hist[-2][1] < tol:
+                break
+        return hist
 
     @property
     def stats(self):

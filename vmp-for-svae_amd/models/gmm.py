@@ -133,6 +133,18 @@ def compute_rnk(expct_log_pi, expct_log_det_cov, expct_dev):
     return torch.softmax(expct_log_pi + 0.5 * expct_log_det_cov - 0.5 * expct_dev, dim=1)
 
 
+def predictive_logprob(x, alpha_k, beta_k, m_k, C_k, v_k, return_resp=False):
+    """Log posterior predictive density of the variational GMM (Bishop, PRML 10.81-10.82) at the rows of x (N,D), from the NIW
+    posterior (alpha_k, beta_k, m_k, C_k, v_k) that inference()'s theta handle returns (C_k is the inverse scale, gmm.py:260):
+    a mixture of Student-t densities with nu' = v_k + 1 - D degrees of freedom, evaluated in one streaming HIP pass
+    (vmp_mix_score_pack_niw + vmp_mix_score).  Returns (logp (N,), total) - total a 0-dim fp64 DEVICE tensor holding
+    sum_n logp_n (deterministic; no host synchronisation) - plus resp (N,K), the predictive responsibilities, when asked."""
+    _mix._score_dims(x, m_k, 'predictive_logprob')
+    pack = _mix.score_pack_niw(alpha_k, beta_k, m_k, C_k, v_k)
+    logp, resp, total = _mix.mixture_score(x, pack, want_resp=return_resp)
+    return (logp, total, resp) if return_resp else (logp, total)
+
+
 class _Handle(object):
     """Stand-in for a TF fetch: call it to get the current value."""
 

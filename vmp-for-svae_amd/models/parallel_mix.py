@@ -238,7 +238,9 @@ class PeerExchange(object):
 class DistributedVMPLoop(_mix.VMPLoop):
     """VMPLoop whose posterior update sees the statistics of ALL ranks' rows.  exchange=PeerExchange(...): the whole
     distributed finalize is ONE launch (moments pushed into the peers' buffers by the kernel itself); otherwise three
-    launches around one all-reduce (RCCL through torch.distributed or the C ABI's PackComm)."""
+    launches around one all-reduce (RCCL through torch.distributed or the C ABI's PackComm).
+    score() / run_until() are inherited: they score the rows THIS rank passes in under the (global) posterior; no collective is
+    added - a cross-rank mean is the caller's all-reduce of (total, rows)."""
 
     def __init__(self, x, r_init, flavour, kappa=None, u_init=None, prior=None, group=None, comm=None, exchange=None):
         # (the data-parallel iteration keeps two launches: the exchange sits between the partial sums and the posterior)

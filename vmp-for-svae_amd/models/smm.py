@@ -109,6 +109,23 @@ def e_step(x, alpha_k, beta_k, m_k, P_k, v_k, kappa_k, name='e_step'):
     return r, u, pi
 
 
+def heldout_logprob(x, alpha_k, beta_k, m_k, C_k, v_k, kappa_k, return_resp=False):
+    """Plug-in log score of the Student-t mixture at the rows of x (N,D) from inference()'s theta
+    (alpha_k, beta_k, m_k, C_k, v_k, kappa_k): the mixture of student_t.logprob_smm_mixture (student_t.py:42-56) + a
+    log-sum-exp over k, with the point estimates
+      mu_k = m_k,   sigma_k = C_k / v_k  (the inverse of the expected precision v_k P_k that smm.py:88-97 uses),
+      nu_k = kappa_k,   log_w_k = log(alpha_k / sum alpha)
+    (beta_k does not enter a plug-in score).  One streaming HIP pass (vmp_mix_score_pack_t + vmp_mix_score).  Returns
+    (logp (N,), total) - total a 0-dim fp64 device tensor, sum_n logp_n, no host synchronisation - plus resp (N,K) when asked."""
+    N, D, K = _mix._score_dims(x, m_k, 'heldout_logprob')
+    for t, n, shp in ((alpha_k, 'alpha_k', (K,)), (beta_k, 'beta_k', (K,)), (C_k, 'C_k', (K, D, D)), (v_k, 'v_k', (K,)),
+                      (kappa_k, 'kappa_k', (K,))):
+        _mix._kd(t, n, shp)
+    pack = _mix.score_pack_t(torch.log(alpha_k / alpha_k.sum()), m_k, C_k / v_k[:, None, None], kappa_k)
+    logp, resp, total = _mix.mixture_score(x, pack, want_resp=return_resp)
+    return (logp, total, resp) if return_resp else (logp, total)
+
+
 def inference(x, K, kappa_init, seed, name='inference', r_init=None):
     """reference smm.py:199-245: as gmm.inference with u_nk initialised to ones and constant kappa."""
     N, D = x.shape

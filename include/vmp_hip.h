@@ -148,6 +148,13 @@ int    vmp_mix_iterate(const float* x, int64_t N, int D, int K, int flavour,
                        const float* kappa, const float* pivot, float* r, float* u,
                        float* alpha, float* beta, float* m, float* C, float* v, float* xbar, float* S, float* pi,
                        float* pack, void* ws, size_t ws_bytes, int iterations, void* stream);
+/* Host query, no launch and no device: the launch plan of a streaming pass of the mixture.  estep / stats / mask name the pass: the M-pass
+ * of vmp_mix_stats* is (0,1,0), vmp_mix_estep runs (1,0,0), with stats_out (1,1,0) - the pass of vmp_mix_estep_fused - and with a
+ * miss_mask (1,0,1).  out = [form (1 tiled, 2 XDL) | KT (tiled: 16-component tiles per wave) or MT (XDL: bf16 terms of the moment
+ * operands) | waves per block | blocks = partial rows the finalize launches reduce | rows per wave | rows per wave of a block's second
+ * half | parallel block reduction | dynamic LDS bytes].  Returns 0, or what the pass would return and out zeroed: VMP_E_DIM,
+ * VMP_E_BADARG (N < 1, a flavour that is neither, a combination no kernel exists for: a mask with VMP_SMM or with stats).  */
+int    vmp_mix_pass_plan(int64_t N, int D, int K, int flavour, int estep, int stats, int mask, int64_t* out);
 
 /* ------------------------------------------------------------------------------------------------
  * Mixture scoring (csrc/vmp_score.hip): held-out log predictive density of the pure mixtures in one streaming pass

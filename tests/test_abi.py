@@ -191,6 +191,92 @@ def test_minibatch_step_entry_points_validate_on_the_host():
         assert fn(*rest) == -2 and b'range' in lib.vmp_last_error(), fn.__name__
 
 
+_P64 = ctypes.c_void_p(64)                 # a non-NULL pointer that is never dereferenced: every call of the table fails its checks first
+_BIG = 1 << 40                             # workspace bytes: no size check fails before the pointer checks
+_PRIOR, _POST = [_P64] * 5, [_P64] * 9     # alpha0 beta0 m0 C0 v0 | alpha beta m C v xbar S pi pack
+# name -> arguments (N = 100, D = 8, K = 16; `fl` is the flavour) with every pointer set, kappa included
+_MIX_CALLS = {
+    'vmp_mix_pivot': lambda fl: [_P64, 100, 8, _P64, None],
+    'vmp_mix_stats': lambda fl: [_P64, _P64, _P64 if fl else None, _P64, 100, 8, 16, _P64, _P64, _BIG, None],
+    'vmp_mix_finalize': lambda fl: [_P64, 8, 16, fl] + _PRIOR + [_P64] + _POST + [None],
+    'vmp_mix_pack_from_params': lambda fl: [8, 16, fl] + [_P64] * 5 + [_P64, _P64, _P64, None],
+    'vmp_mix_estep': lambda fl: [_P64, 100, 8, 16, fl, _P64, None, _P64, _P64, _P64, _P64, _P64, _P64, _BIG, None],
+    'vmp_mix_estep_fused': lambda fl: [_P64, 100, 8, 16, fl, _P64, _P64, _P64, _P64, _P64, _P64, _BIG, None],
+    'vmp_mix_stats_ws': lambda fl: [_P64, _P64, _P64 if fl else None, _P64, 100, 8, 16, _P64, _BIG, None],
+    'vmp_mix_stats_ws_accurate': lambda fl: [_P64, _P64, _P64 if fl else None, _P64, 100, 8, 16, _P64, _BIG, None],
+    'vmp_mix_finalize_ws': lambda fl: [_P64, _P64, 100, 8, 16, fl] + _PRIOR + [_P64] + _POST + [_P64, None],
+    'vmp_mix_finalize_ws64': lambda fl: [_P64, _P64, 100, 8, 16, fl] + _PRIOR + [_P64] + _POST + [_P64, _P64, None],
+    'vmp_mix_finalize_exchange': lambda fl: [_P64, _P64, 100, 8, 16, fl] + _PRIOR + [_P64] + _POST
+                                            + [_P64, (ctypes.c_void_p * 2)(64, 64), 2, 0, 0, _P64, None],
+    'vmp_mix_estep_accurate': lambda fl: [_P64, 100, 8, 16, fl, _P64, _P64, _P64, _P64, None],
+    'vmp_mix_iterate': lambda fl: [_P64, 100, 8, 16, fl] + _PRIOR + [_P64, _P64, _P64, _P64] + _POST + [_P64, _BIG, 1, None],
+    'vmp_mix_pass_plan': lambda fl: [100, 8, 16, fl, 1, 1, 0, _P64],
+}
+# (entry point, flavour, index of the argument that is NULL - 'peer': the second row of the peer table, code).  The pointers each form
+# NEEDS: everything but the optional pivot, logr_out, stats_out, u (GMM), kappa (GMM), the posterior outputs and the stream.  The
+# codes are what the library answered on this very table at the commit before the argument builders of csrc/vmp_mix.hip (Prior /
+# Posterior / check_prior, pass_args, fin_from_ws) replaced the per-entry-point copies; vmp_mix_pass_plan did not exist then.
+_MIX_NULL_CODES = (
+    ('vmp_mix_pivot', 0, 0, -1), ('vmp_mix_pivot', 0, 3, -1),
+    ('vmp_mix_stats', 0, 0, -1), ('vmp_mix_stats', 0, 1, -1), ('vmp_mix_stats', 0, 7, -1), ('vmp_mix_stats', 0, 8, -1),
+    ('vmp_mix_finalize', 0, 0, -1), ('vmp_mix_finalize', 0, 4, -1), ('vmp_mix_finalize', 0, 5, -1), ('vmp_mix_finalize', 0, 6, -1),
+    ('vmp_mix_finalize', 0, 7, -1), ('vmp_mix_finalize', 0, 8, -1), ('vmp_mix_finalize', 1, 9, -1),
+    ('vmp_mix_pack_from_params', 0, 3, -1), ('vmp_mix_pack_from_params', 0, 4, -1), ('vmp_mix_pack_from_params', 0, 5, -1),
+    ('vmp_mix_pack_from_params', 0, 6, -1), ('vmp_mix_pack_from_params', 0, 7, -1), ('vmp_mix_pack_from_params', 0, 9, -1),
+    ('vmp_mix_pack_from_params', 1, 8, -1),
+    ('vmp_mix_estep', 0, 0, -1), ('vmp_mix_estep', 0, 5, -1), ('vmp_mix_estep', 0, 7, -1), ('vmp_mix_estep', 1, 8, -1),
+    ('vmp_mix_estep', 0, 12, -3),                                                        # stats_out without a workspace: VMP_E_WS
+    ('vmp_mix_estep_fused', 0, 0, -1), ('vmp_mix_estep_fused', 0, 5, -1), ('vmp_mix_estep_fused', 0, 6, -1),
+    ('vmp_mix_estep_fused', 0, 10, -1), ('vmp_mix_estep_fused', 1, 7, -1),
+    ('vmp_mix_stats_ws', 0, 0, -1), ('vmp_mix_stats_ws', 0, 1, -1), ('vmp_mix_stats_ws', 0, 7, -1),
+    ('vmp_mix_stats_ws_accurate', 0, 0, -1), ('vmp_mix_stats_ws_accurate', 0, 1, -1), ('vmp_mix_stats_ws_accurate', 0, 7, -1),
+    ('vmp_mix_finalize_ws', 0, 0, -1), ('vmp_mix_finalize_ws', 0, 6, -1), ('vmp_mix_finalize_ws', 0, 7, -1),
+    ('vmp_mix_finalize_ws', 0, 8, -1), ('vmp_mix_finalize_ws', 0, 9, -1), ('vmp_mix_finalize_ws', 0, 10, -1),
+    ('vmp_mix_finalize_ws', 1, 11, -1),
+    ('vmp_mix_finalize_ws64', 0, 0, -1), ('vmp_mix_finalize_ws64', 0, 6, -1), ('vmp_mix_finalize_ws64', 0, 7, -1),
+    ('vmp_mix_finalize_ws64', 0, 8, -1), ('vmp_mix_finalize_ws64', 0, 9, -1), ('vmp_mix_finalize_ws64', 0, 10, -1),
+    ('vmp_mix_finalize_ws64', 0, 20, -1), ('vmp_mix_finalize_ws64', 0, 21, -1), ('vmp_mix_finalize_ws64', 1, 11, -1),
+    ('vmp_mix_finalize_exchange', 0, 0, -1), ('vmp_mix_finalize_exchange', 0, 6, -1), ('vmp_mix_finalize_exchange', 0, 7, -1),
+    ('vmp_mix_finalize_exchange', 0, 8, -1), ('vmp_mix_finalize_exchange', 0, 9, -1), ('vmp_mix_finalize_exchange', 0, 10, -1),
+    ('vmp_mix_finalize_exchange', 0, 22, -1), ('vmp_mix_finalize_exchange', 0, 'peer', -1), ('vmp_mix_finalize_exchange', 1, 11, -1),
+    ('vmp_mix_estep_accurate', 0, 0, -1), ('vmp_mix_estep_accurate', 0, 5, -1), ('vmp_mix_estep_accurate', 0, 6, -1),
+    ('vmp_mix_estep_accurate', 1, 7, -1),
+    # the iteration refuses pack itself; ws, the prior and kappa are refused by its first launch's entry point, vmp_mix_finalize_ws
+    ('vmp_mix_iterate', 0, 22, -1), ('vmp_mix_iterate', 0, 23, -1), ('vmp_mix_iterate', 0, 5, -1), ('vmp_mix_iterate', 0, 6, -1),
+    ('vmp_mix_iterate', 0, 7, -1), ('vmp_mix_iterate', 0, 8, -1), ('vmp_mix_iterate', 0, 9, -1), ('vmp_mix_iterate', 1, 10, -1),
+    ('vmp_mix_pass_plan', 0, 7, -1),
+)
+
+
+def _call_with_null(lib, name, fl, i):
+    args = _MIX_CALLS[name](fl)
+    if i == 'peer':
+        args[22] = (ctypes.c_void_p * 2)(64, 0)
+    else:
+        assert args[i] is _P64 or (name, i) == ('vmp_mix_finalize_exchange', 22), (name, i)       # the table nulls pointers, nothing else
+        args[i] = None
+    rc = getattr(lib, name)(*args)
+    return rc, lib.vmp_last_error() or b''
+
+
+def test_mixture_entry_points_refuse_each_needed_null_pointer():
+    """Every vmp_mix_* entry point of csrc/vmp_mix.hip, each pointer its form needs: refused on the host (nothing is launched) with the
+    recorded code - VMP_E_BADARG, but for the one VMP_E_WS - and a message that names the entry point that refused."""
+    import vmp_for_svae_amd as V
+    lib = V._lib.lib()
+    assert {n for n, _, _, _ in _MIX_NULL_CODES} == set(_MIX_CALLS)
+    in_mix = {n for n in V._lib.exported_symbols() if n.startswith('vmp_mix_')} - {
+        'vmp_mix_pack_words', 'vmp_mix_stats_words', 'vmp_mix_workspace_bytes',                      # no pointer argument
+        'vmp_mix_score', 'vmp_mix_score_pack_niw', 'vmp_mix_score_pack_t', 'vmp_mix_score_workspace_bytes',   # tests/test_mix_score_abi.py
+        'vmp_mix_mahalanobis'}                                                                       # tests/test_standalone_kernels_abi.py
+    assert in_mix == set(_MIX_CALLS)
+    for name, fl, i, code in _MIX_NULL_CODES:
+        rc, msg = _call_with_null(lib, name, fl, i)
+        assert rc == code and code < 0, (name, fl, i, rc)
+        who = b'vmp_mix_finalize_ws' if name == 'vmp_mix_iterate' and i != 22 else name.encode()
+        assert who in msg, (name, fl, i, msg)
+
+
 def test_no_cpu_fallback():
     import vmp_for_svae_amd as V
     from vmp_for_svae_amd.models import gmm, _mix

@@ -152,6 +152,48 @@ def test_vmp_steps_vs_oracle(N, D, K):
             assert relerr(t, o.numpy(), 'smm ' + n_, 1e-5) <= 1e-5
 
 
+@pytest.mark.parametrize('N', [65535, 65536])
+def test_vmp_steps_vs_oracle_on_both_sides_of_the_two_term_moment_threshold(N):
+    """VMP_MOM2_ROWS (csrc/vmp_mix.hip pass_plan): from 65 536 rows on the fused XDL pass multiplies 2-term moment operands, below it
+    3-term ones - two kernel instantiations picked by the plan.  The last size of the one and the first of the other, two steps of both
+    flavours, held to the bars of test_vmp_steps_vs_oracle."""
+    test_vmp_steps_vs_oracle(N, 8, 16)
+
+
+@pytest.mark.parametrize('flavour', ['gmm', 'smm'])
+@pytest.mark.parametrize('N,D,K', [(65, 8, 16), (5000, 5, 17)])
+def test_estep_with_stats_is_the_fused_pass_and_a_reduction_only_finalize(flavour, N, D, K):
+    """vmp_mix_estep(..., stats_out) runs the launches of vmp_mix_estep_fused followed by vmp_mix_finalize_ws with stats_out alone, with
+    the same arguments (one plan, one argument builder: csrc/vmp_mix.hip): on the same data, pack and pivot the two routes agree bit for
+    bit.  (XDL form at K = 16, tiled form with two component tiles at K = 17.)"""
+    from vmp_for_svae_amd import _lib as L
+    from vmp_for_svae_amd.models import _mix
+    x, r0 = _synth(N, D, K, seed=N + D + K)
+    fl = L.VMP_SMM if flavour == 'smm' else L.VMP_GMM
+    loop = _mix.VMPLoop(dev(x), dev(r0), fl, kappa=torch.full((K,), 5.0, device='cuda') if fl == L.VMP_SMM else None)
+    loop.finalize()
+    lib, P, s = L.lib(), L.ptr, L.stream()
+    pack, pivot, nb = loop.post['pack'], loop.pivot, loop.nb
+    out = []
+    for route in (0, 1):
+        r = torch.zeros(N, K, device='cuda')
+        u = torch.zeros(N, K, device='cuda') if fl == L.VMP_SMM else None
+        st = torch.zeros(K, lib.vmp_mix_stats_words(D), dtype=torch.float64, device='cuda')
+        ws = torch.zeros(nb, dtype=torch.uint8, device='cuda')
+        if route == 0:
+            L.check(lib.vmp_mix_estep(P(loop.x), N, D, K, fl, P(pack), None, P(r), P(u), None, P(pivot), P(st), P(ws), nb, s), 'vmp_mix_estep')
+        else:
+            L.check(lib.vmp_mix_estep_fused(P(loop.x), N, D, K, fl, P(pack), P(r), P(u), None, P(pivot), P(ws), nb, s), 'vmp_mix_estep_fused')
+            L.check(lib.vmp_mix_finalize_ws(P(ws), P(pivot), N, D, K, fl, *[P(t) for t in loop.prior], P(loop.kappa), *([None] * 9), P(st), s),
+                    'vmp_mix_finalize_ws')
+        out.append((r, u, st))
+    torch.cuda.synchronize()
+    (r1, u1, st1), (r2, u2, st2) = out
+    assert torch.isfinite(st1).all() and abs(st1[:, 0].sum().item() - N) < 1e-3 * N       # the moments were written at all
+    assert torch.equal(r1, r2) and torch.equal(st1, st2)
+    assert u1 is None or torch.equal(u1, u2)
+
+
 @pytest.mark.parametrize('flavour', ['gmm', 'smm'])
 @pytest.mark.parametrize('N,D,K', [(1, 2, 3), (65, 8, 16), (5000, 5, 17), (20000, 8, 16), (3000, 4, 64), (40001, 8, 10)])
 def test_accurate_mode_vs_oracle(flavour, N, D, K):
@@ -432,7 +474,7 @@ def test_fused_pass_equals_estep_only_repeatedly(N, D, K):
 
 @pytest.mark.parametrize('flavour,N,D,K', [('gmm', 300_007, 8, 16), ('smm', 300_007, 8, 16), ('gmm', 150_001, 5, 33)])
 def test_uneven_wave_shares_cover_every_row_once(flavour, N, D, K):
-    """At this size the pass kernel gives the two waves of a SIMD uneven contiguous row ranges (csrc/vmp_mix.hip make_plan:
+    """At this size the pass kernel gives the two waves of a SIMD uneven contiguous row ranges (csrc/vmp_mix.hip pass_plan:
     64 % / 36 %, also with K > 16 = several component tiles per lane); N is odd, so the last range is ragged.  Every row
     must be written exactly once and counted exactly once: r against the chunked fp64 oracle, the moments against a
     direct fp64 evaluation."""

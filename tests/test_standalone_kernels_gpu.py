@@ -1,5 +1,5 @@
 """Shape sweeps of the stand-alone density and metric kernels (csrc/vmp_density.hip, csrc/vmp_loglike.hip) against the fp64 oracle:
-every D instantiation of VMP_DISPATCH_DD, K in {1, 5, 32, 33, 64} (64 / 12 / 2 / 1 / 1 rows per wave), both Bernoulli forms, the
+every D instantiation of VMP_SWITCH_DIM, K in {1, 5, 32, 33, 64} (64 / 12 / 2 / 1 / 1 rows per wave), both Bernoulli forms, the
 float4 and the scalar reconstruction paths, every lanes-per-cell mapping of the loglike / eval kernels, and one case above every
 launcher's grid cap (guarded, NaN-prefilled outputs; called twice: bit-identical).
 

@@ -137,6 +137,19 @@ size_t lds_budget();
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) with its status checked: 0, or the HIP error code with the message set
 int  set_dyn_lds(const void* kernel, size_t bytes, const char* what);
 
+// ---- host-side helpers shared by the launch layers --------------------------------------------------
+inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }     // vector row loads / stores allowed (NULL counts)
+// compile-time dispatch over a dimension compiled for 1..8 (D of the mixture kernels, L of the SVAE E-step): the statement sees the
+// value as the constexpr int NAME; a value outside 1..8 runs nothing (the entry points have refused it before).
+#define VMP_DIM_CASE_(n, NAME, ...) case n: { constexpr int NAME = n; __VA_ARGS__; } break;
+#define VMP_SWITCH_DIM(v, NAME, ...)                                                                     \
+    switch (v) {                                                                                         \
+        VMP_DIM_CASE_(1, NAME, __VA_ARGS__) VMP_DIM_CASE_(2, NAME, __VA_ARGS__) VMP_DIM_CASE_(3, NAME, __VA_ARGS__) \
+        VMP_DIM_CASE_(4, NAME, __VA_ARGS__) VMP_DIM_CASE_(5, NAME, __VA_ARGS__) VMP_DIM_CASE_(6, NAME, __VA_ARGS__) \
+        VMP_DIM_CASE_(7, NAME, __VA_ARGS__) VMP_DIM_CASE_(8, NAME, __VA_ARGS__)                          \
+        default: break;                                                                                  \
+    }
+
 // ---- geometry of the mixture kernels -----------------------------------------------------------------
 template <int D>
 struct Geo {

@@ -158,19 +158,6 @@ __global__ __launch_bounds__(256) void student_t_kernel(TArgs a) {
     }
 }
 
-#define VMP_DISPATCH_DD(Dv, CALL)          \
-    switch (Dv) {                           \
-        case 1: { constexpr int DD = 1; CALL; } break; \
-        case 2: { constexpr int DD = 2; CALL; } break; \
-        case 3: { constexpr int DD = 3; CALL; } break; \
-        case 4: { constexpr int DD = 4; CALL; } break; \
-        case 5: { constexpr int DD = 5; CALL; } break; \
-        case 6: { constexpr int DD = 6; CALL; } break; \
-        case 7: { constexpr int DD = 7; CALL; } break; \
-        case 8: { constexpr int DD = 8; CALL; } break; \
-        default: break;                     \
-    }
-
 int chk(long long N, int K, int D, int S) {
     if (N <= 0 || S <= 0) { set_error("N and S must be positive"); return VMP_E_BADARG; }
     if (D < 1 || D > VMP_MAX_D) { set_error("D=%d outside compiled range 1..%d", D, VMP_MAX_D); return VMP_E_DIM; }
@@ -416,7 +403,7 @@ int vmp_gauss_logprob_nat_per_samp_bwd(const float* x, const float* eta1, const 
     long long blocks = ((long long)N * K + 255) / 256;
     if (blocks > 8192) blocks = 8192;
     rc = -1;
-    VMP_DISPATCH_DD(D, {
+    VMP_SWITCH_DIM(D, DD, {
         hipLaunchKernelGGL((gauss_nat_bwd_kernel<DD>), dim3((int)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), a);
         rc = check_launch("gauss_nat_bwd_kernel");
     });
@@ -435,7 +422,7 @@ int vmp_student_t_logprob_bwd(const float* y, const float* mu, const float* W, c
     if (!y || !mu || !W || !nu || !g || !gy || !partials) { set_error("vmp_student_t_logprob_bwd: null pointer"); return VMP_E_BADARG; }
     TBArgs a{y, mu, W, nu, g, gy, partials, (long long)N, K, S};
     rc = -1;
-    VMP_DISPATCH_DD(D, {
+    VMP_SWITCH_DIM(D, DD, {
         hipLaunchKernelGGL((student_t_bwd_kernel<DD>), dim3(vmp_student_t_bwd_blocks(N, S), K), dim3(256), 0, static_cast<hipStream_t>(stream), a);
         rc = check_launch("student_t_bwd_kernel");
     });
@@ -452,7 +439,7 @@ int vmp_gauss_logprob_nat_per_samp(const float* x, const float* eta1, const floa
     long long blocks = ((N + RPT - 1) / RPT + 3) / 4;
     if (blocks > 4096) blocks = 4096;
     rc = -1;
-    VMP_DISPATCH_DD(D, {
+    VMP_SWITCH_DIM(D, DD, {
         hipLaunchKernelGGL((gauss_nat_kernel<DD>), dim3((int)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), a);
         rc = check_launch("gauss_nat_kernel");
     });
@@ -469,7 +456,7 @@ int vmp_gauss_logprob_nat(const float* x, const float* eta1, const float* eta2, 
     long long blocks = ((N + RPT - 1) / RPT + 3) / 4;
     if (blocks > 4096) blocks = 4096;
     rc = -1;
-    VMP_DISPATCH_DD(D, {
+    VMP_SWITCH_DIM(D, DD, {
         hipLaunchKernelGGL((gauss_nat_kernel<DD>), dim3((int)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), a);
         rc = check_launch("gauss_nat_kernel");
     });
@@ -485,7 +472,7 @@ int vmp_student_t_logprob(const float* y, const float* mu, const float* W, const
     long long blocks = ((long long)N * K * S + 255) / 256;
     if (blocks > 8192) blocks = 8192;
     rc = -1;
-    VMP_DISPATCH_DD(D, {
+    VMP_SWITCH_DIM(D, DD, {
         hipLaunchKernelGGL((student_t_kernel<DD>), dim3((int)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), a);
         rc = check_launch("student_t_kernel");
     });

@@ -48,7 +48,7 @@ struct PassArgs {
     double* partials;
     long long N;
     long long rpw;        // rows per wave (multiple of 8): wave g owns rows [g*rpw, min(N, (g+1)*rpw))
-    long long rpw_b;      // != rpw: the first half of a block's waves own rpw rows each, the second half rpw_b (see make_plan)
+    long long rpw_b;      // != rpw: the first half of a block's waves own rpw rows each, the second half rpw_b (see pass_plan)
     int K;
     int vec_ok;       // x pointer 16-byte aligned (vector row loads allowed)
     int par_reduce;   // LDS holds one fp64 slab per wave: reduce the waves in one parallel step
@@ -1511,19 +1511,46 @@ __global__ __launch_bounds__(SMALL_STATS_GROUPS * 80) void small_stats_kernel(Sm
 // ---------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------
-struct Plan {
+// Which kernel a pass runs, and with what grid, block and LDS, is decided HERE and nowhere else: run_pass launches what the plan says,
+// the finalize callers size their reduction from it (partial_rows), and vmp_mix_pass_plan answers with it on the host alone.
+enum PassForm { PASS_NONE = 0, PASS_TILED = 1, PASS_XDL = 2 };
+struct PassPlan {
+    int form;                  // PASS_NONE: no kernel is instantiated for this combination
+    int flavour;
+    bool estep, stats, mask;   // with flavour: the instantiation of the form's kernel template
+    int kt_mt;                 // tiled: KT, the 16-component tiles of a wave (1, 2, 4); XDL: MT, the bf16 terms of the moment operands (2, 3)
     int nw, blocks, par_reduce;
     size_t lds;
     long long rpw, rpw_b;
 };
 
-Plan make_plan(long long N, int D, int K, int flavour, bool stats, bool xdl = false) {
-    Plan p;
+// % of a SIMD pair's rows for the older wave: measured optima (N = 3e5 .. 1e7)
+#ifndef VMP_SPLIT_GMM
+#define VMP_SPLIT_GMM 64
+#endif
+#ifndef VMP_SPLIT_SMM
+#define VMP_SPLIT_SMM 62
+#endif
+#ifndef VMP_MOM2_ROWS
+#define VMP_MOM2_ROWS (1ll << 16)      // rows from which the moment GEMM of the XDL pass multiplies 2-term operands (pass_xdl_body, MT)
+#endif
+
+PassPlan pass_plan(long long N, int D, int K, int flavour, bool estep, bool stats, bool mask) {
+    PassPlan p{};
+    if (N < 1 || D < 1 || D > VMP_MAX_D || K < 1 || K > VMP_MAX_K || (flavour != VMP_GMM && flavour != VMP_SMM)) return p;
+    // instantiated: M-pass (stats alone), E-pass, fused E-pass (estep and stats), masked E-pass (GMM, no stats)
+    if ((!estep && !stats) || (mask && (!estep || stats || flavour != VMP_GMM))) return p;
+    p.flavour = flavour; p.estep = estep; p.stats = stats; p.mask = mask;
+    const int KTn = (K + 15) / 16;
+    // E-part on the XDL pipe: E-step launches with K <= 16 and no missing-data mask
+    const bool xdl = estep && !mask && K <= 16;
+    p.form = xdl ? PASS_XDL : PASS_TILED;
+    p.kt_mt = xdl ? (stats && N >= VMP_MOM2_ROWS ? 2 : 3) : (KTn <= 2 ? KTn : 4);
     constexpr int tuned_blocks = 256;      // one 8-wave block per CU
     constexpr int tuned_nw = MAX_NW;
     const size_t wreg = (size_t)((D + 2) * LS + (xdl ? TR * AIS : 0)) * sizeof(float);
     int nw = tuned_nw;
-    if (nw > max_nw((K + 15) / 16)) nw = max_nw((K + 15) / 16);
+    if (nw > max_nw(KTn)) nw = max_nw(KTn);
     if (nw < 1) nw = 1;
     const long long ntiles = (N + TR - 1) / TR;
     if ((long long)nw > ntiles) nw = (int)ntiles;
@@ -1541,13 +1568,7 @@ Plan make_plan(long long N, int D, int K, int flavour, bool stats, bool xdl = fa
     // of the kernel runs one wave per SIMD with nothing to hide its latencies behind (s_setprio does not change it).  The
     // older waves therefore get the larger share, so that both mates finish together.  Ranges stay contiguous and fixed:
     // results remain deterministic.
-#ifndef VMP_SPLIT_GMM
-#define VMP_SPLIT_GMM 64
-#endif
-#ifndef VMP_SPLIT_SMM
-#define VMP_SPLIT_SMM 62
-#endif
-    const int split = flavour == VMP_SMM ? VMP_SPLIT_SMM : VMP_SPLIT_GMM;   // % of a pair's rows for the older wave: measured optima (N = 3e5 .. 1e7)
+    const int split = flavour == VMP_SMM ? VMP_SPLIT_SMM : VMP_SPLIT_GMM;
     if (nw == 8 && split != 50 && rpw >= 2 * TR) {
         long long cap = tuned_blocks < MAX_BLOCKS ? tuned_blocks : MAX_BLOCKS;
         long long pr = ((N + 4 * cap - 1) / (4 * cap) + 7) / 8 * 8;           // rows of a SIMD pair, all blocks in use
@@ -1562,7 +1583,7 @@ Plan make_plan(long long N, int D, int K, int flavour, bool stats, bool xdl = fa
     p.rpw = rpw;
     p.nw = nw;
     p.blocks = (int)blocks;
-    const int FTn = (1 + D + D * (D + 1) / 2 + 15) / 16, KTn = (K + 15) / 16;
+    const int FTn = (1 + D + D * (D + 1) / 2 + 15) / 16;
     const size_t scratch = stats ? (size_t)(KTn <= 2 ? KTn : 4) * (FTn + 1) * 4 * WAVE * sizeof(double) : 0;
     p.lds = wreg * nw;
     p.par_reduce = 0;
@@ -1575,65 +1596,50 @@ Plan make_plan(long long N, int D, int K, int flavour, bool stats, bool xdl = fa
     return p;
 }
 
-template <int D, int KT>
-int launch_pass_dk(const PassArgs& a, const Plan& p, int flavour, bool estep, bool stats, bool mask, hipStream_t s) {
-    dim3 grid(p.blocks), block(p.nw * WAVE);
-#define VMP_LAUNCH(FL, E, S, M) \
-    hipLaunchKernelGGL((pass_kernel<D, KT, FL, E, S, M>), grid, block, p.lds, s, a)
-    if (flavour == VMP_GMM) {
-        if (estep && stats) VMP_LAUNCH(VMP_GMM, true, true, false);
-        else if (estep && mask) VMP_LAUNCH(VMP_GMM, true, false, true);
-        else if (estep) VMP_LAUNCH(VMP_GMM, true, false, false);
-        else VMP_LAUNCH(VMP_GMM, false, true, false);
-    } else {
-        if (estep && stats) VMP_LAUNCH(VMP_SMM, true, true, false);
-        else if (estep) VMP_LAUNCH(VMP_SMM, true, false, false);
-        else VMP_LAUNCH(VMP_SMM, false, true, false);
-    }
-#undef VMP_LAUNCH
+// Rows of the per-block partial buffer that finalize_kernel reads: the block count of the pass that filled it.  INVARIANT: blocks
+// depends on (N, K, flavour) only - not on D, nor on which of the legal (estep, stats, mask) forms ran - so the M-pass plan answers for
+// every pass of that flavour (tests/test_mix_host_plan.py holds the plan to it).  A flavour that is not VMP_SMM reduces as the GMM.
+int partial_rows(long long N, int D, int K, int flavour) {
+    return pass_plan(N, D, K, flavour == VMP_SMM ? VMP_SMM : VMP_GMM, false, true, false).blocks;
+}
+
+template <int D, int KT, int FL, bool E, bool S, bool M>
+int launch_tiled(const PassArgs& a, const PassPlan& p, hipStream_t s) {
+    hipLaunchKernelGGL((pass_kernel<D, KT, FL, E, S, M>), dim3(p.blocks), dim3(p.nw * WAVE), p.lds, s, a);
     return check_launch("pass_kernel");
 }
 
-// E-part on the XDL pipe: E-step launches with K <= 16 and no missing-data mask
-inline bool use_xdl(int K, bool estep, bool mask) { return estep && !mask && K <= 16; }
-
-#ifndef VMP_MOM2_ROWS
-#define VMP_MOM2_ROWS (1ll << 16)      // rows from which the moment GEMM of the XDL pass multiplies 2-term operands (pass_xdl_body, MT)
-#endif
-template <int D>
-int launch_pass_xdl(const PassArgs& a, const Plan& p, int flavour, bool stats, hipStream_t s) {
-    dim3 grid(p.blocks), block(p.nw * WAVE);
-#define VMP_LAUNCH_X(FL, S, M) do { \
-        if (p.lds > 64 * 1024) { if (const int rc_ = set_dyn_lds(reinterpret_cast<const void*>(pass_xdl_kernel<D, FL, S, M>), p.lds, "pass_xdl_kernel")) return rc_; } \
-        hipLaunchKernelGGL((pass_xdl_kernel<D, FL, S, M>), grid, block, p.lds, s, a); } while (0)
-    const bool m2 = stats && a.N >= VMP_MOM2_ROWS;
-    if (flavour == VMP_GMM) { if (m2) VMP_LAUNCH_X(VMP_GMM, true, 2); else if (stats) VMP_LAUNCH_X(VMP_GMM, true, 3); else VMP_LAUNCH_X(VMP_GMM, false, 3); }
-    else { if (m2) VMP_LAUNCH_X(VMP_SMM, true, 2); else if (stats) VMP_LAUNCH_X(VMP_SMM, true, 3); else VMP_LAUNCH_X(VMP_SMM, false, 3); }
-#undef VMP_LAUNCH_X
+template <int D, int FL, bool S, int MT>
+int launch_xdl(const PassArgs& a, const PassPlan& p, hipStream_t s) {
+    if (p.lds > 64 * 1024) {
+        if (const int rc = set_dyn_lds(reinterpret_cast<const void*>(pass_xdl_kernel<D, FL, S, MT>), p.lds, "pass_xdl_kernel")) return rc;
+    }
+    hipLaunchKernelGGL((pass_xdl_kernel<D, FL, S, MT>), dim3(p.blocks), dim3(p.nw * WAVE), p.lds, s, a);
     return check_launch("pass_xdl_kernel");
 }
 
-template <int D>
-int launch_pass_d(const PassArgs& a, const Plan& p, int flavour, bool estep, bool stats, bool mask, hipStream_t s) {
-    if (use_xdl(a.K, estep, mask)) return launch_pass_xdl<D>(a, p, flavour, stats, s);
-    const int KT = (a.K + 15) / 16;
-    if (KT == 1) return launch_pass_dk<D, 1>(a, p, flavour, estep, stats, mask, s);
-    if (KT == 2) return launch_pass_dk<D, 2>(a, p, flavour, estep, stats, mask, s);
-    return launch_pass_dk<D, 4>(a, p, flavour, estep, stats, mask, s);
+template <int D, int KT, int FL>
+int launch_tiled_form(const PassArgs& a, const PassPlan& p, hipStream_t s) {
+    if (!p.estep) return launch_tiled<D, KT, FL, false, true, false>(a, p, s);
+    if (p.stats) return launch_tiled<D, KT, FL, true, true, false>(a, p, s);
+    if constexpr (FL == VMP_GMM) {
+        if (p.mask) return launch_tiled<D, KT, FL, true, false, true>(a, p, s);
+    }
+    return launch_tiled<D, KT, FL, true, false, false>(a, p, s);
 }
 
-#define VMP_DISPATCH_D(D, CALL)            \
-    switch (D) {                            \
-        case 1: { constexpr int DD = 1; CALL; } break; \
-        case 2: { constexpr int DD = 2; CALL; } break; \
-        case 3: { constexpr int DD = 3; CALL; } break; \
-        case 4: { constexpr int DD = 4; CALL; } break; \
-        case 5: { constexpr int DD = 5; CALL; } break; \
-        case 6: { constexpr int DD = 6; CALL; } break; \
-        case 7: { constexpr int DD = 7; CALL; } break; \
-        case 8: { constexpr int DD = 8; CALL; } break; \
-        default: break;                     \
+template <int D, int FL>
+int launch_pass(const PassArgs& a, const PassPlan& p, hipStream_t s) {
+    if (p.form == PASS_XDL) {
+        if (!p.stats) return launch_xdl<D, FL, false, 3>(a, p, s);
+        return p.kt_mt == 2 ? launch_xdl<D, FL, true, 2>(a, p, s) : launch_xdl<D, FL, true, 3>(a, p, s);
     }
+    switch (p.kt_mt) {
+        case 1: return launch_tiled_form<D, 1, FL>(a, p, s);
+        case 2: return launch_tiled_form<D, 2, FL>(a, p, s);
+        default: return launch_tiled_form<D, 4, FL>(a, p, s);
+    }
+}
 
 int check_dims(int64_t N, int D, int K) {
     if (N <= 0) { set_error("N must be positive (got %lld)", (long long)N); return VMP_E_BADARG; }
@@ -1642,14 +1648,16 @@ int check_dims(int64_t N, int D, int K) {
     return 0;
 }
 
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 #ifdef VMP_DEBUG_TS
 static long long* g_dbg_pass = nullptr;
 static long long* g_dbg_t = nullptr;
 #endif
-int run_pass(PassArgs a, int D, int flavour, bool estep, bool stats, bool mask, hipStream_t s) {
-    Plan p = make_plan(a.N, D, a.K, flavour, stats, use_xdl(a.K, estep, mask));
+int run_pass(PassArgs a, int D, int flavour, bool estep, bool stats, hipStream_t s) {
+    const PassPlan p = pass_plan(a.N, D, a.K, flavour, estep, stats, a.mask != nullptr);
+    if (p.form == PASS_NONE) {
+        set_error("mixture pass: no kernel for flavour %d, estep %d, stats %d, mask %d", flavour, (int)estep, (int)stats, (int)(a.mask != nullptr));
+        return VMP_E_BADARG;
+    }
     a.rpw = p.rpw;
     a.rpw_b = p.rpw_b;
     a.par_reduce = p.par_reduce;
@@ -1658,7 +1666,7 @@ int run_pass(PassArgs a, int D, int flavour, bool estep, bool stats, bool mask, 
 #endif
 
     int rc = -1;
-    VMP_DISPATCH_D(D, rc = launch_pass_d<DD>(a, p, flavour, estep, stats, mask, s));
+    VMP_SWITCH_DIM(D, DD, rc = flavour == VMP_SMM ? launch_pass<DD, VMP_SMM>(a, p, s) : launch_pass<DD, VMP_GMM>(a, p, s));
     return rc;
 }
 
@@ -1668,7 +1676,7 @@ int run_finalize(FinArgs f, int D, hipStream_t s) {
     f.dbg_t = g_dbg_t;
 #endif
 
-    VMP_DISPATCH_D(D, {
+    VMP_SWITCH_DIM(D, DD, {
         hipLaunchKernelGGL((finalize_kernel<DD>), dim3(f.K), dim3(FIN_THREADS), 0, s, f);
         rc = check_launch("finalize_kernel");
     });
@@ -1824,6 +1832,51 @@ constexpr size_t WS_TPACK_WORDS = 16 * (VMP_MAX_D + VMP_MAX_D * (VMP_MAX_D + 1) 
 inline size_t ws_partial_bytes(int D, int K) { return (size_t)MAX_BLOCKS * K * (partial_words(D) + 1) * sizeof(double); }
 inline unsigned long long* ws_seq(void* ws, int D, int K) { return reinterpret_cast<unsigned long long*>(static_cast<char*>(ws) + ws_partial_bytes(D, K)); }
 
+// this call seeds the workspace of an iteration loop: the reserved words and the status word start at zero
+int seed_ws(const char* who, void* ws, int D, int K, hipStream_t s) {
+    const hipError_t e = hipMemsetAsync(ws_seq(ws, D, K), 0, (WS_TPACK_WORDS + 2) * sizeof(unsigned long long), s);
+    if (e != hipSuccess) { set_error("%s: hipMemsetAsync: %s", who, hipGetErrorString(e)); return (int)e; }
+    return 0;
+}
+
+// ---- argument builders: every entry point fills PassArgs and FinArgs through these ------------------------
+struct MPassIn { const float *r, *u; };                                                  // what an M-pass reads besides x
+struct EPassOut { const float* pack; const uint8_t* mask; float *r, *u, *logr; };        // what an E-pass reads and writes besides x
+PassArgs pass_args(const float* x, const float* pivot, int64_t N, int K, void* ws, MPassIn in, EPassOut out) {
+    PassArgs a{};
+    a.x = x; a.pivot = pivot; a.N = N; a.K = K; a.partials = static_cast<double*>(ws);
+    a.r_in = in.r; a.u_in = in.u;
+    a.pack = out.pack; a.mask = out.mask; a.r_out = out.r; a.u_out = out.u; a.logr_out = out.logr;
+    a.vec_ok = aligned16(x) && aligned16(in.r) && aligned16(in.u) && aligned16(out.r) && aligned16(out.u) && aligned16(out.logr);   // (NULL is aligned)
+    return a;
+}
+
+struct Prior { const float *alpha0, *beta0, *m0, *C0, *v0, *kappa; };
+struct Posterior { float *alpha, *beta, *m, *C, *v, *xbar, *S, *pi, *pack; };
+int check_prior(const char* who, int flavour, const Prior& p) {
+    if (!p.alpha0 || !p.beta0 || !p.m0 || !p.C0 || !p.v0) { set_error("%s: null pointer", who); return VMP_E_BADARG; }
+    if (flavour == VMP_SMM && !p.kappa) { set_error("%s: SMM needs kappa", who); return VMP_E_BADARG; }
+    return 0;
+}
+// the posterior update of finalize_kernel; no posterior output at all: reduction only (stats_out)
+FinArgs fin_args(int K, int flavour, const Prior& pr, const Posterior& po) {
+    FinArgs f{};
+    f.K = K; f.flavour = flavour;
+    f.do_post = (po.alpha || po.beta || po.m || po.C || po.v || po.xbar || po.S || po.pi || po.pack) ? 1 : 0;
+    f.alpha0 = pr.alpha0; f.beta0 = pr.beta0; f.m0 = pr.m0; f.C0 = pr.C0; f.v0 = pr.v0; f.kappa = pr.kappa;
+    f.alpha = po.alpha; f.beta = po.beta; f.m = po.m; f.C = po.C; f.v = po.v; f.xbar = po.xbar; f.S = po.S; f.pi = po.pi; f.pack = po.pack;
+    return f;
+}
+// ... from the partials a pass of (N, D, K, flavour) left in the workspace (src = 0); the callers add pack64 or the peer table
+FinArgs fin_from_ws(const void* ws, const float* pivot, int64_t N, int D, int K, int flavour, const Prior& pr, const Posterior& po,
+                    double* stats_out) {
+    FinArgs f = fin_args(K, flavour, pr, po);
+    f.partials = static_cast<const double*>(ws);
+    f.nblk = partial_rows(N, D, K, flavour);
+    f.src = 0; f.stats_out = stats_out; f.pivot = pivot;
+    return f;
+}
+
 }  // namespace
 
 // =========================================================================================================
@@ -1854,6 +1907,17 @@ int vmp_mix_pivot(const float* x, int64_t N, int D, float* pivot_out, void* stre
     return check_launch("pivot_kernel");
 }
 
+int vmp_mix_pass_plan(int64_t N, int D, int K, int flavour, int estep, int stats, int mask, int64_t out[8]) {
+    if (!out) { set_error("vmp_mix_pass_plan: null pointer"); return VMP_E_BADARG; }
+    for (int i = 0; i < 8; ++i) out[i] = 0;
+    const int rc = check_dims(N, D, K);
+    if (rc) return rc;
+    const PassPlan p = pass_plan(N, D, K, flavour, estep != 0, stats != 0, mask != 0);
+    if (p.form == PASS_NONE) { set_error("vmp_mix_pass_plan: no kernel for flavour %d, estep %d, stats %d, mask %d", flavour, estep, stats, mask); return VMP_E_BADARG; }
+    out[0] = p.form; out[1] = p.kt_mt; out[2] = p.nw; out[3] = p.blocks; out[4] = p.rpw; out[5] = p.rpw_b; out[6] = p.par_reduce; out[7] = (int64_t)p.lds;
+    return 0;
+}
+
 int vmp_mix_stats(const float* x, const float* r, const float* u, const float* pivot, int64_t N, int D, int K,
                   double* stats, void* ws, size_t ws_bytes, void* stream) {
     int rc = check_dims(N, D, K);
@@ -1867,15 +1931,9 @@ int vmp_mix_stats(const float* x, const float* r, const float* u, const float* p
         return check_launch("small_stats_kernel");
     }
     const int flavour = u ? VMP_SMM : VMP_GMM;
-    PassArgs a{};
-    a.x = x; a.r_in = r; a.u_in = u; a.pivot = pivot; a.N = N; a.K = K; a.partials = static_cast<double*>(ws);
-    a.vec_ok = aligned16(x) && aligned16(r) && (!u || aligned16(u));
-    rc = run_pass(a, D, flavour, false, true, false, s);
+    rc = run_pass(pass_args(x, pivot, N, K, ws, {r, u}, {}), D, flavour, false, true, s);
     if (rc) return rc;
-    FinArgs f{};
-    f.partials = a.partials; f.nblk = make_plan(N, D, K, flavour, true).blocks; f.K = K; f.flavour = flavour;
-    f.src = 0; f.do_post = 0; f.stats_out = stats; f.pivot = pivot;
-    return run_finalize(f, D, s);
+    return run_finalize(fin_from_ws(ws, pivot, N, D, K, flavour, {}, {}, stats), D, s);
 }
 
 int vmp_mix_finalize(const double* stats, int D, int K, int flavour, const float* alpha0, const float* beta0,
@@ -1883,12 +1941,11 @@ int vmp_mix_finalize(const double* stats, int D, int K, int flavour, const float
                      float* m, float* C, float* v, float* xbar, float* S, float* pi, float* pack, void* stream) {
     int rc = check_dims(1, D, K);
     if (rc) return rc;
-    if (!stats || !alpha0 || !beta0 || !m0 || !C0 || !v0) { set_error("vmp_mix_finalize: null pointer"); return VMP_E_BADARG; }
-    if (flavour == VMP_SMM && !kappa) { set_error("vmp_mix_finalize: SMM needs kappa"); return VMP_E_BADARG; }
-    FinArgs f{};
-    f.stats_in = stats; f.nblk = 0; f.K = K; f.flavour = flavour; f.src = 1; f.do_post = 1;
-    f.alpha0 = alpha0; f.beta0 = beta0; f.m0 = m0; f.C0 = C0; f.v0 = v0; f.kappa = kappa;
-    f.alpha = alpha; f.beta = beta; f.m = m; f.C = C; f.v = v; f.xbar = xbar; f.S = S; f.pi = pi; f.pack = pack;
+    const Prior pr{alpha0, beta0, m0, C0, v0, kappa};
+    if (!stats) { set_error("vmp_mix_finalize: null pointer"); return VMP_E_BADARG; }
+    if ((rc = check_prior("vmp_mix_finalize", flavour, pr)) != 0) return rc;
+    FinArgs f = fin_args(K, flavour, pr, {alpha, beta, m, C, v, xbar, S, pi, pack});
+    f.stats_in = stats; f.src = 1; f.do_post = 1;
     return run_finalize(f, D, static_cast<hipStream_t>(stream));
 }
 
@@ -1901,7 +1958,7 @@ int vmp_mix_pack_from_params(int D, int K, int flavour, const float* alpha, cons
     PackArgs a{K, flavour, alpha, beta, m, P, v, kappa, pack, pi};
     hipStream_t s = static_cast<hipStream_t>(stream);
     rc = -1;
-    VMP_DISPATCH_D(D, {
+    VMP_SWITCH_DIM(D, DD, {
         hipLaunchKernelGGL((pack_kernel<DD>), dim3((K + 63) / 64), dim3(64), 0, s, a);
         rc = check_launch("pack_kernel");
     });
@@ -1925,16 +1982,10 @@ int vmp_mix_estep(const float* x, int64_t N, int D, int K, int flavour, const fl
         return VMP_E_WS;
     }
     hipStream_t s = static_cast<hipStream_t>(stream);
-    PassArgs a{};
-    a.x = x; a.mask = miss_mask; a.pack = pack; a.r_out = r_out; a.u_out = u_out; a.logr_out = logr_out;
-    a.pivot = pivot; a.N = N; a.K = K; a.partials = static_cast<double*>(ws);
-    a.vec_ok = aligned16(x) && aligned16(r_out) && (!u_out || aligned16(u_out)) && (!logr_out || aligned16(logr_out));
-    rc = run_pass(a, D, flavour, true, stats_out != nullptr, miss_mask != nullptr, s);
+    // with stats_out: the fused pass of vmp_mix_estep_fused, then the reduction-only finalize of vmp_mix_finalize_ws
+    rc = run_pass(pass_args(x, pivot, N, K, ws, {}, {pack, miss_mask, r_out, u_out, logr_out}), D, flavour, true, stats_out != nullptr, s);
     if (rc || !stats_out) return rc;
-    FinArgs f{};
-    f.partials = a.partials; f.nblk = make_plan(N, D, K, flavour, true).blocks; f.K = K; f.flavour = flavour;
-    f.src = 0; f.do_post = 0; f.stats_out = stats_out; f.pivot = pivot;
-    return run_finalize(f, D, s);
+    return run_finalize(fin_from_ws(ws, pivot, N, D, K, flavour, {}, {}, stats_out), D, s);
 }
 
 int vmp_mix_estep_fused(const float* x, int64_t N, int D, int K, int flavour, const float* pack, float* r_out,
@@ -1945,11 +1996,8 @@ int vmp_mix_estep_fused(const float* x, int64_t N, int D, int K, int flavour, co
     if (flavour != VMP_GMM && flavour != VMP_SMM) { set_error("vmp_mix_estep_fused: bad flavour %d", flavour); return VMP_E_BADARG; }
     if (flavour == VMP_SMM && !u_out) { set_error("vmp_mix_estep_fused: SMM needs u_out"); return VMP_E_BADARG; }
     if (ws_bytes < vmp_mix_workspace_bytes(N, D, K)) { set_error("vmp_mix_estep_fused: workspace too small"); return VMP_E_WS; }
-    PassArgs a{};
-    a.x = x; a.pack = pack; a.r_out = r_out; a.u_out = u_out; a.logr_out = logr_out; a.pivot = pivot;
-    a.N = N; a.K = K; a.partials = static_cast<double*>(ws);
-    a.vec_ok = aligned16(x) && aligned16(r_out) && (!u_out || aligned16(u_out)) && (!logr_out || aligned16(logr_out));
-    return run_pass(a, D, flavour, true, true, false, static_cast<hipStream_t>(stream));
+    return run_pass(pass_args(x, pivot, N, K, ws, {}, {pack, nullptr, r_out, u_out, logr_out}), D, flavour, true, true,
+                    static_cast<hipStream_t>(stream));
 }
 
 int vmp_mix_stats_ws(const float* x, const float* r, const float* u, const float* pivot, int64_t N, int D, int K,
@@ -1958,13 +2006,9 @@ int vmp_mix_stats_ws(const float* x, const float* r, const float* u, const float
     if (rc) return rc;
     if (!x || !r || !ws) { set_error("vmp_mix_stats_ws: null pointer"); return VMP_E_BADARG; }
     if (ws_bytes < vmp_mix_workspace_bytes(N, D, K)) { set_error("vmp_mix_stats_ws: workspace too small"); return VMP_E_WS; }
-    PassArgs a{};
-    a.x = x; a.r_in = r; a.u_in = u; a.pivot = pivot; a.N = N; a.K = K; a.partials = static_cast<double*>(ws);
-    a.vec_ok = aligned16(x) && aligned16(r) && (!u || aligned16(u));
-    // this call seeds the workspace of an iteration loop: the reserved words and the status word start at zero
-    hipError_t e = hipMemsetAsync(ws_seq(ws, D, K), 0, (WS_TPACK_WORDS + 2) * sizeof(unsigned long long), static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) { set_error("vmp_mix_stats_ws: hipMemsetAsync: %s", hipGetErrorString(e)); return (int)e; }
-    return run_pass(a, D, u ? VMP_SMM : VMP_GMM, false, true, false, static_cast<hipStream_t>(stream));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if ((rc = seed_ws("vmp_mix_stats_ws", ws, D, K, s)) != 0) return rc;
+    return run_pass(pass_args(x, pivot, N, K, ws, {r, u}, {}), D, u ? VMP_SMM : VMP_GMM, false, true, s);
 }
 
 int vmp_mix_stats_ws_accurate(const float* x, const float* r, const float* u, const float* pivot, int64_t N, int D, int K,
@@ -1973,15 +2017,13 @@ int vmp_mix_stats_ws_accurate(const float* x, const float* r, const float* u, co
     if (rc) return rc;
     if (!x || !r || !ws) { set_error("vmp_mix_stats_ws_accurate: null pointer"); return VMP_E_BADARG; }
     if (ws_bytes < vmp_mix_workspace_bytes(N, D, K)) { set_error("vmp_mix_stats_ws_accurate: workspace too small"); return VMP_E_WS; }
-    // the block count finalize_kernel will read (vmp_mix_finalize_ws / _ws64 derive it from the same plan)
-    const int blocks = make_plan(N, D, K, u ? VMP_SMM : VMP_GMM, true).blocks;
+    const int blocks = partial_rows(N, D, K, u ? VMP_SMM : VMP_GMM);          // the rows finalize_kernel will read
     AccStatArgs a{x, r, u, pivot, static_cast<double*>(ws), N, (N + blocks - 1) / blocks, K};
     const size_t lds = (size_t)ACC_RS * (D + 1 + 2 * K) * sizeof(float);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    hipError_t e = hipMemsetAsync(ws_seq(ws, D, K), 0, (WS_TPACK_WORDS + 2) * sizeof(unsigned long long), s);
-    if (e != hipSuccess) { set_error("vmp_mix_stats_ws_accurate: hipMemsetAsync: %s", hipGetErrorString(e)); return (int)e; }
+    if ((rc = seed_ws("vmp_mix_stats_ws_accurate", ws, D, K, s)) != 0) return rc;
     rc = -1;
-    VMP_DISPATCH_D(D, {
+    VMP_SWITCH_DIM(D, DD, {
         if (lds > 48 * 1024) { if ((rc = set_dyn_lds(reinterpret_cast<const void*>(stats_f64_kernel<DD>), lds, "stats_f64_kernel")) != 0) return rc; }
         hipLaunchKernelGGL((stats_f64_kernel<DD>), dim3(blocks), dim3(ACC_THREADS), lds, s, a);
         rc = check_launch("stats_f64_kernel");
@@ -1996,17 +2038,11 @@ int vmp_mix_finalize_exchange(const void* ws, const float* pivot, int64_t N, int
                               unsigned long long iteration, int* status, void* stream) {
     int rc = check_dims(N, D, K);
     if (rc) return rc;
-    if (!ws || !alpha0 || !beta0 || !m0 || !C0 || !v0 || !peers) { set_error("vmp_mix_finalize_exchange: null pointer"); return VMP_E_BADARG; }
+    const Prior pr{alpha0, beta0, m0, C0, v0, kappa};
+    if (!ws || !peers) { set_error("vmp_mix_finalize_exchange: null pointer"); return VMP_E_BADARG; }
     if (nranks < 1 || nranks > VMP_EXCH_MAX_RANKS || rank < 0 || rank >= nranks) { set_error("vmp_mix_finalize_exchange: bad rank / nranks"); return VMP_E_BADARG; }
-    if (flavour == VMP_SMM && !kappa) { set_error("vmp_mix_finalize_exchange: SMM needs kappa"); return VMP_E_BADARG; }
-    FinArgs f{};
-    f.partials = static_cast<const double*>(ws);
-    f.nblk = make_plan(N, D, K, flavour, true).blocks;
-    f.K = K; f.flavour = flavour; f.src = 0;
-    f.do_post = (alpha || beta || m || C || v || xbar || S || pi || pack) ? 1 : 0;
-    f.alpha0 = alpha0; f.beta0 = beta0; f.m0 = m0; f.C0 = C0; f.v0 = v0; f.kappa = kappa;
-    f.alpha = alpha; f.beta = beta; f.m = m; f.C = C; f.v = v; f.xbar = xbar; f.S = S; f.pi = pi; f.pack = pack;
-    f.stats_out = stats_out; f.pivot = pivot;
+    if ((rc = check_prior("vmp_mix_finalize_exchange", flavour, pr)) != 0) return rc;
+    FinArgs f = fin_from_ws(ws, pivot, N, D, K, flavour, pr, {alpha, beta, m, C, v, xbar, S, pi, pack}, stats_out);
     for (int g = 0; g < nranks; ++g) {
         if (!peers[g]) { set_error("vmp_mix_finalize_exchange: peers[%d] is null", g); return VMP_E_BADARG; }
         f.peer[g] = static_cast<double*>(peers[g]);
@@ -2021,17 +2057,12 @@ int vmp_mix_finalize_ws(const void* ws, const float* pivot, int64_t N, int D, in
                         double* stats_out, void* stream) {
     int rc = check_dims(N, D, K);
     if (rc) return rc;
-    if (!ws || !alpha0 || !beta0 || !m0 || !C0 || !v0) { set_error("vmp_mix_finalize_ws: null pointer"); return VMP_E_BADARG; }
-    if (flavour == VMP_SMM && !kappa) { set_error("vmp_mix_finalize_ws: SMM needs kappa"); return VMP_E_BADARG; }
-    FinArgs f{};
-    f.partials = static_cast<const double*>(ws);
-    f.nblk = make_plan(N, D, K, flavour, true).blocks;
-    f.K = K; f.flavour = flavour; f.src = 0;
-    f.do_post = (alpha || beta || m || C || v || xbar || S || pi || pack) ? 1 : 0;   // stats_out only: reduction only
-    f.alpha0 = alpha0; f.beta0 = beta0; f.m0 = m0; f.C0 = C0; f.v0 = v0; f.kappa = kappa;
-    f.alpha = alpha; f.beta = beta; f.m = m; f.C = C; f.v = v; f.xbar = xbar; f.S = S; f.pi = pi; f.pack = pack;
-    f.stats_out = stats_out; f.pivot = pivot;
-    return run_finalize(f, D, static_cast<hipStream_t>(stream));
+    const Prior pr{alpha0, beta0, m0, C0, v0, kappa};
+    if (!ws) { set_error("vmp_mix_finalize_ws: null pointer"); return VMP_E_BADARG; }
+    if ((rc = check_prior("vmp_mix_finalize_ws", flavour, pr)) != 0) return rc;
+    // stats_out only: reduction only
+    return run_finalize(fin_from_ws(ws, pivot, N, D, K, flavour, pr, {alpha, beta, m, C, v, xbar, S, pi, pack}, stats_out), D,
+                        static_cast<hipStream_t>(stream));
 }
 
 int vmp_mix_finalize_ws64(const void* ws, const float* pivot, int64_t N, int D, int K, int flavour, const float* alpha0, const float* beta0,
@@ -2040,15 +2071,11 @@ int vmp_mix_finalize_ws64(const void* ws, const float* pivot, int64_t N, int D, 
                           double* stats_out, void* stream) {
     int rc = check_dims(N, D, K);
     if (rc) return rc;
-    if (!ws || !alpha0 || !beta0 || !m0 || !C0 || !v0 || !pack || !pack64) { set_error("vmp_mix_finalize_ws64: null pointer"); return VMP_E_BADARG; }
-    if (flavour == VMP_SMM && !kappa) { set_error("vmp_mix_finalize_ws64: SMM needs kappa"); return VMP_E_BADARG; }
-    FinArgs f{};
-    f.partials = static_cast<const double*>(ws);
-    f.nblk = make_plan(N, D, K, flavour, true).blocks;
-    f.K = K; f.flavour = flavour; f.src = 0; f.do_post = 1;
-    f.alpha0 = alpha0; f.beta0 = beta0; f.m0 = m0; f.C0 = C0; f.v0 = v0; f.kappa = kappa;
-    f.alpha = alpha; f.beta = beta; f.m = m; f.C = C; f.v = v; f.xbar = xbar; f.S = S; f.pi = pi; f.pack = pack; f.pack64 = pack64;
-    f.stats_out = stats_out; f.pivot = pivot;
+    const Prior pr{alpha0, beta0, m0, C0, v0, kappa};
+    if (!ws || !pack || !pack64) { set_error("vmp_mix_finalize_ws64: null pointer"); return VMP_E_BADARG; }
+    if ((rc = check_prior("vmp_mix_finalize_ws64", flavour, pr)) != 0) return rc;
+    FinArgs f = fin_from_ws(ws, pivot, N, D, K, flavour, pr, {alpha, beta, m, C, v, xbar, S, pi, pack}, stats_out);
+    f.pack64 = pack64;
     return run_finalize(f, D, static_cast<hipStream_t>(stream));
 }
 
@@ -2064,7 +2091,7 @@ int vmp_mix_estep_accurate(const float* x, int64_t N, int D, int K, int flavour,
     if (blocks > 2048) blocks = 2048;
     const size_t lds = (size_t)K * pack_words(D) * sizeof(double);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    VMP_DISPATCH_D(D, {
+    VMP_SWITCH_DIM(D, DD, {
         if (flavour == VMP_SMM) hipLaunchKernelGGL((estep_f64_kernel<DD, true>), dim3((int)blocks), dim3(256), lds, s, a);
         else hipLaunchKernelGGL((estep_f64_kernel<DD, false>), dim3((int)blocks), dim3(256), lds, s, a);
     });

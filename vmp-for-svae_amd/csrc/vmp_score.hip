@@ -255,19 +255,6 @@ int score_dims(const char* who, int D, int K) {
     return 0;
 }
 
-#define VMP_SCORE_DISPATCH_D(D, CALL)      \
-    switch (D) {                            \
-        case 1: { constexpr int DD = 1; CALL; } break; \
-        case 2: { constexpr int DD = 2; CALL; } break; \
-        case 3: { constexpr int DD = 3; CALL; } break; \
-        case 4: { constexpr int DD = 4; CALL; } break; \
-        case 5: { constexpr int DD = 5; CALL; } break; \
-        case 6: { constexpr int DD = 6; CALL; } break; \
-        case 7: { constexpr int DD = 7; CALL; } break; \
-        case 8: { constexpr int DD = 8; CALL; } break; \
-        default: break;                     \
-    }
-
 template <int D>
 int launch_score(const ScoreArgs& a, int blocks, hipStream_t s) {
     const dim3 grid(blocks), block(SCORE_NW * WAVE);
@@ -291,7 +278,7 @@ int vmp_mix_score_pack_niw(int D, int K, const float* alpha, const float* beta, 
     if (!alpha || !beta || !m || !C || !v || !pack) { set_error("vmp_mix_score_pack_niw: null pointer"); return VMP_E_BADARG; }
     ScorePackArgs a{K, alpha, beta, m, C, v, pack};
     rc = -1;
-    VMP_SCORE_DISPATCH_D(D, {
+    VMP_SWITCH_DIM(D, DD, {
         hipLaunchKernelGGL((score_pack_niw_kernel<DD>), dim3(1), dim3(64), 0, static_cast<hipStream_t>(stream), a);
         rc = check_launch("score_pack_niw_kernel");
     });
@@ -305,7 +292,7 @@ int vmp_mix_score_pack_t(int D, int K, const float* log_w, const float* mu, cons
     if (!log_w || !mu || !sigma || !nu || !pack) { set_error("vmp_mix_score_pack_t: null pointer"); return VMP_E_BADARG; }
     ScorePackArgs a{K, log_w, nullptr, mu, sigma, nu, pack};
     rc = -1;
-    VMP_SCORE_DISPATCH_D(D, {
+    VMP_SWITCH_DIM(D, DD, {
         hipLaunchKernelGGL((score_pack_t_kernel<DD>), dim3(1), dim3(64), 0, static_cast<hipStream_t>(stream), a);
         rc = check_launch("score_pack_t_kernel");
     });
@@ -337,9 +324,9 @@ int vmp_mix_score(const float* x, int64_t N, int D, int K, const float* pack, fl
     a.x = x; a.pack = pack; a.logp = logp_out; a.resp = resp_out; a.partials = sum_out ? static_cast<double*>(ws) : nullptr;
     a.N = N; a.K = K;
     a.rpw = ((N + waves - 1) / waves + 7) / 8 * 8;
-    a.vec_ok = (reinterpret_cast<uintptr_t>(x) & 15) == 0;
+    a.vec_ok = aligned16(x);
     rc = -1;
-    VMP_SCORE_DISPATCH_D(D, rc = launch_score<DD>(a, blocks, s));
+    VMP_SWITCH_DIM(D, DD, rc = launch_score<DD>(a, blocks, s));
     if (rc || !sum_out) return rc;
     hipLaunchKernelGGL(score_sum_kernel, dim3(1), dim3(WAVE), 0, s, a.partials, blocks, sum_out);
     return check_launch("score_sum_kernel");

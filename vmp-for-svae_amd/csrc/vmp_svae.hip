@@ -1937,21 +1937,6 @@ int sv_blocks(long long N, int K) {
     return (int)b;
 }
 
-bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
-#define VMP_DISPATCH_L(Lv, ...)            \
-    switch (Lv) {                           \
-        case 1: { constexpr int LL = 1; __VA_ARGS__; } break; \
-        case 2: { constexpr int LL = 2; __VA_ARGS__; } break; \
-        case 3: { constexpr int LL = 3; __VA_ARGS__; } break; \
-        case 4: { constexpr int LL = 4; __VA_ARGS__; } break; \
-        case 5: { constexpr int LL = 5; __VA_ARGS__; } break; \
-        case 6: { constexpr int LL = 6; __VA_ARGS__; } break; \
-        case 7: { constexpr int LL = 7; __VA_ARGS__; } break; \
-        case 8: { constexpr int LL = 8; __VA_ARGS__; } break; \
-        default: break;                     \
-    }
-
 // ---- launch plans.  Which kernel a shape runs, with what block, grid and LDS, is decided in two pure functions: fwd_plan and
 // bwd_plan.  Every launch and every size query of the ABI goes through them, so a buffer sized from a query and the launch that fills
 // it cannot disagree.
@@ -2144,7 +2129,7 @@ static int run_fwd(EFwdArgs a, int L, void* stream, bool rng, bool fwd1_ok = tru
 #ifdef VMP_DEBUG_TS
     a.dbg_t = g_dbg_svae;
 #endif
-    const FwdPlan p = fwd_plan(a.N, a.K, L, a.S, rng, al16(a.noise), a.mom != nullptr, fwd1_ok);
+    const FwdPlan p = fwd_plan(a.N, a.K, L, a.S, rng, aligned16(a.noise), a.mom != nullptr, fwd1_ok);
     const bool s10 = a.S == 10;                             // the compiled-in sample count (ST = 10; ST = 0: S at run time)
     int rc = -1;
     switch (p.form) {
@@ -2153,7 +2138,7 @@ static int run_fwd(EFwdArgs a, int L, void* stream, bool rng, bool fwd1_ok = tru
             else set_error("in-kernel noise covers L = 8, and L < 8 with L*S %% 4 == 0 tiles that fit the LDS (L=%d, S=%d)", L, a.S);
             return VMP_E_DIM;
         case FwdForm::fwd1:
-            VMP_DISPATCH_L(L, {
+            VMP_SWITCH_DIM(L, LL, {
                 hipLaunchKernelGGL((svae_estep_fwd1_kernel<LL>), dim3(p.grid), dim3(p.nw * WAVE), 0, static_cast<hipStream_t>(stream), a);
                 rc = check_launch("svae_estep_fwd1_kernel");
             });
@@ -2162,18 +2147,18 @@ static int run_fwd(EFwdArgs a, int L, void* stream, bool rng, bool fwd1_ok = tru
         case FwdForm::pst2:
             return s10 ? launch_fwd4<8, 10, true, true>(a, p, stream) : launch_fwd4<8, 0, true, true>(a, p, stream);
         case FwdForm::tile:
-            if (rng) { VMP_DISPATCH_L(L, rc = s10 ? launch_fwd4<LL, 10, true, false>(a, p, stream) : launch_fwd4<LL, 0, true, false>(a, p, stream)); }
-            else { VMP_DISPATCH_L(L, rc = s10 ? launch_fwd4<LL, 10, false, false>(a, p, stream) : launch_fwd4<LL, 0, false, false>(a, p, stream)); }
+            if (rng) { VMP_SWITCH_DIM(L, LL, rc = s10 ? launch_fwd4<LL, 10, true, false>(a, p, stream) : launch_fwd4<LL, 0, true, false>(a, p, stream)); }
+            else { VMP_SWITCH_DIM(L, LL, rc = s10 ? launch_fwd4<LL, 10, false, false>(a, p, stream) : launch_fwd4<LL, 0, false, false>(a, p, stream)); }
             return rc;
         case FwdForm::chunked:
-            VMP_DISPATCH_L(L, {
+            VMP_SWITCH_DIM(L, LL, {
                 if ((rc = set_dyn_lds(reinterpret_cast<const void*>(svae_estep_fwd_chunked_kernel<LL>), p.lds, "svae_estep_fwd")) != 0) return rc;
                 hipLaunchKernelGGL((svae_estep_fwd_chunked_kernel<LL>), dim3(p.grid), dim3(p.nw * WAVE), p.lds, static_cast<hipStream_t>(stream), a, p.cs);
                 rc = check_launch("svae_estep_fwd_chunked_kernel");
             });
             return rc;
         case FwdForm::fwd3:
-            VMP_DISPATCH_L(L, rc = s10 ? launch_fwd3<LL, 10>(a, p, stream) : launch_fwd3<LL, 0>(a, p, stream));
+            VMP_SWITCH_DIM(L, LL, rc = s10 ? launch_fwd3<LL, 10>(a, p, stream) : launch_fwd3<LL, 0>(a, p, stream));
             return rc;
     }
     return rc;
@@ -2201,7 +2186,7 @@ static int fwd_begin(const char* who, const float* eta1, const float* eta2d, con
         set_error("%s: null pointer", who);
         return VMP_E_BADARG;
     }
-    a = EFwdArgs{eta1, eta2d, hk, Pk, bias, nullptr, mk, Wk, kappa, nu, x, lz, Tp, N, K, S, al16(x), 0ull};
+    a = EFwdArgs{eta1, eta2d, hk, Pk, bias, nullptr, mk, Wk, kappa, nu, x, lz, Tp, N, K, S, aligned16(x), 0ull};
     return 0;
 }
 static int fwd_need_in_kernel(const char* who, int K, int L, int S) {
@@ -2216,7 +2201,7 @@ int vmp_svae_estep_fwd(const float* eta1, const float* eta2d, const float* hk, c
     EFwdArgs a;
     if (const int rc = fwd_begin("vmp_svae_estep_fwd", eta1, eta2d, hk, Pk, bias, mk, Wk, kappa, nu, N, K, L, S, x, lz, Tp, noise != nullptr, a)) return rc;
     a.noise = noise;
-    a.vec_ok = al16(noise) && al16(x);
+    a.vec_ok = aligned16(noise) && aligned16(x);
     return run_fwd(a, L, stream, false);
 }
 
@@ -2255,7 +2240,7 @@ static int run_fwd_seeded(const char* who, EFwdArgs a, int L, float* noise_ws, b
     if (!noise_ws) { set_error("%s: this shape needs the (N,K,L,S) noise workspace", who); return VMP_E_WS; }
     if (const int rc = philox_noise_impl(a.seed, nullptr, a.N, a.K, L, a.S, noise_ws, stream, a.row0)) return rc;
     a.noise = noise_ws;
-    a.vec_ok = al16(noise_ws) && al16(a.x);
+    a.vec_ok = aligned16(noise_ws) && aligned16(a.x);
     return run_fwd(a, L, stream, false);
 }
 
@@ -2380,7 +2365,7 @@ int vmp_svae_estep_bwd_n(const float* eta1, const float* eta2d, const float* hk,
         return VMP_E_BADARG;
     }
     EBwdArgs a{eta1, eta2d, hk, Pk, bias, mk, Wk, nu, x, lz, Gx, Glz, GT, g_eta1, g_eta2d, partials, N, K, S, 0};
-    a.vec_ok = al16(x) && al16(Gx);
+    a.vec_ok = aligned16(x) && aligned16(Gx);
 #ifdef VMP_DEBUG_TS
     a.dbg_t = g_dbg_svae;
 #endif
@@ -2397,7 +2382,7 @@ int vmp_svae_estep_bwd_n(const float* eta1, const float* eta2d, const float* hk,
     const int PWa = nu ? PW : PW / 2;
     const size_t lds = (size_t)(K * ((L * (L + 1) / 2) | 1) + SV_NW * WAVE + SV_NW * 2 * L * SV_AST + SV_NW * PWa * SV_AST) * sizeof(float);
     rc = -1;
-    VMP_DISPATCH_L(L, {
+    VMP_SWITCH_DIM(L, LL, {
         if (p.form == BwdForm::generic_one) hipLaunchKernelGGL((svae_estep_bwd_kernel<LL, true>), dim3(p.blocks), dim3(SV_NW * WAVE), lds, static_cast<hipStream_t>(stream), a);
         else hipLaunchKernelGGL((svae_estep_bwd_kernel<LL, false>), dim3(p.blocks), dim3(SV_NW * WAVE), lds, static_cast<hipStream_t>(stream), a);
         rc = check_launch("svae_estep_bwd_kernel");

@@ -62,23 +62,33 @@ def _prior(prior, K, D, dev):
             L.dev_f32(v0.to(dev, torch.float32), 'v_0', (K,)))
 
 
+_POST = ('alpha', 'beta', 'm', 'C', 'v', 'xbar', 'S', 'pi', 'pack')      # the posterior outputs, in the order of the C ABI
+
+
+def _post_buffers(K, D, device, want_pack=True):
+    f32 = dict(dtype=torch.float32, device=device)
+    return dict(alpha=torch.empty(K, **f32), beta=torch.empty(K, **f32), m=torch.empty(K, D, **f32),
+                C=torch.empty(K, D, D, **f32), v=torch.empty(K, **f32), xbar=torch.empty(K, D, **f32),
+                S=torch.empty(K, D, D, **f32), pi=torch.empty(K, **f32),
+                pack=torch.empty(K, L.lib().vmp_mix_pack_words(D), **f32) if want_pack else None)
+
+
+def _fin_tail(D, K, flavour, prior, kappa, post):
+    """(D, K, flavour, prior x 5, kappa, posterior x 9): what every finalize entry point takes behind its source (post=None: no
+    posterior output, the reduction-only form)"""
+    return ([D, K, flavour] + [L.ptr(t) for t in prior] + [L.ptr(kappa)]
+            + [L.ptr(post[k]) if post is not None else None for k in _POST])
+
+
 def finalize(stats, prior, flavour, kappa=None, want_pack=True):
     """Posterior (alpha, beta, m, C, v, xbar, S, pi) and the E-step pack from raw stats (vmp_mix_finalize)."""
     K = stats.shape[0]
     dev = stats.device
     D = prior[2].shape[1]
-    a0, b0, m0, C0, v0 = _prior(prior, K, D, dev)
-    f32 = dict(dtype=torch.float32, device=dev)
-    out = dict(alpha=torch.empty(K, **f32), beta=torch.empty(K, **f32), m=torch.empty(K, D, **f32),
-               C=torch.empty(K, D, D, **f32), v=torch.empty(K, **f32), xbar=torch.empty(K, D, **f32),
-               S=torch.empty(K, D, D, **f32), pi=torch.empty(K, **f32))
-    pack = torch.empty(K, L.lib().vmp_mix_pack_words(D), **f32) if want_pack else None
+    out = _post_buffers(K, D, dev, want_pack)
     kap = None if kappa is None else L.dev_f32(kappa.to(dev, torch.float32), 'kappa', (K,))
-    L.check(L.lib().vmp_mix_finalize(L.ptr(stats), D, K, flavour, L.ptr(a0), L.ptr(b0), L.ptr(m0), L.ptr(C0), L.ptr(v0),
-                                     L.ptr(kap), L.ptr(out['alpha']), L.ptr(out['beta']), L.ptr(out['m']),
-                                     L.ptr(out['C']), L.ptr(out['v']), L.ptr(out['xbar']), L.ptr(out['S']),
-                                     L.ptr(out['pi']), L.ptr(pack), L.stream()), 'vmp_mix_finalize')
-    out['pack'] = pack
+    L.check(L.lib().vmp_mix_finalize(L.ptr(stats), *_fin_tail(D, K, flavour, _prior(prior, K, D, dev), kap, out), L.stream()),
+            'vmp_mix_finalize')
     return out
 
 
@@ -223,12 +233,8 @@ class VMPLoop(object):
         self.u = None
         if flavour == L.VMP_SMM:
             self.u = (torch.ones_like(self.r) if u_init is None else L.dev_f32(u_init, 'u_nk', (self.N, K)).clone())
-        f32 = dict(dtype=torch.float32, device=dev)
         D = self.D
-        self.post = dict(alpha=torch.empty(K, **f32), beta=torch.empty(K, **f32), m=torch.empty(K, D, **f32),
-                         C=torch.empty(K, D, D, **f32), v=torch.empty(K, **f32), xbar=torch.empty(K, D, **f32),
-                         S=torch.empty(K, D, D, **f32), pi=torch.empty(K, **f32),
-                         pack=torch.empty(K, L.lib().vmp_mix_pack_words(D), **f32))
+        self.post = _post_buffers(K, D, dev)
         self.logr = None
         self.nb = L.lib().vmp_mix_workspace_bytes(self.N, D, K)
         self.ws = torch.empty(self.nb, dtype=torch.uint8, device=dev)      # private: partials live across calls
@@ -240,20 +246,17 @@ class VMPLoop(object):
         self.iterations = 0
         self.pack64 = torch.empty(K, L.lib().vmp_mix_pack_words(D), dtype=torch.float64, device=dev) if self.accurate else None
 
+    def _fin_ptrs(self, post=True):
+        """(ws, pivot, N, D, K, flavour, prior x 5, kappa, posterior x 9): the leading arguments of vmp_mix_finalize_ws / _ws64 /
+        _exchange; post=False: no posterior output (the reduction-only form).  [3:] is what vmp_mix_finalize takes behind its stats."""
+        return [L.ptr(self.ws), L.ptr(self.pivot), self.N] + _fin_tail(self.D, self.K, self.flavour, self.prior, self.kappa,
+                                                                      self.post if post else None)
+
     def finalize(self, stats_out=None):
-        p, pr = self.post, self.prior
         if self.accurate:
-            L.check(L.lib().vmp_mix_finalize_ws64(L.ptr(self.ws), L.ptr(self.pivot), self.N, self.D, self.K, self.flavour, L.ptr(pr[0]),
-                                                  L.ptr(pr[1]), L.ptr(pr[2]), L.ptr(pr[3]), L.ptr(pr[4]), L.ptr(self.kappa),
-                                                  L.ptr(p['alpha']), L.ptr(p['beta']), L.ptr(p['m']), L.ptr(p['C']),
-                                                  L.ptr(p['v']), L.ptr(p['xbar']), L.ptr(p['S']), L.ptr(p['pi']),
-                                                  L.ptr(p['pack']), L.ptr(self.pack64), L.ptr(stats_out), L.stream()), 'vmp_mix_finalize_ws64')
+            L.check(L.lib().vmp_mix_finalize_ws64(*self._fin_ptrs(), L.ptr(self.pack64), L.ptr(stats_out), L.stream()), 'vmp_mix_finalize_ws64')
             return
-        L.check(L.lib().vmp_mix_finalize_ws(L.ptr(self.ws), L.ptr(self.pivot), self.N, self.D, self.K, self.flavour, L.ptr(pr[0]),
-                                            L.ptr(pr[1]), L.ptr(pr[2]), L.ptr(pr[3]), L.ptr(pr[4]), L.ptr(self.kappa),
-                                            L.ptr(p['alpha']), L.ptr(p['beta']), L.ptr(p['m']), L.ptr(p['C']),
-                                            L.ptr(p['v']), L.ptr(p['xbar']), L.ptr(p['S']), L.ptr(p['pi']),
-                                            L.ptr(p['pack']), L.ptr(stats_out), L.stream()), 'vmp_mix_finalize_ws')
+        L.check(L.lib().vmp_mix_finalize_ws(*self._fin_ptrs(), L.ptr(stats_out), L.stream()), 'vmp_mix_finalize_ws')
 
     def finalize_phase(self):
         """everything of an iteration that is not the streaming launch (bench.py brackets that launch with events): the finalize launch"""
@@ -289,13 +292,9 @@ class VMPLoop(object):
             for _ in range(int(iterations)):
                 self.step()
             return self.r
-        p, pr = self.post, self.prior
-        L.check(L.lib().vmp_mix_iterate(L.ptr(self.x), self.N, self.D, self.K, self.flavour, L.ptr(pr[0]), L.ptr(pr[1]),
-                                        L.ptr(pr[2]), L.ptr(pr[3]), L.ptr(pr[4]), L.ptr(self.kappa), L.ptr(self.pivot),
-                                        L.ptr(self.r), L.ptr(self.u), L.ptr(p['alpha']), L.ptr(p['beta']), L.ptr(p['m']),
-                                        L.ptr(p['C']), L.ptr(p['v']), L.ptr(p['xbar']), L.ptr(p['S']), L.ptr(p['pi']),
-                                        L.ptr(p['pack']), L.ptr(self.ws), self.nb, int(iterations), L.stream()),
-                'vmp_mix_iterate')
+        ws, pivot, *f = self._fin_ptrs()                       # f = N, D, K, flavour, prior x 5, kappa | posterior x 9
+        L.check(L.lib().vmp_mix_iterate(L.ptr(self.x), *f[:10], pivot, L.ptr(self.r), L.ptr(self.u), *f[10:], ws, self.nb,
+                                        int(iterations), L.stream()), 'vmp_mix_iterate')
         self.iterations += int(iterations)
         return self.r
 

@@ -82,35 +82,19 @@ class PeerExchange(object):
     arbitrary 64-byte payloads and may not assume a single call."""
 
     def __init__(self, K, D, group=None, rank=None, world=None, gather=None):
-        import ctypes
         import torch.distributed as dist
         self.world = dist.get_world_size(group) if world is None else int(world)
         self.rank = dist.get_rank(group) if rank is None else int(rank)
-        if not 1 <= self.world <= 16:
-            raise L.VmpError('PeerExchange supports 1..16 ranks')
         self.K, self.D = int(K), int(D)
-        nbytes = L.lib().vmp_exch_bytes(self.world, self.K, self.D)
-        buf = ctypes.c_void_p()
-        L.check(L.lib().vmp_exch_alloc(ctypes.byref(buf), nbytes), 'vmp_exch_alloc')
-        self._buf = buf
-        hb = ctypes.create_string_buffer(64)
-        L.check(L.lib().vmp_exch_export(buf, hb), 'vmp_exch_export')
+        self._peers, self._buf = [], None
+        raw = self._alloc_export()
         if gather is not None:
-            handles = gather(hb.raw)                      # caller-supplied all-gather of the 64-byte handles
+            handles = gather(raw)                         # caller-supplied all-gather of the 64-byte handles
         else:
             handles = [None] * self.world
-            dist.all_gather_object(handles, hb.raw, group=group)
-        self._peers = []
-        for g, h in enumerate(handles):
-            if g == self.rank:
-                self._peers.append(ctypes.c_void_p(buf.value))
-            else:
-                pp = ctypes.c_void_p()
-                L.check(L.lib().vmp_exch_open(ctypes.create_string_buffer(h, 64), ctypes.byref(pp)), 'vmp_exch_open')
-                self._peers.append(pp)
-        self.table = (ctypes.c_void_p * self.world)(*[p.value for p in self._peers])
-        self.iteration = 0
-        self.status = torch.zeros(1, dtype=torch.int32, device='cuda')
+            dist.all_gather_object(handles, raw, group=group)
+        self._map_peers(handles)
+        self._ready()
         # nobody may publish into a buffer a peer has not mapped yet, and the in-kernel wait is bounded (~4 s): without this
         # rendezvous a start skew between the ranks (data generation, uploads) could time a rank out before its peers arrive,
         # after which the sequence words never match again
@@ -127,7 +111,6 @@ class PeerExchange(object):
         """Collective and exception-free: EVERY rank gets an exchange, or every rank gets None (some rank could not allocate, export or
         map a buffer - the reason is in .last_failure of the class).  Each stage is followed by an exchange of success flags, so that a
         rank that fails never leaves its peers waiting in a rendezvous.  For callers that want to fall back to the all-reduce form."""
-        import ctypes
         import torch.distributed as dist
         self = cls.__new__(cls)
         self.world, self.rank = dist.get_world_size(group), dist.get_rank(group)
@@ -135,27 +118,14 @@ class PeerExchange(object):
         self._peers, self._buf, self._group, self._gather = [], None, group, None
         why, raw = '', b''
         try:
-            if not 1 <= self.world <= 16:
-                raise L.VmpError('PeerExchange supports 1..16 ranks')
-            buf = ctypes.c_void_p()
-            L.check(L.lib().vmp_exch_alloc(ctypes.byref(buf), L.lib().vmp_exch_bytes(self.world, self.K, self.D)), 'vmp_exch_alloc')
-            self._buf = buf
-            hb = ctypes.create_string_buffer(64)
-            L.check(L.lib().vmp_exch_export(buf, hb), 'vmp_exch_export')
-            raw = hb.raw
+            raw = self._alloc_export()
         except Exception as e:                               # noqa: BLE001 - reported through the flags
             why = 'rank %d: %r' % (self.rank, e)
         got = [None] * self.world
         dist.all_gather_object(got, (why, raw), group=group)
         if not any(w for w, _ in got):
             try:
-                for g, (_, h) in enumerate(got):
-                    if g == self.rank:
-                        self._peers.append(ctypes.c_void_p(self._buf.value))
-                    else:
-                        pp = ctypes.c_void_p()
-                        L.check(L.lib().vmp_exch_open(ctypes.create_string_buffer(h, 64), ctypes.byref(pp)), 'vmp_exch_open')
-                        self._peers.append(pp)
+                self._map_peers([h for _, h in got])
             except Exception as e:                           # noqa: BLE001
                 why = 'rank %d: %r' % (self.rank, e)
             # pad for close(): it walks the list by rank index
@@ -175,12 +145,40 @@ class PeerExchange(object):
                 L.lib().vmp_exch_free(self._buf)
                 self._buf = None
             return None
-        self.table = (ctypes.c_void_p * self.world)(*[p_.value for p_ in self._peers])
-        self.iteration = 0
-        self.status = torch.zeros(1, dtype=torch.int32, device='cuda')
+        self._ready()
         return self
 
     last_failure = ''
+
+    def _alloc_export(self):
+        """this rank's exchange buffer (self._buf) and the 64 bytes of its IPC handle"""
+        import ctypes
+        if not 1 <= self.world <= 16:
+            raise L.VmpError('PeerExchange supports 1..16 ranks')
+        buf = ctypes.c_void_p()
+        L.check(L.lib().vmp_exch_alloc(ctypes.byref(buf), L.lib().vmp_exch_bytes(self.world, self.K, self.D)), 'vmp_exch_alloc')
+        self._buf = buf
+        hb = ctypes.create_string_buffer(64)
+        L.check(L.lib().vmp_exch_export(buf, hb), 'vmp_exch_export')
+        return hb.raw
+
+    def _map_peers(self, handles):
+        """self._peers, by rank: this rank's own buffer, the peers' mapped through their handles (close() walks the list by rank)"""
+        import ctypes
+        for g, h in enumerate(handles):
+            if g == self.rank:
+                self._peers.append(ctypes.c_void_p(self._buf.value))
+            else:
+                pp = ctypes.c_void_p()
+                L.check(L.lib().vmp_exch_open(ctypes.create_string_buffer(h, 64), ctypes.byref(pp)), 'vmp_exch_open')
+                self._peers.append(pp)
+
+    def _ready(self):
+        """what vmp_mix_finalize_exchange takes: the peer table, the iteration count and the device status word"""
+        import ctypes
+        self.table = (ctypes.c_void_p * self.world)(*[p.value for p in self._peers])
+        self.iteration = 0
+        self.status = torch.zeros(1, dtype=torch.int32, device='cuda')
 
     def __enter__(self):
         return self
@@ -251,30 +249,18 @@ class DistributedVMPLoop(_mix.VMPLoop):
 
     def finalize(self, stats_out=None):
         if self.exchange is not None:
-            ex, p, pr = self.exchange, self.post, self.prior
-            L.check(L.lib().vmp_mix_finalize_exchange(
-                L.ptr(self.ws), L.ptr(self.pivot), self.N, self.D, self.K, self.flavour, L.ptr(pr[0]), L.ptr(pr[1]),
-                L.ptr(pr[2]), L.ptr(pr[3]), L.ptr(pr[4]), L.ptr(self.kappa), L.ptr(p['alpha']), L.ptr(p['beta']),
-                L.ptr(p['m']), L.ptr(p['C']), L.ptr(p['v']), L.ptr(p['xbar']), L.ptr(p['S']), L.ptr(p['pi']),
-                L.ptr(p['pack']), L.ptr(self._stats), ex.table, ex.world, ex.rank, ex.iteration, L.ptr(ex.status),
-                L.stream()), 'vmp_mix_finalize_exchange')
+            ex = self.exchange
+            L.check(L.lib().vmp_mix_finalize_exchange(*self._fin_ptrs(), L.ptr(self._stats), ex.table, ex.world, ex.rank, ex.iteration,
+                                                      L.ptr(ex.status), L.stream()), 'vmp_mix_finalize_exchange')
             ex.iteration += 1
             if stats_out is not None:
                 stats_out.copy_(self._stats)
             return
         # local reduction of the per-block partials -> (K, SW) fp64; sum over ranks; global posterior + pack
-        pr = self.prior
-        L.check(L.lib().vmp_mix_finalize_ws(L.ptr(self.ws), L.ptr(self.pivot), self.N, self.D, self.K, self.flavour,
-                                            L.ptr(pr[0]), L.ptr(pr[1]), L.ptr(pr[2]), L.ptr(pr[3]), L.ptr(pr[4]),
-                                            L.ptr(self.kappa), *([None] * 9), L.ptr(self._stats), L.stream()),
+        L.check(L.lib().vmp_mix_finalize_ws(*self._fin_ptrs(post=False), L.ptr(self._stats), L.stream()),
                 'vmp_mix_finalize_ws')                   # all outputs NULL: fixed-order reduction of the partials only
         allreduce_sum_(self._stats, self.group, self.comm)
-        p, pr = self.post, self.prior
-        L.check(L.lib().vmp_mix_finalize(L.ptr(self._stats), self.D, self.K, self.flavour, L.ptr(pr[0]), L.ptr(pr[1]),
-                                         L.ptr(pr[2]), L.ptr(pr[3]), L.ptr(pr[4]), L.ptr(self.kappa),
-                                         L.ptr(p['alpha']), L.ptr(p['beta']), L.ptr(p['m']), L.ptr(p['C']),
-                                         L.ptr(p['v']), L.ptr(p['xbar']), L.ptr(p['S']), L.ptr(p['pi']),
-                                         L.ptr(p['pack']), L.stream()), 'vmp_mix_finalize')
+        L.check(L.lib().vmp_mix_finalize(L.ptr(self._stats), *self._fin_ptrs()[3:], L.stream()), 'vmp_mix_finalize')
         if stats_out is not None:
             stats_out.copy_(self._stats)
 

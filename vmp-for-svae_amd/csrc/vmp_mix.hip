@@ -682,13 +682,6 @@ __device__ __forceinline__ void pass_xdl_body(const PassArgs& a) {
     // position of tile row t in a value-row of the fp32 image: the 4 rows {g, 4+g, 8+g, 12+g} of a 16-row sub-tile that one
     // lane group owns are adjacent (one ds_read_b128 per feature factor)
     const int ppos = (lane & ~15) + 4 * (lane & 3) + ((lane >> 2) & 3);
-    xl[ONE * LS + lane] = 1.0f;
-    xl[ZERO * LS + lane] = 0.0f;
-    {
-        u32x4 ones = u32x4{0x3F803F80u, 0x00003F80u, 0u, 0u}, zeros = u32x4{0u, 0u, 0u, 0u};
-        *reinterpret_cast<u32x4*>(ai + lane * AIS + 12) = ones;
-        *reinterpret_cast<u32x4*>(ai + lane * AIS + 16) = zeros;
-    }
 
     const bool vec = a.vec_ok != 0;
     long long lo, hi;
@@ -718,35 +711,48 @@ __device__ __forceinline__ void pass_xdl_body(const PassArgs& a) {
         for (int j = 0; j < D; ++j) { const float v = pp[j]; pv[j] = hasp ? v : 0.f; }
     }
 
-    // ---- B operands of the y GEMM: lane (k = i16, g = kk) holds the terms of W_k its lane group multiplies (see the header)
+    // ---- B operands of the y GEMM: lane (k = i16, g = kk) holds the terms of W_k its lane group multiplies (see the header).
+    // They are the same in the four lane groups of a wave and in every wave of the block, and only 16 x D (component, output
+    // coordinate) items are distinct: the block builds each item ONCE into an LDS image (below) and every lane reads its own
+    // quadruples from it, instead of every lane forming all D coordinates of its component.
     constexpr int NS = D < 4 ? D : 4;                        // output coordinates done by ONE MFMA (contraction over x'_0..3)
     constexpr int NB = D > 4 ? D - 4 : 0;                    // output coordinates 4.. : two MFMAs (contraction over x'_0..7)
+    // Image: per component QK distinct quadruples (16 bytes each), components QS quadruples apart.
+    //   coordinate i < NS, slots 3 i ..:        (W_h|W_m)  (W_h|W_l)  bias        over the coordinate pairs (0,1), (2,3)
+    //   coordinate i >= 4, slots 3 NS + 4 (i - 4) ..:  W_h  W_m  W_l  bias        over the coordinate pairs (0,1) .. (6,7)
+    // QS is odd: the 16 components of a ds_read_b128 lane group then start in 16 different 16-byte bank slots.
+    // The image lies at the start of the block's dynamic LDS, over the xl / ai region of wave 0 (and of wave 1 where a region is
+    // shorter than the image), which nothing has written yet.  It fits ONE wave's region for every D (asserted below), so every plan,
+    // the one-wave launches included, takes this path: there is no per-lane form left.
+    constexpr int QK = 3 * NS + 4 * NB, QS = QK | 1;
+    static_assert(16 * QS * 4 <= xdl_wave_floats<D>(), "the operand image must fit the LDS of a one-wave launch");
     u32x4 Bsm[NS], B1[NB > 0 ? NB : 1], B2[NB > 0 ? NB : 1];
     v2f pch;
     float pua, pub;
     {
         const bool on = i16 < K;
-        const float* __restrict__ p = a.pack + (on ? i16 : 0) * G::PACK;
-        float raw[G::PACK];
-        if (G::PACK % 4 == 0 && (reinterpret_cast<uintptr_t>(a.pack) & 15) == 0) {
+        const float* __restrict__ pc = a.pack + (on ? i16 : 0) * G::PACK + D + G::TRI;
+        const float c0 = pc[0], c1 = pc[1], c2 = pc[2], c3 = pc[3];
+        pch.x = on ? c0 : -INFINITY;                         // log2-domain constant; -inf switches the lane off
+        pch.y = on ? c1 : 0.f;
+        pua = on ? c2 : 0.f;
+        pub = on ? c3 : 1.f;
+    }
+    {
+        u32x4* img = reinterpret_cast<u32x4*>(smem);
+        // item (k, i) -> thread k D + i; the stride covers the plans with fewer than 16 D threads (nw goes down to 1)
+        for (int it = threadIdx.x; it < 16 * D; it += blockDim.x) {
+            const int k = it / D, i = it - k * D;
+            const bool on = k < K;                           // a switched-off component: all-zero operands
+            const float* __restrict__ p = a.pack + (on ? k : 0) * G::PACK;
+            const int tri = i * (i + 1) / 2;
+            float mr[D], wr[D];                              // m_k, and row i of W_k (words beyond the diagonal: never used)
 #pragma unroll
-            for (int j = 0; j < G::PACK / 4; ++j) {
-                const float4 q = reinterpret_cast<const float4*>(p)[j];
-                raw[4 * j] = q.x; raw[4 * j + 1] = q.y; raw[4 * j + 2] = q.z; raw[4 * j + 3] = q.w;
-            }
-        } else {
-#pragma unroll
-            for (int j = 0; j < G::PACK; ++j) raw[j] = p[j];
-        }
-        pch.x = on ? raw[D + G::TRI] : -INFINITY;            // log2-domain constant; -inf switches the lane off
-        pch.y = on ? raw[D + G::TRI + 1] : 0.f;
-        pua = on ? raw[D + G::TRI + 2] : 0.f;
-        pub = on ? raw[D + G::TRI + 3] : 1.f;
-#pragma unroll
-        for (int i = 0; i < D; ++i) {
+            for (int j = 0; j < D; ++j) { mr[j] = p[j]; wr[j] = p[D + tri + j]; }      // D + tri + j < D + TRI: inside the pack row
             double bi = 0.0;                                 // b_i = -sum_j W_ij (m_j - pivot_j), fp64
 #pragma unroll
-            for (int j = 0; j <= i; ++j) bi -= (double)raw[D + i * (i + 1) / 2 + j] * ((double)raw[j] - (double)pv[j]);
+            for (int j = 0; j < D; ++j)
+                if (j <= i) bi -= (double)wr[j] * ((double)mr[j] - (double)pv[j]);
             unsigned tb[3];
             split_bf16<3>(v2f{(float)bi, 0.f}, tb);          // low halves: b_h, b_m, b_l
             const unsigned bias0 = (tb[0] & 0xffffu) | (tb[1] << 16), bias1 = tb[2] & 0xffffu;   // slots (b_h, b_m), (b_l, 0)
@@ -754,35 +760,60 @@ __device__ __forceinline__ void pass_xdl_body(const PassArgs& a) {
 #pragma unroll
             for (int q = 0; q < DP; ++q) {
                 const int j0 = 2 * q, j1 = 2 * q + 1;
-                const float wa = j0 <= i ? raw[D + i * (i + 1) / 2 + j0] : 0.f;
-                const float wb = (j1 <= i && j1 < D) ? raw[D + i * (i + 1) / 2 + (j1 <= i ? j1 : 0)] : 0.f;
+                const float wa = j0 <= i ? wr[j0] : 0.f;
+                const float wb = (j1 <= i && j1 < D) ? wr[j1 < D ? j1 : 0] : 0.f;
                 unsigned t3[3];
                 split_bf16<3>(v2f{wa, wb}, t3);
                 th[q] = t3[0]; tm[q] = t3[1]; tl[q] = t3[2];
             }
+            const u32x4 zero = u32x4{0u, 0u, 0u, 0u};
+            const u32x4 bias = on ? u32x4{bias0, bias1, 0u, 0u} : zero;
             if (i < NS) {
-                // (W_h|W_m), (W_h|W_l), (W_h|W_m), bias  over the coordinate pairs (0,1), (2,3)
-                const u32x4 w = kk == 0 ? u32x4{th[0], th[1], tm[0], tm[1]}
-                              : kk == 1 ? u32x4{th[0], th[1], tl[0], tl[1]}
-                              : kk == 2 ? u32x4{th[0], th[1], tm[0], tm[1]}
-                                        : u32x4{bias0, bias1, 0u, 0u};
-                Bsm[i] = on ? w : u32x4{0u, 0u, 0u, 0u};
+                u32x4* o = img + k * QS + 3 * i;
+                o[0] = on ? u32x4{th[0], th[1], tm[0], tm[1]} : zero;
+                o[1] = on ? u32x4{th[0], th[1], tl[0], tl[1]} : zero;
+                o[2] = bias;
             } else {
-                const int ib = i - 4;
-                // MFMA 1: W_h | bias | W_m | W_h  (x x'_h | ones | x'_h | x'_m: the leading products, the bias that cancels most of them and the
-                //          first-order corrections)      MFMA 2: W_l | W_h | W_m | 0  (x x'_h | x'_l | x'_m: the second-order corrections).
-                // The MFMA rounds its sum ONCE, at the exponent of its LARGEST term (tools/ubench/mfma_cancel_numerics.hip): with the
-                // bias beside the leading products the first MFMA leaves y itself (|y| ~ 3 where |W x'|, |b| ~ 15) and the second one adds
-                // terms of 2^-16 of that to it - one rounding at the scale of the large terms instead of two (round 4 had the bias in the
-                // second MFMA); tools/r5_smm_error_budget.py: max |r - r_fp64| of the SMM 6.1e-6 -> 2.4e-6 in emulation.
-                const u32x4 w1 = kk == 0 ? u32x4{th[0], th[1], th[2], th[3]} : kk == 1 ? u32x4{bias0, bias1, 0u, 0u}
-                               : kk == 2 ? u32x4{tm[0], tm[1], tm[2], tm[3]} : u32x4{th[0], th[1], th[2], th[3]};
-                const u32x4 w2 = kk == 0 ? u32x4{tl[0], tl[1], tl[2], tl[3]} : kk == 1 ? u32x4{th[0], th[1], th[2], th[3]}
-                               : kk == 2 ? u32x4{tm[0], tm[1], tm[2], tm[3]} : u32x4{0u, 0u, 0u, 0u};
-                B1[ib < 0 ? 0 : ib] = on ? w1 : u32x4{0u, 0u, 0u, 0u};
-                B2[ib < 0 ? 0 : ib] = on ? w2 : u32x4{0u, 0u, 0u, 0u};
+                u32x4* o = img + k * QS + 3 * NS + 4 * (i - 4);
+                o[0] = on ? u32x4{th[0], th[1], th[2], th[3]} : zero;
+                o[1] = on ? u32x4{tm[0], tm[1], tm[2], tm[3]} : zero;
+                o[2] = on ? u32x4{tl[0], tl[1], tl[2], tl[3]} : zero;
+                o[3] = bias;
             }
         }
+        __syncthreads();
+        const u32x4* q = img + i16 * QS;
+        // one MFMA: (W_h|W_m), (W_h|W_l), (W_h|W_m), bias  for the lane groups 0..3
+        const int s0 = kk == 1 ? 1 : (kk == 3 ? 2 : 0);
+#pragma unroll
+        for (int i = 0; i < NS; ++i) Bsm[i] = q[3 * i + s0];
+        if constexpr (NB > 0) {
+            // MFMA 1: W_h | bias | W_m | W_h  (x x'_h | ones | x'_h | x'_m: the leading products, the bias that cancels most of them and the
+            //          first-order corrections)      MFMA 2: W_l | W_h | W_m | 0  (x x'_h | x'_l | x'_m: the second-order corrections).
+            // The MFMA rounds its sum ONCE, at the exponent of its LARGEST term (tools/ubench/mfma_cancel_numerics.hip): with the
+            // bias beside the leading products the first MFMA leaves y itself (|y| ~ 3 where |W x'|, |b| ~ 15) and the second one adds
+            // terms of 2^-16 of that to it - one rounding at the scale of the large terms instead of two (round 4 had the bias in the
+            // second MFMA); tools/r5_smm_error_budget.py: max |r - r_fp64| of the SMM 6.1e-6 -> 2.4e-6 in emulation.
+            const int s1 = kk == 1 ? 3 : (kk == 2 ? 1 : 0), s2 = kk == 0 ? 2 : (kk == 1 ? 0 : 1);
+#pragma unroll
+            for (int ib = 0; ib < NB; ++ib) {
+                B1[ib] = q[3 * NS + 4 * ib + s1];
+                const u32x4 w2 = q[3 * NS + 4 * ib + s2];
+                B2[ib] = kk == 3 ? u32x4{0u, 0u, 0u, 0u} : w2;
+            }
+        }
+        // Second barrier, not a layout clear of the staging area: a one-wave launch has no LDS beside the region its first tile is staged
+        // into.  Every wave's image reads are complete before it arrives here (the barrier waits for its LDS counter), and the constant
+        // rows below and all tile staging are stored after it, so no store can reach the image while a lane still reads it.
+        __syncthreads();
+    }
+    // constant rows of the two images (written once; the tiles never touch them)
+    xl[ONE * LS + lane] = 1.0f;
+    xl[ZERO * LS + lane] = 0.0f;
+    {
+        u32x4 ones = u32x4{0x3F803F80u, 0x00003F80u, 0u, 0u}, zeros = u32x4{0u, 0u, 0u, 0u};
+        *reinterpret_cast<u32x4*>(ai + lane * AIS + 12) = ones;
+        *reinterpret_cast<u32x4*>(ai + lane * AIS + 16) = zeros;
     }
     // A operands: lane (m = i16, g = kk) reads term T[g] of tile row rho(m) = 4 (m & 3) + (m >> 2)
     const int rho = 4 * (i16 & 3) + (i16 >> 2);
@@ -826,7 +857,7 @@ __device__ __forceinline__ void pass_xdl_body(const PassArgs& a) {
     }
 
 #ifdef VMP_DEBUG_TS
-    asm volatile("" :: "v"(xr[0]), "v"(pv[0]), "v"(pch.x), "v"(B1[0][0]));      // the stamp below is taken when rows, pivot and pack have ARRIVED
+    asm volatile("" :: "v"(xr[0]), "v"(pv[0]), "v"(pch.x), "v"(Bsm[0][0]));    // the stamp below is taken when rows, pivot and operands have ARRIVED
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #endif
     PASS_TS(1);

@@ -189,6 +189,46 @@ int    vmp_mix_score(const float* x, int64_t N, int D, int K, const float* pack,
                      double* sum_out, void* ws, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Mixture imputation (csrc/vmp_impute.hip): partly observed rows under a mixture of Student-t densities in one streaming pass
+ * ------------------------------------------------------------------------------------------------
+ * For a row x with observed entries o (D_o of them) and missing entries m, a component (log w, mu, Sigma, nu), Lambda = Sigma^-1,
+ * d_o = x_o - mu_o:   R R^T = Lambda_mm,  t = Lambda_mo d_o,  y = R^-1 t,
+ *   q = d_o^T Sigma_oo^-1 d_o = d_o^T Lambda_oo d_o - |y|^2,    log det Sigma_oo = -log det Lambda + 2 sum_i log R_ii,
+ *   l_k = log w + lgamma((nu + D_o)/2) - lgamma(nu/2) - D_o/2 log(pi nu) - 1/2 log det Sigma_oo - (nu + D_o)/2 log1p(q / nu),
+ *   xhat_m^(k) = mu_m - R^-T y   (the conditional mean for nu > 1; for nu <= 1 the mean does not exist and this is the
+ *                                 conditional location - it is what is returned either way),
+ *   logp = logsumexp_k l_k,   resp_k = exp(l_k - logp),   xhat_m = sum_k resp_k xhat_m^(k).
+ * A row with nothing missing: logp and resp of vmp_mix_score; a row with nothing observed: l_k = log w_k.
+ * Impute pack: (K, vmp_mixture_impute_pack_words(D)) fp32 =
+ *   [ mu (D) | Lambda packed lower-triangular, row-major (D(D+1)/2) | log w | nu | log det Lambda | 1 / nu | G[0..D] ],
+ *   G[j] = lgamma((nu + j)/2) - lgamma(nu/2) - j/2 log(pi nu)  - the streaming kernel evaluates no lgamma.  A component whose matrix is
+ *   not symmetric positive definite, or whose degrees of freedom are not positive, gets a NaN pack row: every row's logp is NaN.
+ * (These entry points are named vmp_mixture_*: the vmp_mix_* prefix is the closed set of csrc/vmp_mix.hip and the scoring pass.)
+ *
+ * vmp_mixture_impute_pack_niw: the posterior predictive of the NIW posterior (alpha (K), beta (K), m (K,D), C (K,D,D), v (K)) of
+ *   gmm.inference: w = alpha / sum alpha, mu = m, nu' = v + 1 - D, Sigma = C (1 + beta) / (beta nu') - the mapping of
+ *   vmp_mix_score_pack_niw.
+ * vmp_mixture_impute_pack_t: explicit (log_w (K), mu (K,D), sigma (K,D,D), nu (K)), as vmp_mix_score_pack_t.              */
+int    vmp_mixture_impute_pack_words(int D);
+int    vmp_mixture_impute_pack_niw(int D, int K, const float* alpha, const float* beta, const float* m, const float* C,
+                                   const float* v, float* pack, void* stream);
+int    vmp_mixture_impute_pack_t(int D, int K, const float* log_w, const float* mu, const float* sigma, const float* nu,
+                                 float* pack, void* stream);
+/* The streaming pass.  x (N,D) (any alignment); mask (N,D) uint8, nonzero = missing (the convention of missing_data_mask,
+ * models/gmm.py:97-114); pack from one of the builders above.  The value in a missing slot of x never enters arithmetic (NaN and
+ * +-Inf there are as good as 0).  Outputs, each optional but not all NULL: x_out (N,D) - the observed entries of x copied bit for
+ * bit, the missing ones filled with xhat; x_out == x fills in place; logp_out (N); resp_out (N,K); sum_out = sum_n logp_n, one
+ * fp64 word: per-block fp64 partials in `ws` (vmp_mixture_impute_workspace_bytes, needed only with sum_out) added in a fixed order
+ * by a second one-wave launch - no atomics, bit-identical from run to run.  Every output has the same bits whichever others are
+ * requested.  log w_k = -inf: resp_k = 0; every log w = -inf: logp = -inf, resp = 0 and the filled entries are 0 (the observed ones
+ * are still copied) - no NaN.
+ * Errors (decided before any launch): VMP_E_DIM (D, K outside 1..VMP_MAX_D / 1..VMP_MAX_K), VMP_E_BADARG (N < 1, x, mask or pack
+ * NULL, no output), VMP_E_WS.                                                                                              */
+size_t vmp_mixture_impute_workspace_bytes(int64_t N, int D, int K);
+int    vmp_mixture_impute(const float* x, const uint8_t* mask, int64_t N, int D, int K, const float* pack, float* x_out,
+                          float* logp_out, float* resp_out, double* sum_out, void* ws, size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * T2: SVAE E-step fused with the ELBO regulariser (models/svae.py:14-119 and :229-252)
  * ------------------------------------------------------------------------------------------------
  * Per (n,k) cell:  Pt = diag(-2 eta2d_n) + P_k,  ht = eta1_n + h_k,  Lt = chol(Pt),

@@ -31,3 +31,16 @@ def mixture_logprob(y, mu, sigma, v, log_pi, return_resp=False):
     pack = _mix.score_pack_t(log_pi, mu, sigma, v)
     logp, resp, _ = _mix.mixture_score(y, pack, want_resp=return_resp, want_sum=False)
     return (logp, resp) if return_resp else logp
+
+
+def mixture_impute(y, miss, mu, sigma, v, log_pi, return_resp=False):
+    """Conditional means of the missing entries of y (N,D) - miss (N,D), nonzero = missing - under the mixture
+    sum_k pi_k S(. | mu_k, sigma_k, v_k): (y_filled (N,D), logp (N,)) with logp the marginal log density of each row's observed
+    entries, plus the (N,K) responsibilities exp(term_nk - logp_n) with return_resp=True.  For v_k <= 1 a Student-t has no mean; the
+    component's conditional location mu_m + sigma_mo sigma_oo^-1 (y_o - mu_o) is used either way.  One streaming HIP pass
+    (vmp_mixture_impute_pack_t + vmp_mixture_impute)."""
+    from ..models import _mix
+    _mix._impute_dims(y, miss, mu, 'mixture_impute')
+    pack = _mix.impute_pack_t(log_pi, mu, sigma, v)
+    y_out, logp, resp, _ = _mix.mixture_impute(y, miss, pack, want_resp=return_resp)
+    return (y_out, logp, resp) if return_resp else (y_out, logp)

@@ -181,6 +181,7 @@ def mixture_score(x, pack, want_logp=True, want_resp=False, want_sum=True):
     K = pack.shape[0]
     N, D = _dims(x, K)
     dev = x.device
+    pack = L.dev_f32(pack, 'pack', (K, L.lib().vmp_mix_pack_words(D)))      # an impute pack is wider: not interchangeable
     logp = torch.empty(N, dtype=torch.float32, device=dev) if want_logp else None
     resp = torch.empty(N, K, dtype=torch.float32, device=dev) if want_resp else None
     total, ws, nb = None, None, 0
@@ -191,6 +192,86 @@ def mixture_score(x, pack, want_logp=True, want_resp=False, want_sum=True):
     L.check(L.lib().vmp_mix_score(L.ptr(x), N, D, K, L.ptr(pack), L.ptr(logp), L.ptr(resp), L.ptr(total), L.ptr(ws), nb,
                                   L.stream()), 'vmp_mix_score')
     return logp, resp, total
+
+
+def _impute_dims(x, miss, m, what):
+    """shapes of (x, miss, component locations) BEFORE the library or the device is touched"""
+    N, D, K = _score_dims(x, m, what)
+    if not torch.is_tensor(miss) or tuple(miss.shape) != (N, D):
+        raise L.VmpError('%s: the missing-data mask must be (%d,%d), got %s' % (what, N, D, tuple(miss.shape) if torch.is_tensor(miss) else type(miss)))
+    return N, D, K
+
+
+def _impute_pack(entry, ops, names, shapes, K, D, device):
+    ops = [_kd(t, n, shp) for t, n, shp in zip(ops, names, shapes)]
+    ops = [L.dev_f32(t.detach().to(torch.float32), n) for t, n in zip(ops, names)]
+    pack = torch.empty(K, L.lib().vmp_mixture_impute_pack_words(D), dtype=torch.float32, device=device)
+    L.check(getattr(L.lib(), entry)(D, K, *[L.ptr(t) for t in ops], L.ptr(pack), L.stream()), entry)
+    return pack
+
+
+def impute_pack_niw(alpha_k, beta_k, m_k, C_k, v_k):
+    """Impute pack of the GMM posterior predictive (vmp_mixture_impute_pack_niw) from the NIW posterior (alpha (K), beta (K), m (K,D),
+    C (K,D,D), v (K)) = gmm.inference's theta: the mixture score_pack_niw scores."""
+    K, D = m_k.shape
+    return _impute_pack('vmp_mixture_impute_pack_niw', (alpha_k, beta_k, m_k, C_k, v_k), ('alpha_k', 'beta_k', 'm_k', 'C_k', 'v_k'),
+                        ((K,), (K,), (K, D), (K, D, D), (K,)), K, D, m_k.device)
+
+
+def impute_pack_t(log_w, mu, sigma, nu):
+    """Impute pack of an explicit Student-t mixture (vmp_mixture_impute_pack_t): log_w (K), mu (K,D), sigma (K,D,D) scale matrices,
+    nu (K) degrees of freedom."""
+    K, D = mu.shape
+    return _impute_pack('vmp_mixture_impute_pack_t', (log_w, mu, sigma, nu), ('log_w', 'mu', 'sigma', 'nu'),
+                        ((K,), (K, D), (K, D, D), (K,)), K, D, mu.device)
+
+
+def mixture_impute(x, miss, pack, want_x=True, want_logp=True, want_resp=False, want_sum=False, inplace=False):
+    """One streaming pass (vmp_mixture_impute) over the rows of x (N,D) and their mask miss (N,D; nonzero / True = missing) under an
+    impute pack: (x_out (N,D), logp (N,), resp (N,K), total 0-dim fp64); outputs that are not wanted are None.
+      x_out - x with its missing entries replaced by sum_k resp_k (mu_m - Lambda_mm^-1 Lambda_mo (x_o - mu_o))_k, the conditional mean
+              (for nu <= 1, where no mean exists, the conditional location); observed entries are copied bit for bit; inplace=True
+              writes into x itself (which must then be a contiguous fp32 GPU tensor) and returns it;
+      logp  - the marginal log density of the observed entries (log 1 = the log-sum-exp of the weights for a row without any);
+      resp  - exp(term_nk - logp_n).
+    What a missing slot of x holds is never read into arithmetic (NaN there is fine).  A row whose every weight is -inf gets
+    logp = -inf, resp = 0 and 0 in its missing entries.  Everything stays on the device: no host synchronisation."""
+    xin = x
+    x = L.dev_f32(x, 'x')
+    if not torch.is_tensor(pack) or pack.dim() != 2:
+        raise L.VmpError('pack must be a (K, words) tensor from impute_pack_niw / impute_pack_t')
+    K = pack.shape[0]
+    N, D = _dims(x, K)
+    dev = x.device
+    # a score pack (D + D(D+1)/2 + 4 words) passed by mistake would make the kernel read past its end
+    pack = L.dev_f32(pack, 'pack', (K, L.lib().vmp_mixture_impute_pack_words(D)))
+    if pack.device != dev:
+        raise L.VmpError('pack is on %s, x on %s' % (pack.device, dev))
+    if not torch.is_tensor(miss) or tuple(miss.shape) != (N, D):
+        raise L.VmpError('the missing-data mask must be (%d,%d)' % (N, D))
+    if miss.device != dev:
+        raise L.VmpError('the missing-data mask is on %s, x on %s' % (miss.device, dev))
+    if miss.dtype == torch.bool:
+        mask = miss.contiguous().view(torch.uint8)
+    elif miss.dtype == torch.uint8:
+        mask = miss.contiguous()
+    else:
+        mask = (miss != 0).view(torch.uint8)
+    x_out = None
+    if want_x:
+        if inplace and x.data_ptr() != xin.data_ptr():
+            raise L.VmpError('inplace=True needs a contiguous x')
+        x_out = x if inplace else torch.empty_like(x)
+    logp = torch.empty(N, dtype=torch.float32, device=dev) if want_logp else None
+    resp = torch.empty(N, K, dtype=torch.float32, device=dev) if want_resp else None
+    total, ws, nb = None, None, 0
+    if want_sum:
+        total = torch.empty((), dtype=torch.float64, device=dev)
+        nb = L.lib().vmp_mixture_impute_workspace_bytes(N, D, K)
+        ws = L.workspace(dev, nb)
+    L.check(L.lib().vmp_mixture_impute(L.ptr(x), L.ptr(mask), N, D, K, L.ptr(pack), L.ptr(x_out), L.ptr(logp), L.ptr(resp),
+                                       L.ptr(total), L.ptr(ws), nb, L.stream()), 'vmp_mixture_impute')
+    return (xin if (want_x and inplace) else x_out), logp, resp, total
 
 
 def default_prior(K, D, device):
@@ -316,6 +397,26 @@ class VMPLoop(object):
             raise L.VmpError('x_val has shape %s, expected (M >= 1, %d)' % (tuple(x_val.shape), self.D))
         _, _, total = mixture_score(x_val, self.score_pack(), want_logp=False)
         return total.item() / x_val.shape[0]
+
+    def impute_pack(self):
+        """Impute pack of the CURRENT posterior: the mixture score_pack() scores (GMM: impute_pack_niw; SMM: impute_pack_t)."""
+        if self.iterations == 0:
+            raise L.VmpError('no posterior to impute from yet: run at least one iteration')
+        al, be, m, C, v = self.theta()
+        if self.flavour == L.VMP_SMM:
+            return impute_pack_t(torch.log(al / al.sum()), m, C / v[:, None, None], self.kappa)
+        return impute_pack_niw(al, be, m, C, v)
+
+    def impute(self, x_new, miss):
+        """(x_filled (M,D), logp (M,)) of the partly observed rows x_new (M,D) with mask miss (M,D; nonzero = missing) under the current
+        posterior - gmm.predictive_impute / smm.heldout_impute on theta().  One streaming launch, no host synchronisation."""
+        if self.iterations == 0:
+            raise L.VmpError('no posterior to impute from yet: run at least one iteration')
+        if not torch.is_tensor(x_new) or x_new.dim() != 2 or x_new.shape[1] != self.D or x_new.shape[0] < 1:
+            raise L.VmpError('x_new has shape %s, expected (M >= 1, %d)' % (tuple(x_new.shape) if torch.is_tensor(x_new) else type(x_new), self.D))
+        _impute_dims(x_new, miss, self.post['m'], 'impute')
+        x_out, logp, _, _ = mixture_impute(x_new, miss, self.impute_pack())
+        return x_out, logp
 
     def run_until(self, x_val, tol, check_every=5, max_iterations=1000):
         """run(check_every) and score(x_val) in turn until the score improves by less than `tol` (absolute, nats per row) over

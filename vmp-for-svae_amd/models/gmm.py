@@ -145,6 +145,19 @@ def predictive_logprob(x, alpha_k, beta_k, m_k, C_k, v_k, return_resp=False):
     return (logp, total, resp) if return_resp else (logp, total)
 
 
+def predictive_impute(x, miss, alpha_k, beta_k, m_k, C_k, v_k, return_resp=False):
+    """Fill the missing entries of the rows of x (N,D) - miss (N,D), nonzero = missing, the convention of missing_data_mask - from
+    the posterior predictive of the variational GMM (the Student-t mixture predictive_logprob scores): each missing block gets
+    sum_k r_nk E[x_m | x_o, k] with r_nk the responsibilities that follow from the MARGINAL density of the observed entries (unlike
+    e_step_missing_data, which zeroes the missing differences inside the full precision).  One streaming HIP pass
+    (vmp_mixture_impute_pack_niw + vmp_mixture_impute).  Returns (x_filled (N,D), logp (N,)) - logp the marginal log density of the
+    observed entries - plus resp (N,K) when asked.  What the missing slots of x hold is never read into arithmetic."""
+    _mix._impute_dims(x, miss, m_k, 'predictive_impute')
+    pack = _mix.impute_pack_niw(alpha_k, beta_k, m_k, C_k, v_k)
+    x_out, logp, resp, _ = _mix.mixture_impute(x, miss, pack, want_resp=return_resp)
+    return (x_out, logp, resp) if return_resp else (x_out, logp)
+
+
 class _Handle(object):
     """Stand-in for a TF fetch: call it to get the current value."""
 

@@ -126,6 +126,21 @@ def heldout_logprob(x, alpha_k, beta_k, m_k, C_k, v_k, kappa_k, return_resp=Fals
     return (logp, total, resp) if return_resp else (logp, total)
 
 
+def heldout_impute(x, miss, alpha_k, beta_k, m_k, C_k, v_k, kappa_k, return_resp=False):
+    """Fill the missing entries of the rows of x (N,D) (miss (N,D), nonzero = missing) from the plug-in Student-t mixture of
+    heldout_logprob (mu_k = m_k, sigma_k = C_k / v_k, nu_k = kappa_k, log_w_k = log(alpha_k / sum alpha)): the conditional mean of the
+    missing block given the observed one, averaged with the responsibilities of the observed entries' marginal density (for
+    kappa_k <= 1, where a Student-t has no mean, the conditional location).  One streaming HIP pass (vmp_mixture_impute_pack_t +
+    vmp_mixture_impute).  Returns (x_filled (N,D), logp (N,)) plus resp (N,K) when asked."""
+    N, D, K = _mix._impute_dims(x, miss, m_k, 'heldout_impute')
+    for t, n, shp in ((alpha_k, 'alpha_k', (K,)), (beta_k, 'beta_k', (K,)), (C_k, 'C_k', (K, D, D)), (v_k, 'v_k', (K,)),
+                      (kappa_k, 'kappa_k', (K,))):
+        _mix._kd(t, n, shp)
+    pack = _mix.impute_pack_t(torch.log(alpha_k / alpha_k.sum()), m_k, C_k / v_k[:, None, None], kappa_k)
+    x_out, logp, resp, _ = _mix.mixture_impute(x, miss, pack, want_resp=return_resp)
+    return (x_out, logp, resp) if return_resp else (x_out, logp)
+
+
 def inference(x, K, kappa_init, seed, name='inference', r_init=None):
     """reference smm.py:199-245: as gmm.inference with u_nk initialised to ones and constant kappa."""
     N, D = x.shape

@@ -229,6 +229,50 @@ int    vmp_mixture_impute(const float* x, const uint8_t* mask, int64_t N, int D,
                           float* logp_out, float* resp_out, double* sum_out, void* ws, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Mixture fitting on partly observed rows (csrc/vmp_missfit.hip): variational Bayes with the missing entries as latent variables
+ * ------------------------------------------------------------------------------------------------
+ * The variational GMM of models/gmm.py (NIW posterior (alpha, beta, m, C, v) per component, C the inverse scale, P = C^-1) on rows
+ * whose entries are missing at random.  The factor is q(z_n, x_n,m) = q(z_n) q(x_n,m | z_n); for a row with observed entries o (D_o of
+ * them) and missing entries m, Lbar_k = v_k P_k and d_o = x_o - m_k,o its optimum given q(pi, mu, Lambda) is
+ *   R R^T = Lbar_mm,   t = Lbar_mo d_o,   y = R^-1 t,   q_o = d_o^T Lbar_oo d_o - |y|^2,
+ *   xhat_m^(k) = m_k,m - R^-T y,   xhat_o^(k) = x_o,   Cov^(k) = Lbar_mm^-1 on the (m,m) block and 0 elsewhere (it depends on the
+ *                                                       row's pattern and on k, not on the row's values),
+ *   log rho_nk = E log pi_k + 1/2 E log|Lambda_k| - D / (2 beta_k) - 1/2 q_o - sum_i log R_ii   [ - D_o/2 log 2 pi ],
+ *   r_nk = softmax_k log rho_nk,
+ * with E log pi and E log|Lambda| as compute_log_pi / compute_expct_log_det_prec give them (models/gmm.py:117-138, the det <= 1e-20
+ * guard included).  The bracketed term is the same for every k: the pass leaves it out (it matters for the lower bound only).  A row
+ * with nothing missing is the E-step of vmp_mix_estep (Bishop 10.46 / 10.64); a row with nothing observed has q_o = 0.
+ * The M-step is the NIW update of vmp_mix_finalize, unchanged, on the raw moments of the COMPLETED rows in the vmp_mix_stats layout:
+ *   Nk = Wk = sum_n r_nk,   sx = sum_n r_nk xhat_n^(k),   sxx = sum_n r_nk ( xhat_n^(k) xhat_n^(k)^T + Cov_n^(k) ).
+ * Fit pack: (K, vmp_mixture_fit_pack_words(D)) fp32 = [ m (D) | Lbar packed lower-triangular, row-major (D(D+1)/2) | c ],
+ *   c = E log pi + 1/2 E log|Lambda| - D / (2 beta), built by vmp_mixture_fit_pack from (alpha (K), beta (K), m (K,D), C (K,D,D), v (K))
+ *   with one thread per component, fp64 inside, rounded once.  A component whose C is not symmetric positive definite gets a NaN row.
+ *
+ * vmp_mixture_fit_pass: one streaming pass over x (N,D) (any alignment) and mask (N,D) uint8, nonzero = missing.  The value in a
+ *   missing slot of x never enters arithmetic (NaN and +-Inf there are as good as 0).  Outputs: r_out (N,K), required; logr_out (N,K)
+ *   = log r, optional; x_fill_out (N,D), optional - the observed entries of x copied bit for bit, the missing ones filled with
+ *   sum_k r_nk xhat_m^(k); stats_out (K, vmp_mix_stats_words(D)) fp64, optional.  The moments are accumulated in fp32 on
+ *   xhat - m_k (the shift is the component's own location, taken from the pack), flushed to fp64 every 128 rows of a wave into that
+ *   wave's own words of `ws`, and added over the waves in a fixed order by a second launch that undoes the shift in fp64 - no
+ *   atomics; every output is bit-identical from run to run and whichever optional outputs are requested.  ws
+ *   (vmp_mixture_fit_workspace_bytes, 8-byte aligned) is always needed; without stats_out the second launch is skipped.
+ * vmp_mixture_fit_iterate: `iterations` x (vmp_mix_finalize on stats -> vmp_mixture_fit_pack -> vmp_mixture_fit_pass with stats_out =
+ *   stats) enqueued back to back, no host work in between; stats holds the moments of the current r on entry (seeded by
+ *   vmp_mix_stats) and of the last r on return.  logr, x_fill, xbar, S, pi may be NULL.
+ * Errors (decided before any launch): VMP_E_DIM (D, K outside 1..VMP_MAX_D / 1..VMP_MAX_K), VMP_E_BADARG (N < 1, x, mask, pack or
+ *   r_out NULL - no output -, a NULL prior, posterior or stats of the iteration, iterations < 0), VMP_E_WS.                      */
+int    vmp_mixture_fit_pack_words(int D);
+int    vmp_mixture_fit_pack(int D, int K, const float* alpha, const float* beta, const float* m, const float* C, const float* v,
+                            float* pack, void* stream);
+size_t vmp_mixture_fit_workspace_bytes(int64_t N, int D, int K);
+int    vmp_mixture_fit_pass(const float* x, const uint8_t* mask, int64_t N, int D, int K, const float* pack, float* r_out,
+                            float* logr_out, float* x_fill_out, double* stats_out, void* ws, size_t ws_bytes, void* stream);
+int    vmp_mixture_fit_iterate(const float* x, const uint8_t* mask, int64_t N, int D, int K, const float* alpha0,
+                               const float* beta0, const float* m0, const float* C0, const float* v0, float* r, float* logr,
+                               float* x_fill, float* alpha, float* beta, float* m, float* C, float* v, float* xbar, float* S,
+                               float* pi, float* pack, double* stats, void* ws, size_t ws_bytes, int iterations, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * T2: SVAE E-step fused with the ELBO regulariser (models/svae.py:14-119 and :229-252)
  * ------------------------------------------------------------------------------------------------
  * Per (n,k) cell:  Pt = diag(-2 eta2d_n) + P_k,  ht = eta1_n + h_k,  Lt = chol(Pt),

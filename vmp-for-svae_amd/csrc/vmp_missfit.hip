@@ -1,0 +1,525 @@
+// Fitting the variational Gaussian mixture on partly observed rows (missing at random): the E-step of the factor
+// q(z_n, x_n,m) = q(z_n) q(x_n,m | z_n) and the sufficient statistics of the completed rows, in one streaming pass over (x, mask).
+//
+// Per (row, component) cell, with Lbar = v_k C_k^-1 the expected precision, o / m the observed / missing index sets of the row,
+// d_o = x_o - m_k,o:
+//   R R^T = Lbar_mm,  t = Lbar_mo d_o,  y = R^-1 t,  q_o = d_o^T Lbar_oo d_o - |y|^2,
+//   xhat_m^(k) = m_k,m - R^-T y,   xhat_o^(k) = x_o,   Cov^(k) = Lbar_mm^-1 on the (m,m) block, 0 elsewhere,
+//   log rho_nk = c_k - 1/2 q_o - sum_i log R_ii,   c_k = E log pi_k + 1/2 E log|Lambda_k| - D / (2 beta_k),
+//   r_nk = softmax_k log rho_nk,   x_fill_m = sum_k r_nk xhat_m^(k),
+//   Nk = sum_n r_nk,  sx = sum_n r_nk xhat^(k),  sxx = sum_n r_nk (xhat^(k) xhat^(k)^T + Cov^(k)).
+// As in vmp_impute.hip the kernel factors A~ = M Lbar M + (I - M), M = diag(miss): a D x D factorisation with static indices whose
+// observed rows and columns are those of the identity.  Its inverse is M Lbar_mm^-1 M + (I - M): the missing block of R^-1 (R^-1)^T is
+// Cov^(k), the observed diagonal (exactly 1) is dropped by a select, everything else is a product of exact zeros.  The value in a
+// missing slot of x never enters arithmetic.
+//
+// Moments.  The products are formed in fp32 on xhat - m_k: the shift is the component's own location, which is in the pack, costs
+// nothing (x_o - m_k is d_o, xhat_m - m_k is -R^-T y) and is the centre of the rows that carry the component's weight.  Every lane
+// adds its rows in fp32; every FIT_CHUNK rows of a wave the four lanes that own a component are added (rows4_sum) and flushed to the
+// wave's own fp64 words in the workspace - a plain read-modify-write of words no other wave touches, no atomics.  A second launch adds
+// the waves in a fixed order and un-shifts in fp64 into the (K, vmp_mix_stats_words(D)) layout of vmp_mix_stats.
+//
+// Lane map: lane l = (i16 = l & 15, kk = l >> 4) owns component k = i16 + 16 t of every component tile t and, per loop iteration, the
+// data row n4 + kk (vmp_impute.hip).  K <= 16: the component is resident in VGPRs and a cell is evaluated once.  K > 16: a chunk of
+// rows is walked twice - first all tiles of a row for the softmax (r, log r and x_fill are written), then tile by tile with the cell
+// evaluated again and r read back (the lane's own store), so that one set of accumulators serves every tile.
+#include "vmp_common.h"
+#include "vmp_linalg.h"
+
+using namespace vmp;
+
+namespace {
+
+constexpr int FIT_NW = 4;                 // waves per block
+constexpr int FIT_MAX_BLOCKS = 512;
+constexpr int FIT_CHUNK = 128;            // rows of a wave between two fp32 -> fp64 flushes: VMP_MOM_FLUSH (2) tiles of 64 rows in vmp_mix.hip
+constexpr int FIT_RED_GROUPS = 16;        // wave groups of the reduction block
+
+inline int fit_blocks(int64_t N) {
+    const int64_t per = (int64_t)FIT_NW * FIT_CHUNK;
+    const int64_t b = (N + per - 1) / per;
+    return (int)(b < 1 ? 1 : (b > FIT_MAX_BLOCKS ? FIT_MAX_BLOCKS : b));
+}
+
+// fit pack: [ m_k (D) | Lbar_k = v_k C_k^-1 lower, row-major packed (D(D+1)/2) | c_k ]
+template <int D>
+struct FGeo {
+    static constexpr int TRI  = D * (D + 1) / 2;
+    static constexpr int C    = D + TRI;
+    static constexpr int PACK = C + 1;
+    static constexpr int STRIDE = PACK | 1;        // LDS stride: odd, so that the 16 components of a tile fall into 16 banks
+    static constexpr int MW   = 1 + D + TRI;       // moment words per component: Nk | s1 (D) | s2 lower packed
+    static constexpr int SW   = 2 + D + D * D;     // public stats words
+};
+
+inline int fit_pack_words(int D) { return D + D * (D + 1) / 2 + 1; }
+inline int fit_moment_words(int D) { return 1 + D + D * (D + 1) / 2; }
+
+__device__ double fit_digamma(double x) {
+    double r = 0.0;
+    while (x < 10.0) { r -= 1.0 / x; x += 1.0; }
+    const double f = 1.0 / (x * x);
+    return r + log(x) - 0.5 / x
+           - f * (1.0 / 12 - f * (1.0 / 120 - f * (1.0 / 252 - f * (1.0 / 240 - f * (1.0 / 132 - f * (691.0 / 32760))))));
+}
+
+struct FitPackArgs {
+    int K;
+    const float *alpha, *beta, *m, *C, *v;
+    float* pack;
+};
+
+// One thread per component, fp64 inside, rounded once: P = C^-1 through the Cholesky factor, Lbar = v P, and the constant of
+// log rho as compute_log_pi / compute_expct_log_det_prec give it (gmm.py:117-138, the det <= 1e-20 guard included).
+template <int D>
+__global__ __launch_bounds__(WAVE) void fit_pack_kernel(FitPackArgs a) {
+    using G = FGeo<D>;
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= a.K) return;
+    const float qnan = __builtin_nanf("");
+    double asum = 0.0;
+    for (int j = 0; j < a.K; ++j) asum += a.alpha[j];
+    double A[D * D], W[D * D];
+    const float* Ck = a.C + k * D * D;
+#pragma unroll
+    for (int i = 0; i < D; ++i)
+#pragma unroll
+        for (int j = 0; j < D; ++j) A[i * D + j] = 0.5 * ((double)Ck[i * D + j] + (double)Ck[j * D + i]);
+    const bool ok = chol_lower<D>(A);
+    double sumlog = 0.0;
+#pragma unroll
+    for (int i = 0; i < D; ++i) sumlog += log(A[i * D + i]);
+    tri_inv_lower<D>(A, W);
+    const double vk = a.v[k], bk = a.beta[k];
+    float* p = a.pack + k * G::PACK;
+#pragma unroll
+    for (int j = 0; j < D; ++j) p[j] = ok ? a.m[k * D + j] : qnan;
+    int idx = D;
+#pragma unroll
+    for (int i = 0; i < D; ++i)
+#pragma unroll
+        for (int j = 0; j <= i; ++j) {           // (C^-1)_ij = sum_{q >= i} W_qi W_qj   (W = L^-1 lower, j <= i)
+            double s = 0.0;
+#pragma unroll
+            for (int q = i; q < D; ++q) s += W[q * D + i] * W[q * D + j];
+            p[idx++] = ok ? (float)(vk * s) : qnan;
+        }
+    const double logdetP = -2.0 * sumlog;
+    const double ld = (logdetP > log(1e-20)) ? logdetP : 0.0;
+    double sdg = 0.0;
+    for (int i = 0; i < D; ++i) sdg += fit_digamma(0.5 * (vk + 1.0 + i));
+    const double elp = fit_digamma((double)a.alpha[k]) - fit_digamma(asum);
+    const double c = elp + 0.5 * (sdg + D * 0.69314718055994530942 + ld) - 0.5 * (D / bk);
+    p[G::C] = ok ? (float)c : qnan;
+}
+
+struct FitArgs {
+    const float* x;
+    const uint8_t* mask;
+    const float* pack;
+    float* r;             // (N,K)
+    float* logr;          // (N,K) or NULL
+    float* x_fill;        // (N,D) or NULL
+    double* slab;         // (waves, K, MW) fp64: the moments of a wave's rows
+    long long N;
+    long long rpw;        // rows per wave (multiple of 4): wave g owns rows [g rpw, min(N, (g+1) rpw))
+    int K;
+    int vec_in, vec_out;  // x / x_fill 16-byte aligned
+};
+
+template <int D>
+struct FitParams {
+    float mu[D], lam[FGeo<D>::TRI], c;
+    __device__ __forceinline__ void load(const float* src) {
+        using G = FGeo<D>;
+#pragma unroll
+        for (int d = 0; d < D; ++d) mu[d] = src[d];
+#pragma unroll
+        for (int i = 0; i < G::TRI; ++i) lam[i] = src[D + i];
+        c = src[G::C];
+    }
+    __device__ __forceinline__ float L(int i, int j) const { return lam[i >= j ? i * (i + 1) / 2 + j : j * (j + 1) / 2 + i]; }
+};
+
+// One (row, component) cell: log rho; dh[] = xhat - m_k (x_o - m_k,o in the observed slots, -R^-T y in the missing ones); A[] the
+// off-diagonal entries of the Cholesky factor of A~ and rd[] its reciprocal diagonal, for fit_moments.
+template <int D>
+__device__ __forceinline__ float fit_cell(const FitParams<D>& p, const float (&x)[D], const bool (&miss)[D], float (&dh)[D],
+                                          float (&A)[FGeo<D>::TRI], float (&rd)[D]) {
+    float dt[D], v[D];
+#pragma unroll
+    for (int d = 0; d < D; ++d) dt[d] = miss[d] ? 0.f : x[d] - p.mu[d];
+    float qo = 0.f;
+#pragma unroll
+    for (int i = 0; i < D; ++i) {
+        float s = p.L(i, 0) * dt[0];
+#pragma unroll
+        for (int j = 1; j < D; ++j) s = fmaf(p.L(i, j), dt[j], s);
+        v[i] = miss[i] ? s : 0.f;
+        qo = fmaf(dt[i], s, qo);                 // dt[i] = 0 in the missing rows
+    }
+    float piv[D];
+#pragma unroll
+    for (int i = 0; i < D; ++i)
+#pragma unroll
+        for (int j = 0; j <= i; ++j) A[i * (i + 1) / 2 + j] = (miss[i] && miss[j]) ? p.lam[i * (i + 1) / 2 + j] : (i == j ? 1.f : 0.f);
+#pragma unroll
+    for (int j = 0; j < D; ++j) {
+        float s = A[j * (j + 1) / 2 + j];
+#pragma unroll
+        for (int q = 0; q < j; ++q) s = fmaf(-A[j * (j + 1) / 2 + q], A[j * (j + 1) / 2 + q], s);
+        piv[j] = s;
+        rd[j] = __builtin_amdgcn_rsqf(s);
+#pragma unroll
+        for (int i = j + 1; i < D; ++i) {
+            float t = A[i * (i + 1) / 2 + j];
+#pragma unroll
+            for (int q = 0; q < j; ++q) t = fmaf(-A[i * (i + 1) / 2 + q], A[j * (j + 1) / 2 + q], t);
+            A[i * (i + 1) / 2 + j] = t * rd[j];
+        }
+    }
+    float slog = 0.f;                            // sum_i log R_ii = 1/2 sum log pivot, two pivots per logarithm
+#pragma unroll
+    for (int j = 0; j + 1 < D; j += 2) slog += logf(piv[j] * piv[j + 1]);
+    if constexpr (D % 2) slog += logf(piv[D - 1]);
+    slog *= 0.5f;
+    float yy = 0.f;                              // y = R^-1 t (in v), |y|^2, z = R^-T y (in v)
+#pragma unroll
+    for (int i = 0; i < D; ++i) {
+        float s = v[i];
+#pragma unroll
+        for (int q = 0; q < i; ++q) s = fmaf(-A[i * (i + 1) / 2 + q], v[q], s);
+        v[i] = s * rd[i];
+        yy = fmaf(v[i], v[i], yy);
+    }
+#pragma unroll
+    for (int i = D - 1; i >= 0; --i) {
+        float s = v[i];
+#pragma unroll
+        for (int q = i + 1; q < D; ++q) s = fmaf(-A[q * (q + 1) / 2 + i], v[q], s);
+        v[i] = s * rd[i];
+    }
+#pragma unroll
+    for (int d = 0; d < D; ++d) dh[d] = dt[d] - v[d];        // one of the two is an exact zero
+    float q = qo - yy;
+    q = q < 0.f ? 0.f : q;                       // rounding of the difference; a NaN stays a NaN
+    return (p.c - slog) - 0.5f * q;
+}
+
+// acc += r [ 1 | dh | dh dh^T + Cov ]:  W = R^-1 in place of the factor (column by column: an entry of R is last read when its own
+// slot is written), Cov = W^T W with the observed diagonal (exactly 1) dropped.
+template <int D>
+__device__ __forceinline__ void fit_moments(const float (&dh)[D], const bool (&miss)[D], float (&A)[FGeo<D>::TRI], const float (&rd)[D],
+                                            float r, float (&acc)[FGeo<D>::MW]) {
+#pragma unroll
+    for (int j = 0; j < D; ++j)
+#pragma unroll
+        for (int i = j + 1; i < D; ++i) {
+            float s = A[i * (i + 1) / 2 + j] * rd[j];
+#pragma unroll
+            for (int q = j + 1; q < i; ++q) s = fmaf(A[i * (i + 1) / 2 + q], A[q * (q + 1) / 2 + j], s);
+            A[i * (i + 1) / 2 + j] = -s * rd[i];
+        }
+    acc[0] += r;
+#pragma unroll
+    for (int d = 0; d < D; ++d) acc[1 + d] = fmaf(r, dh[d], acc[1 + d]);
+#pragma unroll
+    for (int i = 0; i < D; ++i)
+#pragma unroll
+        for (int j = 0; j <= i; ++j) {
+            float cv = (i == j ? rd[i] : A[i * (i + 1) / 2 + j]) * rd[i];                 // q = i: W_ii W_ij
+#pragma unroll
+            for (int q = i + 1; q < D; ++q) cv = fmaf(A[q * (q + 1) / 2 + i], A[q * (q + 1) / 2 + j], cv);
+            if (i == j) cv = miss[i] ? cv : 0.f;
+            acc[1 + D + i * (i + 1) / 2 + j] = fmaf(r, fmaf(dh[i], dh[j], cv), acc[1 + D + i * (i + 1) / 2 + j]);
+        }
+}
+
+template <int D>
+__device__ __forceinline__ void fit_store_row(float* __restrict__ p, const float (&o)[D], bool vec) {
+    if constexpr (D % 4 == 0) {
+        if (vec) {
+#pragma unroll
+            for (int j = 0; j < D / 4; ++j) reinterpret_cast<float4*>(p)[j] = make_float4(o[4 * j], o[4 * j + 1], o[4 * j + 2], o[4 * j + 3]);
+            return;
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < D; ++j) p[j] = o[j];
+}
+
+// the four lanes that own component k add their sums; lane kk = 0 adds the result to the wave's fp64 words (first: replaces them)
+template <int D>
+__device__ __forceinline__ void fit_flush(float (&acc)[FGeo<D>::MW], double* __restrict__ dst, bool first, bool owner) {
+#pragma unroll
+    for (int i = 0; i < FGeo<D>::MW; ++i) {
+        const float s = rows4_sum(acc[i]);
+        if (owner) dst[i] = (first ? 0.0 : dst[i]) + (double)s;
+        acc[i] = 0.f;
+    }
+}
+
+template <int D>
+__device__ __forceinline__ int fit_load_row(const FitArgs& a, long long nr, float (&x)[D], bool (&miss)[D]) {
+    load_row<D>(a.x + nr * D, x, a.vec_in != 0);
+    int n_obs = 0;
+#pragma unroll
+    for (int d = 0; d < D; ++d) { miss[d] = a.mask[nr * D + d] != 0; n_obs += miss[d] ? 0 : 1; }
+    return n_obs;
+}
+
+template <int D, int KTMAX>
+__global__ __launch_bounds__(FIT_NW * WAVE) void fit_kernel(FitArgs a) {
+    using G = FGeo<D>;
+    __shared__ float lds[KTMAX * 16 * G::STRIDE];
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int i16 = lane & 15, kk = lane >> 4;
+    const int KT = KTMAX == 1 ? 1 : (a.K + 15) / 16;
+
+    for (int i = threadIdx.x; i < a.K * G::PACK; i += FIT_NW * WAVE) lds[(i / G::PACK) * G::STRIDE + i % G::PACK] = a.pack[i];
+    __syncthreads();
+    FitParams<D> p;
+    if constexpr (KTMAX == 1) p.load(lds + (i16 < a.K ? i16 : 0) * G::STRIDE);   // lanes beyond K: a readable component, its term forced to -inf
+
+    const long long g = (long long)blockIdx.x * FIT_NW + wave;
+    const long long r0 = g * a.rpw;
+    const long long r1 = r0 + a.rpw < a.N ? r0 + a.rpw : a.N;
+    double* slab = a.slab + g * a.K * G::MW;
+    if (r0 >= r1) {                                                          // a wave without rows: its moments are zero
+        for (int i = lane; i < a.K * G::MW; i += WAVE) slab[i] = 0.0;
+        return;
+    }
+    float acc[G::MW];
+#pragma unroll
+    for (int i = 0; i < G::MW; ++i) acc[i] = 0.f;
+
+    for (long long c0 = r0; c0 < r1; c0 += FIT_CHUNK) {
+        const long long c1 = c0 + FIT_CHUNK < r1 ? c0 + FIT_CHUNK : r1;
+        for (long long n4 = c0; n4 < c1; n4 += 4) {
+            const long long n = n4 + kk;
+            const bool valid = n < c1;
+            const long long nr = valid ? n : c1 - 1;                         // rows past the range: a row of the range, discarded
+            float x[D];
+            bool miss[D];
+            fit_load_row<D>(a, nr, x, miss);
+
+            // lane-local online log-sum-exp over the lane's tiles: ml = running maximum, s = sum e, ax = sum e xhat
+            float ml = -INFINITY, s = 0.f, ax[D], lt[KTMAX], dh[D], A[G::TRI], rd[D];
+#pragma unroll
+            for (int d = 0; d < D; ++d) ax[d] = 0.f;
+#pragma unroll
+            for (int j = 0; j < KTMAX; ++j) lt[j] = -INFINITY;
+#pragma unroll 1
+            for (int t = 0; t < KT; ++t) {
+                const int k = t * 16 + i16;
+                if constexpr (KTMAX > 1) p.load(lds + (k < a.K ? k : 0) * G::STRIDE);
+                float l = fit_cell<D>(p, x, miss, dh, A, rd);
+                l = k < a.K ? l : -INFINITY;
+#pragma unroll
+                for (int j = 0; j < KTMAX; ++j) lt[j] = t == j ? l : lt[j];
+                const float mn = fmaxf(ml, l);
+                const float sh = mn == -INFINITY ? 0.f : mn;                 // every term so far -inf: -inf - (-inf) would be NaN
+                const float c = __expf(ml - sh), e = __expf(l - sh);
+                s = fmaf(s, c, e);
+#pragma unroll
+                for (int d = 0; d < D; ++d) ax[d] = fmaf(ax[d], c, e == 0.f ? 0.f : e * (p.mu[d] + dh[d]));
+                ml = mn;
+            }
+            const float mx = row16_max(ml);
+            const float shift = mx == -INFINITY ? 0.f : mx;
+            const float f = __expf(ml - shift);
+            const float S = row16_sum(s * f);
+            const float inv = S == 0.f ? 0.f : 1.0f / S;                     // a row without mass: r = 0, filled entries 0
+            const float lp = shift + logf(S);
+            if (a.x_fill) {
+                float o[D];
+#pragma unroll
+                for (int d = 0; d < D; ++d) {
+                    const float xs = row16_sum(ax[d] * f) * inv;
+                    o[d] = miss[d] ? xs : x[d];
+                }
+                if (valid && i16 == 0) fit_store_row<D>(a.x_fill + n * D, o, a.vec_out != 0);
+            }
+            float rk = 0.f;
+#pragma unroll
+            for (int j = 0; j < KTMAX; ++j) {
+                const int k = j * 16 + i16;
+                rk = __expf(lt[j] - shift) * inv;
+                if (valid && k < a.K) {
+                    a.r[n * a.K + k] = rk;
+                    if (a.logr) a.logr[n * a.K + k] = lt[j] - lp;
+                }
+            }
+            if constexpr (KTMAX == 1) fit_moments<D>(dh, miss, A, rd, (valid && i16 < a.K) ? rk : 0.f, acc);
+        }
+        if constexpr (KTMAX == 1) {
+            fit_flush<D>(acc, slab + i16 * G::MW, c0 == r0, kk == 0 && i16 < a.K);
+        } else {
+#pragma unroll 1
+            for (int t = 0; t < KT; ++t) {
+                const int k = t * 16 + i16;
+                p.load(lds + (k < a.K ? k : 0) * G::STRIDE);
+                for (long long n4 = c0; n4 < c1; n4 += 4) {
+                    const long long n = n4 + kk;
+                    const bool valid = n < c1;
+                    const long long nr = valid ? n : c1 - 1;
+                    float x[D], dh[D], A[G::TRI], rd[D];
+                    bool miss[D];
+                    fit_load_row<D>(a, nr, x, miss);
+                    fit_cell<D>(p, x, miss, dh, A, rd);
+                    const float rk = (valid && k < a.K) ? a.r[n * a.K + k] : 0.f;      // the lane's own store of the first walk
+                    fit_moments<D>(dh, miss, A, rd, rk, acc);
+                }
+                fit_flush<D>(acc, slab + (k < a.K ? k : 0) * G::MW, c0 == r0, kk == 0 && k < a.K);
+            }
+        }
+    }
+}
+
+struct FitReduceArgs {
+    const double* slab;
+    const float* pack;
+    double* stats;        // (K, SW)
+    int nwaves, K;
+};
+
+// One block per component: wave group j adds waves j, j + 16, ... in that order, the 16 group sums are added in group order, then
+// the shift by m_k (the fp32 words of the pack, exact in fp64) is undone:
+//   sx = s1 + Nk m,   sxx = s2 + s1 m^T + m s1^T + Nk m m^T.
+template <int D>
+__global__ __launch_bounds__(FIT_RED_GROUPS * WAVE) void fit_reduce_kernel(FitReduceArgs a) {
+    using G = FGeo<D>;
+    __shared__ double part[FIT_RED_GROUPS][WAVE];
+    __shared__ double red[WAVE];
+    const int k = blockIdx.x, grp = threadIdx.x >> 6, i = threadIdx.x & 63;
+    double s = 0.0;
+    if (i < G::MW)
+        for (int w = grp; w < a.nwaves; w += FIT_RED_GROUPS) s += a.slab[((long long)w * a.K + k) * G::MW + i];
+    part[grp][i] = s;
+    __syncthreads();
+    if (grp == 0) {
+        double t = part[0][i];
+#pragma unroll
+        for (int j = 1; j < FIT_RED_GROUPS; ++j) t += part[j][i];
+        red[i] = t;
+    }
+    __syncthreads();
+    const int j = threadIdx.x;
+    if (j >= G::SW) return;
+    const float* pk = a.pack + k * G::PACK;
+    const double Nk = red[0];
+    double out;
+    if (j < 2) out = Nk;
+    else if (j < 2 + D) { const int d = j - 2; out = red[1 + d] + Nk * (double)pk[d]; }
+    else {
+        const int d = (j - 2 - D) / D, e = (j - 2 - D) % D;
+        const int hi = d > e ? d : e, lo = d > e ? e : d;
+        const double md = pk[d], me = pk[e];
+        out = red[1 + D + hi * (hi + 1) / 2 + lo] + red[1 + d] * me + md * red[1 + e] + Nk * md * me;
+    }
+    a.stats[(long long)k * G::SW + j] = out;
+}
+
+int fit_dims(const char* who, int D, int K) {
+    if (D < 1 || D > VMP_MAX_D) { set_error("%s: D=%d outside compiled range 1..%d", who, D, VMP_MAX_D); return VMP_E_DIM; }
+    if (K < 1 || K > VMP_MAX_K) { set_error("%s: K=%d outside compiled range 1..%d", who, K, VMP_MAX_K); return VMP_E_DIM; }
+    return 0;
+}
+
+template <int D>
+int launch_fit(const FitArgs& a, int blocks, hipStream_t s) {
+    const dim3 grid(blocks), block(FIT_NW * WAVE);
+    if (a.K <= 16) hipLaunchKernelGGL((fit_kernel<D, 1>), grid, block, 0, s, a);
+    else           hipLaunchKernelGGL((fit_kernel<D, 4>), grid, block, 0, s, a);
+    return check_launch("fit_kernel");
+}
+
+// every refusal of the pass, decided on the host
+int fit_pass_check(const char* who, const float* x, const uint8_t* mask, int64_t N, int D, int K, const float* pack, const float* r_out,
+                   const void* ws, size_t ws_bytes) {
+    int rc = fit_dims(who, D, K);
+    if (rc) return rc;
+    if (N <= 0) { set_error("%s: N must be positive (got %lld)", who, (long long)N); return VMP_E_BADARG; }
+    if (!x || !mask || !pack) { set_error("%s: null pointer (%s)", who, !x ? "x" : !mask ? "mask" : "pack"); return VMP_E_BADARG; }
+    if (!r_out) { set_error("%s: no output requested (r_out is required)", who); return VMP_E_BADARG; }
+    const size_t need = vmp_mixture_fit_workspace_bytes(N, D, K);
+    if (!ws || ws_bytes < need) {
+        set_error("%s: workspace too small (%zu bytes, need %zu)", who, ws ? ws_bytes : (size_t)0, need);
+        return VMP_E_WS;
+    }
+    if (reinterpret_cast<uintptr_t>(ws) & 7) { set_error("%s: workspace not 8-byte aligned", who); return VMP_E_BADARG; }
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vmp_mixture_fit_pack_words(int D) { return (D < 1 || D > VMP_MAX_D) ? 0 : fit_pack_words(D); }
+
+int vmp_mixture_fit_pack(int D, int K, const float* alpha, const float* beta, const float* m, const float* C, const float* v,
+                         float* pack, void* stream) {
+    int rc = fit_dims("vmp_mixture_fit_pack", D, K);
+    if (rc) return rc;
+    if (!alpha || !beta || !m || !C || !v || !pack) { set_error("vmp_mixture_fit_pack: null pointer"); return VMP_E_BADARG; }
+    FitPackArgs a{K, alpha, beta, m, C, v, pack};
+    rc = -1;
+    VMP_SWITCH_DIM(D, DD, {
+        hipLaunchKernelGGL((fit_pack_kernel<DD>), dim3(1), dim3(64), 0, static_cast<hipStream_t>(stream), a);
+        rc = check_launch("fit_pack_kernel");
+    });
+    return rc;
+}
+
+size_t vmp_mixture_fit_workspace_bytes(int64_t N, int D, int K) {
+    if (D < 1 || D > VMP_MAX_D || K < 1 || K > VMP_MAX_K) return 0;
+    return (size_t)fit_blocks(N) * FIT_NW * K * fit_moment_words(D) * sizeof(double);      // the fp64 moments of every wave
+}
+
+int vmp_mixture_fit_pass(const float* x, const uint8_t* mask, int64_t N, int D, int K, const float* pack, float* r_out,
+                         float* logr_out, float* x_fill_out, double* stats_out, void* ws, size_t ws_bytes, void* stream) {
+    int rc = fit_pass_check("vmp_mixture_fit_pass", x, mask, N, D, K, pack, r_out, ws, ws_bytes);
+    if (rc) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int blocks = fit_blocks(N);
+    const long long waves = (long long)blocks * FIT_NW;
+    FitArgs a{};
+    a.x = x; a.mask = mask; a.pack = pack; a.r = r_out; a.logr = logr_out; a.x_fill = x_fill_out;
+    a.slab = static_cast<double*>(ws);
+    a.N = N; a.K = K;
+    a.rpw = ((N + waves - 1) / waves + 3) / 4 * 4;
+    a.vec_in = aligned16(x); a.vec_out = aligned16(x_fill_out);
+    rc = -1;
+    VMP_SWITCH_DIM(D, DD, rc = launch_fit<DD>(a, blocks, s));
+    if (rc || !stats_out) return rc;
+    FitReduceArgs ra{a.slab, pack, stats_out, (int)waves, K};
+    rc = -1;
+    VMP_SWITCH_DIM(D, DD, {
+        hipLaunchKernelGGL((fit_reduce_kernel<DD>), dim3(K), dim3(FIT_RED_GROUPS * WAVE), 0, s, ra);
+        rc = check_launch("fit_reduce_kernel");
+    });
+    return rc;
+}
+
+int vmp_mixture_fit_iterate(const float* x, const uint8_t* mask, int64_t N, int D, int K, const float* alpha0, const float* beta0,
+                            const float* m0, const float* C0, const float* v0, float* r, float* logr, float* x_fill, float* alpha,
+                            float* beta, float* m, float* C, float* v, float* xbar, float* S, float* pi, float* pack, double* stats,
+                            void* ws, size_t ws_bytes, int iterations, void* stream) {
+    int rc = fit_pass_check("vmp_mixture_fit_iterate", x, mask, N, D, K, pack, r, ws, ws_bytes);
+    if (rc) return rc;
+    if (iterations < 0) { set_error("vmp_mixture_fit_iterate: iterations must not be negative (got %d)", iterations); return VMP_E_BADARG; }
+    if (!alpha0 || !beta0 || !m0 || !C0 || !v0 || !alpha || !beta || !m || !C || !v || !stats) {
+        set_error("vmp_mixture_fit_iterate: null pointer (prior, posterior or stats)");
+        return VMP_E_BADARG;
+    }
+    for (int it = 0; it < iterations; ++it) {
+        rc = vmp_mix_finalize(stats, D, K, VMP_GMM, alpha0, beta0, m0, C0, v0, nullptr, alpha, beta, m, C, v, xbar, S, pi, nullptr, stream);
+        if (rc) return rc;
+        if ((rc = vmp_mixture_fit_pack(D, K, alpha, beta, m, C, v, pack, stream)) != 0) return rc;
+        if ((rc = vmp_mixture_fit_pass(x, mask, N, D, K, pack, r, logr, x_fill, stats, ws, ws_bytes, stream)) != 0) return rc;
+    }
+    return 0;
+}
+
+}  // extern "C"

@@ -251,12 +251,7 @@ def mixture_impute(x, miss, pack, want_x=True, want_logp=True, want_resp=False, 
         raise L.VmpError('the missing-data mask must be (%d,%d)' % (N, D))
     if miss.device != dev:
         raise L.VmpError('the missing-data mask is on %s, x on %s' % (miss.device, dev))
-    if miss.dtype == torch.bool:
-        mask = miss.contiguous().view(torch.uint8)
-    elif miss.dtype == torch.uint8:
-        mask = miss.contiguous()
-    else:
-        mask = (miss != 0).view(torch.uint8)
+    mask = _mask_u8(miss)
     x_out = None
     if want_x:
         if inplace and x.data_ptr() != xin.data_ptr():
@@ -272,6 +267,69 @@ def mixture_impute(x, miss, pack, want_x=True, want_logp=True, want_resp=False, 
     L.check(L.lib().vmp_mixture_impute(L.ptr(x), L.ptr(mask), N, D, K, L.ptr(pack), L.ptr(x_out), L.ptr(logp), L.ptr(resp),
                                        L.ptr(total), L.ptr(ws), nb, L.stream()), 'vmp_mixture_impute')
     return (xin if (want_x and inplace) else x_out), logp, resp, total
+
+
+def _mask_u8(miss):
+    """(N,D) uint8 view / copy of a missing-data mask of any dtype (nonzero = missing), as mixture_impute normalises it"""
+    if miss.dtype == torch.bool:
+        return miss.contiguous().view(torch.uint8)
+    if miss.dtype == torch.uint8:
+        return miss.contiguous()
+    return (miss != 0).view(torch.uint8)
+
+
+def fit_pack(alpha_k, beta_k, m_k, C_k, v_k):
+    """Fit pack of the NIW posterior (vmp_mixture_fit_pack): [m | v C^-1 packed lower | E log pi + 1/2 E log|Lambda| - D / (2 beta)]
+    per component - what mixture_fit_pass evaluates the E-step on partly observed rows from."""
+    K, D = m_k.shape
+    names = ('alpha_k', 'beta_k', 'm_k', 'C_k', 'v_k')
+    ops = [_kd(t, n, shp) for t, n, shp in zip((alpha_k, beta_k, m_k, C_k, v_k), names, ((K,), (K,), (K, D), (K, D, D), (K,)))]
+    ops = [L.dev_f32(t.detach().to(torch.float32), n) for t, n in zip(ops, names)]
+    pack = torch.empty(K, L.lib().vmp_mixture_fit_pack_words(D), dtype=torch.float32, device=m_k.device)
+    L.check(L.lib().vmp_mixture_fit_pack(D, K, *[L.ptr(t) for t in ops], L.ptr(pack), L.stream()), 'vmp_mixture_fit_pack')
+    return pack
+
+
+def mixture_fit_pass(x, miss, pack, want_logr=False, want_fill=False, want_stats=True):
+    """One streaming pass (vmp_mixture_fit_pass) over the rows of x (N,D) and their mask miss (N,D; nonzero = missing) under a fit
+    pack: (r (N,K), logr (N,K), x_fill (N,D), stats (K, 2+D+D*D) fp64); outputs that are not wanted are None.  r is the E-step with
+    the missing entries integrated out; x_fill is x with its missing entries replaced by sum_k r_nk E_q[x_m | k]; stats are the raw
+    moments [Nk | Wk | sx | sxx] of the completed rows, the conditional covariances included - the input of finalize().  What a
+    missing slot of x holds is never read into arithmetic.  No host synchronisation."""
+    x = L.dev_f32(x, 'x')
+    if not torch.is_tensor(pack) or pack.dim() != 2:
+        raise L.VmpError('pack must be a (K, words) tensor from fit_pack')
+    K = pack.shape[0]
+    N, D = _dims(x, K)
+    dev = x.device
+    pack = L.dev_f32(pack, 'pack', (K, L.lib().vmp_mixture_fit_pack_words(D)))
+    if pack.device != dev:
+        raise L.VmpError('pack is on %s, x on %s' % (pack.device, dev))
+    if not torch.is_tensor(miss) or tuple(miss.shape) != (N, D):
+        raise L.VmpError('the missing-data mask must be (%d,%d)' % (N, D))
+    if miss.device != dev:
+        raise L.VmpError('the missing-data mask is on %s, x on %s' % (miss.device, dev))
+    mask = _mask_u8(miss)
+    f32 = dict(dtype=torch.float32, device=dev)
+    r = torch.empty(N, K, **f32)
+    logr = torch.empty(N, K, **f32) if want_logr else None
+    x_fill = torch.empty(N, D, **f32) if want_fill else None
+    stats = torch.empty((K, L.lib().vmp_mix_stats_words(D)), dtype=torch.float64, device=dev) if want_stats else None
+    nb = L.lib().vmp_mixture_fit_workspace_bytes(N, D, K)
+    ws = L.workspace(dev, nb)
+    L.check(L.lib().vmp_mixture_fit_pass(L.ptr(x), L.ptr(mask), N, D, K, L.ptr(pack), L.ptr(r), L.ptr(logr), L.ptr(x_fill),
+                                         L.ptr(stats), L.ptr(ws), nb, L.stream()), 'vmp_mixture_fit_pass')
+    return r, logr, x_fill, stats
+
+
+def mean_filled(x, mask):
+    """x with every missing entry replaced by its column's mean over the observed entries (0 for a column with none): the copy the
+    masked loop takes the moments of r_init from."""
+    gone = mask != 0
+    xz = torch.where(gone, torch.zeros((), dtype=x.dtype, device=x.device), x)
+    cnt = (~gone).sum(0)
+    mean = (xz.double().sum(0) / cnt.clamp_min(1).double()).to(x.dtype)
+    return torch.where(gone, mean[None, :].expand_as(x), x).contiguous()
 
 
 def default_prior(K, D, device):
@@ -298,9 +356,17 @@ class VMPLoop(object):
     per iteration instead of one.  It is what meets the stated 1e-5 on the SMM's responsibilities at C5 (whose log rho is linear in
     the Mahalanobis distance with a factor (D + kappa) / 2 and reaches 1e2..1e3: beyond fp32); the default stays the fused pass.
     (A one-launch form of the iteration - posterior in the heads of the streaming launch - was built and measured in round 5:
-    bit-identical and no faster; removed in round 6.)"""
+    bit-identical and no faster; removed in round 6.)
+    miss=mask (GMM only; (N,D) on x's device, nonzero = missing): the fit on partly observed rows, the missing entries being latent
+    variables of the posterior (include/vmp_hip.h "Mixture fitting on partly observed rows").  An iteration is vmp_mix_finalize on
+    the (K, stats words) moments of the completed rows, vmp_mixture_fit_pack, and the streaming vmp_mixture_fit_pass with its
+    fixed-order reduction; run() enqueues them through vmp_mixture_fit_iterate.  filled() returns x with its gaps filled.  miss=None
+    is the loop described above, unchanged."""
 
-    def __init__(self, x, r_init, flavour, kappa=None, u_init=None, prior=None, accurate=False):
+    def __init__(self, x, r_init, flavour, kappa=None, u_init=None, prior=None, accurate=False, miss=None):
+        self.miss = None
+        if miss is not None:
+            self._check_miss(x, miss, flavour, accurate)               # before the device is touched
         self.x = L.dev_f32(x, 'x')
         self.N, self.D = self.x.shape
         self.K = K = r_init.shape[1]
@@ -317,15 +383,48 @@ class VMPLoop(object):
         D = self.D
         self.post = _post_buffers(K, D, dev)
         self.logr = None
+        self.accurate = bool(accurate)
+        self.iterations = 0
+        self.pack64 = None
+        if miss is not None:
+            self._init_masked(miss)
+            return
         self.nb = L.lib().vmp_mix_workspace_bytes(self.N, D, K)
         self.ws = torch.empty(self.nb, dtype=torch.uint8, device=dev)      # private: partials live across calls
         self.pivot = pivot_of(self.x)                                     # once per dataset
-        self.accurate = bool(accurate)
         seed_fn = L.lib().vmp_mix_stats_ws_accurate if self.accurate else L.lib().vmp_mix_stats_ws
         L.check(seed_fn(L.ptr(self.x), L.ptr(self.r), L.ptr(self.u), L.ptr(self.pivot), self.N, D, K,
                         L.ptr(self.ws), self.nb, L.stream()), 'vmp_mix_stats_ws')
-        self.iterations = 0
         self.pack64 = torch.empty(K, L.lib().vmp_mix_pack_words(D), dtype=torch.float64, device=dev) if self.accurate else None
+
+    @staticmethod
+    def _check_miss(x, miss, flavour, accurate):
+        """the refusals of a masked loop, on the host: nothing here looks at a device"""
+        if flavour != L.VMP_GMM:
+            raise L.VmpError('miss= is for the Gaussian mixture (VMP_GMM): the Student-t mixture on partly observed rows needs the joint '
+                             'q(u, x_m | k) and is not implemented')
+        if accurate:
+            raise L.VmpError('miss= and accurate=True do not combine: the masked pass has no fp64 form')
+        if not torch.is_tensor(x) or x.dim() != 2:
+            raise L.VmpError('x must be (N,D)')
+        if not torch.is_tensor(miss) or tuple(miss.shape) != tuple(x.shape):
+            raise L.VmpError('the missing-data mask has shape %s, expected %s' % (tuple(miss.shape) if torch.is_tensor(miss) else type(miss),
+                                                                                 tuple(x.shape)))
+        if miss.device != x.device:
+            raise L.VmpError('the missing-data mask is on %s, x on %s' % (miss.device, x.device))
+
+    def _init_masked(self, miss):
+        """State of the loop on partly observed rows: the moments live in self._stats (K, stats words) fp64 - seeded here from r_init
+        on a copy of x whose missing entries hold their column's observed mean, no covariance term - and every iteration is
+        vmp_mix_finalize -> vmp_mixture_fit_pack -> vmp_mixture_fit_pass (csrc/vmp_missfit.hip)."""
+        dev, N, D, K = self.x.device, self.N, self.D, self.K
+        self.miss = _mask_u8(miss)
+        self._stats = raw_stats(mean_filled(self.x, self.miss), self.r)
+        self.fpack = torch.empty(K, L.lib().vmp_mixture_fit_pack_words(D), dtype=torch.float32, device=dev)
+        self.x_fill = torch.empty_like(self.x)
+        self.nb = L.lib().vmp_mixture_fit_workspace_bytes(N, D, K)
+        self.ws = torch.empty(self.nb, dtype=torch.uint8, device=dev)
+        self.pivot = None
 
     def _fin_ptrs(self, post=True):
         """(ws, pivot, N, D, K, flavour, prior x 5, kappa, posterior x 9): the leading arguments of vmp_mix_finalize_ws / _ws64 /
@@ -334,6 +433,13 @@ class VMPLoop(object):
                                                                       self.post if post else None)
 
     def finalize(self, stats_out=None):
+        if self.miss is not None:
+            L.check(L.lib().vmp_mix_finalize(L.ptr(self._stats), *_fin_tail(self.D, self.K, self.flavour, self.prior, None, self.post),
+                                             L.stream()), 'vmp_mix_finalize')
+            p = self.post
+            L.check(L.lib().vmp_mixture_fit_pack(self.D, self.K, L.ptr(p['alpha']), L.ptr(p['beta']), L.ptr(p['m']), L.ptr(p['C']),
+                                                 L.ptr(p['v']), L.ptr(self.fpack), L.stream()), 'vmp_mixture_fit_pack')
+            return
         if self.accurate:
             L.check(L.lib().vmp_mix_finalize_ws64(*self._fin_ptrs(), L.ptr(self.pack64), L.ptr(stats_out), L.stream()), 'vmp_mix_finalize_ws64')
             return
@@ -347,6 +453,11 @@ class VMPLoop(object):
         """E-pass with fused moments on the current pack (the second launch of an iteration)"""
         if want_logr and self.logr is None:
             self.logr = torch.empty_like(self.r)
+        if self.miss is not None:
+            L.check(L.lib().vmp_mixture_fit_pass(L.ptr(self.x), L.ptr(self.miss), self.N, self.D, self.K, L.ptr(self.fpack), L.ptr(self.r),
+                                                 L.ptr(self.logr if want_logr else None), L.ptr(self.x_fill), L.ptr(self._stats),
+                                                 L.ptr(self.ws), self.nb, L.stream()), 'vmp_mixture_fit_pass')
+            return
         if self.accurate:
             L.check(L.lib().vmp_mix_estep_accurate(L.ptr(self.x), self.N, self.D, self.K, self.flavour, L.ptr(self.pack64), L.ptr(self.r),
                                                    L.ptr(self.u), L.ptr(self.logr if want_logr else None), L.stream()), 'vmp_mix_estep_accurate')
@@ -372,6 +483,14 @@ class VMPLoop(object):
         if self.accurate:
             for _ in range(int(iterations)):
                 self.step()
+            return self.r
+        if self.miss is not None:
+            p = self.post
+            L.check(L.lib().vmp_mixture_fit_iterate(L.ptr(self.x), L.ptr(self.miss), self.N, self.D, self.K, *[L.ptr(t) for t in self.prior],
+                                                    L.ptr(self.r), None, L.ptr(self.x_fill), *[L.ptr(p[k]) for k in _POST[:8]],
+                                                    L.ptr(self.fpack), L.ptr(self._stats), L.ptr(self.ws), self.nb, int(iterations),
+                                                    L.stream()), 'vmp_mixture_fit_iterate')
+            self.iterations += int(iterations)
             return self.r
         ws, pivot, *f = self._fin_ptrs()                       # f = N, D, K, flavour, prior x 5, kappa | posterior x 9
         L.check(L.lib().vmp_mix_iterate(L.ptr(self.x), *f[:10], pivot, L.ptr(self.r), L.ptr(self.u), *f[10:], ws, self.nb,
@@ -437,13 +556,25 @@ class VMPLoop(object):
 
     @property
     def stats(self):
-        """Raw moments of the current r (reduces the partials the last pass left in the workspace)."""
+        """Raw moments of the current r (reduces the partials the last pass left in the workspace; a masked loop keeps them
+        reduced: the moments of the completed rows, conditional covariances included)."""
+        if self.miss is not None:
+            return self._stats.clone()
         st = torch.empty((self.K, L.lib().vmp_mix_stats_words(self.D)), dtype=torch.float64, device=self.x.device)
         keep = {k: v.clone() for k, v in self.post.items()}
         self.finalize(stats_out=st)
         for k, v in keep.items():
             self.post[k].copy_(v)
         return st
+
+    def filled(self):
+        """x with its missing entries replaced by sum_k r_nk E_q[x_m | k] under the factor of the last iteration (observed entries
+        carry the bits of x).  Masked loops only; needs one iteration."""
+        if self.miss is None:
+            raise L.VmpError('filled() is for a loop built with miss=')
+        if self.iterations == 0:
+            raise L.VmpError('nothing filled in yet: run at least one iteration')
+        return self.x_fill
 
     def theta(self):
         p = self.post

@@ -168,6 +168,30 @@ class _Handle(object):
         return self._fn()
 
 
+def _dirichlet_init(N, K, seed, device):
+    g = torch.Generator(device='cpu').manual_seed(int(seed))
+    e = -torch.log(torch.rand(N, K, generator=g).clamp_min(1e-30))
+    return (e / e.sum(1, keepdim=True)).to(device)
+
+
+def inference_missing(x, miss, K, seed, name='inference_missing', r_init=None):
+    """inference() on partly observed rows: miss (N,D), nonzero = missing, on x's device; what the missing slots of x hold is never
+    read into arithmetic.  The missing entries are latent variables of the variational posterior, q(z_n, x_n,m) = q(z_n) q(x_n,m | z_n):
+    every iteration is the NIW update of inference() on the moments of the completed rows (conditional means and covariances) and an
+    E-step on the marginal of the observed entries, in one streaming HIP pass (csrc/vmp_missfit.hip) - unlike e_step_missing_data,
+    which zeroes the missing differences inside the full precision and cannot feed an M-step.  Returns (step, log_r_nk, theta,
+    (x_k, S_k, pi), x_filled): inference()'s four, and a handle for x with its missing entries replaced by sum_k r_nk E[x_m | x_o, k]."""
+    N, D = x.shape
+    if r_init is None:
+        r_init = _dirichlet_init(N, K, seed, x.device)
+    loop = _mix.VMPLoop(x, r_init, L.VMP_GMM, miss=miss)
+
+    def step():
+        return loop.step(want_logr=True)
+
+    return (step, _Handle(lambda: loop.logr), _Handle(loop.theta), _Handle(loop.aux), _Handle(loop.filled))
+
+
 def inference(x, K, seed, name='inference', r_init=None):
     """reference gmm.py:230-269.  Returns (step, log_r_nk, theta, (x_k, S_k, pi)) where `step()` executes one
     VMP iteration (M-step, E-step, assign) and returns the new r_nk; the other three are handles that are

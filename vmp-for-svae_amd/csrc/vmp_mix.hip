@@ -94,6 +94,45 @@ __device__ __forceinline__ v2f row16_sum2(v2f v) {
     return v2f{a, b};
 }
 
+// Four independent reductions interleaved (both halves of a 16-row sub-tile of pass_xdl_body): every butterfly step is four DPP
+// instructions back to back, so the DPP read of a register comes three instructions after the step that wrote it - more than the
+// two wait states "VALU writes a VGPR -> v_*_dpp reads that VGPR" asks for - and no step needs an s_nop.  Only the first step
+// reads registers written outside the statement, possibly by the VALU instruction just ahead of it: it keeps its two wait states
+// (s_nop 1).  Same rotations in the same order as the two-wide form: every maximum and sum is bit-identical.
+#define VMP_DPP4(OP, CTRL)                                                   \
+    "v_" OP "_f32_dpp %0, %0, %0 " CTRL " row_mask:0xf bank_mask:0xf\n\t"  \
+    "v_" OP "_f32_dpp %1, %1, %1 " CTRL " row_mask:0xf bank_mask:0xf\n\t"  \
+    "v_" OP "_f32_dpp %2, %2, %2 " CTRL " row_mask:0xf bank_mask:0xf\n\t"  \
+    "v_" OP "_f32_dpp %3, %3, %3 " CTRL " row_mask:0xf bank_mask:0xf\n\t"
+#define VMP_DPP4_FIRST(OP, CTRL)                                             \
+    "v_" OP "_f32_dpp %0, %4, %4 " CTRL " row_mask:0xf bank_mask:0xf\n\t"  \
+    "v_" OP "_f32_dpp %1, %5, %5 " CTRL " row_mask:0xf bank_mask:0xf\n\t"  \
+    "v_" OP "_f32_dpp %2, %6, %6 " CTRL " row_mask:0xf bank_mask:0xf\n\t"  \
+    "v_" OP "_f32_dpp %3, %7, %7 " CTRL " row_mask:0xf bank_mask:0xf\n\t"
+__device__ __forceinline__ void row16_max4(v2f v0, v2f v1, v2f& o0, v2f& o1) {
+    float a, b, c, d;
+    asm("s_nop 1\n\t" VMP_DPP4_FIRST("max", "row_ror:8") VMP_DPP4("max", "row_ror:4") VMP_DPP4("max", "row_ror:2")
+        VMP_DPP4("max", "row_ror:1")
+        : "=&v"(a), "=&v"(b), "=&v"(c), "=&v"(d) : "v"(v0.x), "v"(v0.y), "v"(v1.x), "v"(v1.y));
+    o0 = v2f{a, b};
+    o1 = v2f{c, d};
+}
+__device__ __forceinline__ void row16_sum4(v2f v0, v2f v1, v2f& o0, v2f& o1) {
+    float a, b, c, d;
+    asm("s_nop 1\n\t" VMP_DPP4_FIRST("add", "row_ror:8") VMP_DPP4("add", "row_ror:4") VMP_DPP4("add", "row_ror:2")
+        VMP_DPP4("add", "row_ror:1")
+        : "=&v"(a), "=&v"(b), "=&v"(c), "=&v"(d) : "v"(v0.x), "v"(v0.y), "v"(v1.x), "v"(v1.y));
+    o0 = v2f{a, b};
+    o1 = v2f{c, d};
+}
+
+// Exploration switch of the streaming loop of pass_xdl_body (tools/build_variant.sh ... -DVMP_PASS_PIPE=n), for the attribution in
+// profiles/NOTES_mix_pass_pipeline.md: 1 = straight-line full tiles, the staging still waits for the tile's stores;
+// 2 = + counted wait (the staging waits for the row loads only); 3 = + four-wide DPP reductions.
+#ifndef VMP_PASS_PIPE
+#define VMP_PASS_PIPE 3
+#endif
+
 constexpr int MOM_TERMS = 3;
 #ifndef VMP_MOM_FLUSH
 #define VMP_MOM_FLUSH 2       // tiles of 64 rows between two fp32 -> fp64 flushes of the moment accumulators (both pass kernels)
@@ -709,6 +748,10 @@ __device__ __forceinline__ void pass_xdl_body(const PassArgs& a) {
         const bool hasp = a.pivot != nullptr;
 #pragma unroll
         for (int j = 0; j < D; ++j) { const float v = pp[j]; pv[j] = hasp ? v : 0.f; }
+        // the pivot is the same in every lane: held in scalar registers (the two copies of the streaming loop below leave no
+        // vector registers for it: 247 / 256 + scratch instead of 239 / 249 at D = 8)
+#pragma unroll
+        for (int j = 0; j < D; ++j) pv[j] = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, pv[j])));
     }
 
     // ---- B operands of the y GEMM: lane (k = i16, g = kk) holds the terms of W_k its lane group multiplies (see the header).
@@ -861,11 +904,17 @@ __device__ __forceinline__ void pass_xdl_body(const PassArgs& a) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #endif
     PASS_TS(1);
-    for (long long row0 = lo; row0 < hi; row0 += TR) {
-        const int trows = (hi - row0 < TR) ? (int)(hi - row0) : TR;
-        // ---- stage this tile: lane = tile row.  fp32 image for the moment features, bf16 term image for the y GEMM
+    // The streaming loop runs in two parts over the same per-tile pieces (stage / body / flush below): whole 64-row tiles with
+    // K == 16 as straight-line code (no trip counts, no validity tests, store addresses = one base + compile-time offsets), then
+    // today's general form for what is left: the ragged last tile, or every tile when K < 16.  The pieces run in the same order on
+    // the same values in both parts, so no result depends on which part a tile went through.
+    long long row0 = lo, tbase = 0;                          // tbase: this lane's element of r/u for (row0 + kk, component i16)
+    int trows = TR;                                          // rows of the tile: read by the not-FULL bodies only (general form)
+    // ---- stage a tile: lane = tile row.  fp32 image for the moment features, bf16 term image for the y GEMM
+    auto stage = [&](auto whole_c) __attribute__((always_inline)) {
+        constexpr bool WHOLE = decltype(whole_c)::value;     // a whole tile of K == 16: every row valid
         {
-            const bool valid = row0 + lane < hi;
+            const bool valid = WHOLE || row0 + lane < hi;
             float xs[2 * DP];
 #pragma unroll
             for (int j = 0; j < 2 * DP; ++j) xs[j] = (valid && j < D) ? xr[j < D ? j : 0] - pv[j < D ? j : 0] : 0.f;
@@ -890,151 +939,167 @@ __device__ __forceinline__ void pass_xdl_body(const PassArgs& a) {
             if (n2 < hi) load_row<D>(a.x + n2 * D, xr, vec);
         }
         __builtin_amdgcn_wave_barrier();
-
-        const long long tbase = (row0 + kk) * K + i16;       // this lane's element of r/u for (row0 + kk, component i16)
-#pragma unroll 1
-        for (int n0 = 0; n0 < trows; n0 += 32) {
-            const bool full = (K == 16) && (n0 + 32 <= trows);
-            // One instance of the whole body (two sub-tiles + the moment MFMAs) per path: the operand registers of the MFMAs
-            // are written and consumed inside the same instance, so no register tuple has to be re-assembled where the two
-            // paths would merge (the first version paid 64 v_mov per body for that).
-            auto body = [&](auto full_c) __attribute__((always_inline)) {
-            constexpr bool FULL = decltype(full_c)::value;
-            unsigned As[3][4], Bs[FT][3][4];                 // [term h/m/l][k-slot pair: (sub-tile jj, v pair)]
-            auto subtile = [&](auto jj_c) __attribute__((always_inline)) {
-                constexpr int jj = decltype(jj_c)::value;
-                const int n16 = n0 + 16 * jj;                // first tile row of this 16-row sub-tile
-                if (!FULL && n16 >= trows) {                 // wave-uniform: nothing left
-                    if constexpr (STATS) {
-#pragma unroll
-                        for (int t = 0; t < 3; ++t) {
-                            As[t][2 * jj] = 0u; As[t][2 * jj + 1] = 0u;
-#pragma unroll
-                            for (int ft = 0; ft < FT; ++ft) { Bs[ft][t][2 * jj] = 0u; Bs[ft][t][2 * jj + 1] = 0u; }
-                        }
-                    }
-                    return;
-                }
-                // ---- y = W x' + b on the XDL pipe, q = |y|^2 in the accumulator registers
-                f32x4 y[D];
-                {
-                    const bf16x8 a3 = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(ai + n16 * AIS + offA3));
-#pragma unroll
-                    for (int i = 0; i < NS; ++i)
-                        y[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a3, __builtin_bit_cast(bf16x8, Bsm[i]), f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
-                }
-                if constexpr (NB > 0) {
-                    const bf16x8 a1 = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(ai + n16 * AIS + offA1));
-                    const bf16x8 a2 = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(ai + n16 * AIS + offA2));
-#pragma unroll
-                    for (int i = 0; i < NB; ++i)
-                        y[4 + i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1, __builtin_bit_cast(bf16x8, B1[i]), f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
-#pragma unroll
-                    for (int i = 0; i < NB; ++i)
-                        y[4 + i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a2, __builtin_bit_cast(bf16x8, B2[i]), y[4 + i], 0, 0, 0);
-                }
-                f32x4 q4 = y[0] * y[0], q4b = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                for (int i = 1; i < D; ++i) {
-                    if (i & 1) q4b = __builtin_elementwise_fma(y[i], y[i], q4b);
-                    else q4 = __builtin_elementwise_fma(y[i], y[i], q4);
-                }
-                q4 += q4b;
-                // register v <-> data row n16 + 4 v + kk
-                v2f lg[2], uu[2], rr[2], w[2];
-#pragma unroll
-                for (int h = 0; h < 2; ++h) {
-                    const v2f qh = v2f{q4[2 * h], q4[2 * h + 1]};
-                    lg[h] = pk_const_minus_scaled(qh, pch);                 // log2 rho
-                    if constexpr (SMM) uu[h] = v2f{pua * __builtin_amdgcn_rcpf(qh.x + pub), pua * __builtin_amdgcn_rcpf(qh.y + pub)};
-                }
-#pragma unroll
-                for (int h = 0; h < 2; ++h) {
-                    const v2f mx = row16_max2(lg[h]);
-                    lg[h] = v2f{__builtin_amdgcn_exp2f(lg[h].x - mx.x), __builtin_amdgcn_exp2f(lg[h].y - mx.y)};
-                    const v2f ssum = row16_sum2(lg[h]);
-                    v2f inv = v2f{__builtin_amdgcn_rcpf(ssum.x), __builtin_amdgcn_rcpf(ssum.y)};
-                    if constexpr (!FULL) {
-                        const bool va = row0 + n16 + 8 * h + kk < hi, vb = row0 + n16 + 8 * h + 4 + kk < hi;
-                        inv = v2f{va ? inv.x : 0.f, vb ? inv.y : 0.f};
-                    }
-                    rr[h] = lg[h] * inv;
-                    w[h] = SMM ? rr[h] * uu[h] : rr[h];
-                }
-                // ---- stores: for fixed v the 64 lanes cover rows n16 + 4 v .. + 3 x 16 components = 256 contiguous bytes
-#pragma unroll
-                for (int v = 0; v < 4; ++v) {
-                    const float rv = rr[v >> 1][v & 1];
-                    if constexpr (FULL) {
-                        float* __restrict__ ro = a.r_out + tbase + (long long)(n16 + 4 * v) * 16;
-                        __builtin_nontemporal_store(rv, ro);
-                        if constexpr (SMM) __builtin_nontemporal_store(uu[v >> 1][v & 1], a.u_out + tbase + (long long)(n16 + 4 * v) * 16);
-                        if (a.logr_out) a.logr_out[tbase + (long long)(n16 + 4 * v) * 16] = logf(rv);
-                    } else {
-                        const bool sv = (row0 + n16 + 4 * v + kk < hi) && i16 < K;
-                        const long long o = tbase + (long long)(n16 + 4 * v) * K;
-                        if (sv) {
-                            a.r_out[o] = rv;
-                            if constexpr (SMM) a.u_out[o] = uu[v >> 1][v & 1];
-                            if (a.logr_out) a.logr_out[o] = logf(rv);
-                        }
-                    }
-                }
+        tbase = (row0 + kk) * (WHOLE ? 16 : K) + i16;
+    };
+    // One instance of the whole body (two sub-tiles + the moment MFMAs) per path: the operand registers of the MFMAs
+    // are written and consumed inside the same instance, so no register tuple has to be re-assembled where the two
+    // paths would merge (the first version paid 64 v_mov per body for that).  n0: first tile row of the body, an int or
+    // (straight-line tiles) an integral_constant.
+    auto body = [&](auto full_c, auto n0_v) __attribute__((always_inline)) {
+        constexpr bool FULL = decltype(full_c)::value;
+        constexpr bool LINE = !std::is_same<decltype(n0_v), int>::value;   // part of a straight-line tile
+        const int n0 = n0_v;
+        unsigned As[3][4], Bs[FT][3][4];                 // [term h/m/l][k-slot pair: (sub-tile jj, v pair)]
+        auto subtile = [&](auto jj_c) __attribute__((always_inline)) {
+            constexpr int jj = decltype(jj_c)::value;
+            const int n16 = n0 + 16 * jj;                // first tile row of this 16-row sub-tile
+            if (!FULL && n16 >= trows) {                 // wave-uniform: nothing left
                 if constexpr (STATS) {
-                    unsigned t3[3];
 #pragma unroll
-                    for (int h = 0; h < 2; ++h) {
-                        split_bf16<MT>(w[h], t3);
+                    for (int t = 0; t < 3; ++t) {
+                        As[t][2 * jj] = 0u; As[t][2 * jj + 1] = 0u;
 #pragma unroll
-                        for (int t = 0; t < 3; ++t) As[t][2 * jj + h] = t3[t];
-                    }
-                    if constexpr (SMM) nsum += (rr[0].x + rr[0].y) + (rr[1].x + rr[1].y);
-#pragma unroll
-                    for (int ft = 0; ft < FT; ++ft) {
-                        const f32x4 fa = *reinterpret_cast<const f32x4*>(&xl[offA[ft] + n16]);
-                        const f32x4 fb = *reinterpret_cast<const f32x4*>(&xl[offB[ft] + n16]);
-                        const f32x4 pr = fa * fb;
-#pragma unroll
-                        for (int h = 0; h < 2; ++h) {
-                            split_bf16<MT>(v2f{pr[2 * h], pr[2 * h + 1]}, t3);
-#pragma unroll
-                            for (int t = 0; t < 3; ++t) Bs[ft][t][2 * jj + h] = t3[t];
-                        }
+                        for (int ft = 0; ft < FT; ++ft) { Bs[ft][t][2 * jj] = 0u; Bs[ft][t][2 * jj + 1] = 0u; }
                     }
                 }
-            };
-            using std::integral_constant;
-            subtile(integral_constant<int, 0>{});
-            subtile(integral_constant<int, 1>{});
-
-            if constexpr (STATS) {
-                bf16x8 b[FT][3];
+                return;
+            }
+            // ---- y = W x' + b on the XDL pipe, q = |y|^2 in the accumulator registers
+            f32x4 y[D];
+            {
+                const bf16x8 a3 = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(ai + n16 * AIS + offA3));
 #pragma unroll
-                for (int ft = 0; ft < FT; ++ft)
+                for (int i = 0; i < NS; ++i)
+                    y[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a3, __builtin_bit_cast(bf16x8, Bsm[i]), f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
+            }
+            if constexpr (NB > 0) {
+                const bf16x8 a1 = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(ai + n16 * AIS + offA1));
+                const bf16x8 a2 = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(ai + n16 * AIS + offA2));
 #pragma unroll
-                    for (int t = 0; t < 3; ++t)
-                        b[ft][t] = __builtin_bit_cast(bf16x8, u32x4{Bs[ft][t][0], Bs[ft][t][1], Bs[ft][t][2], Bs[ft][t][3]});
-                bf16x8 av[3];
+                for (int i = 0; i < NB; ++i)
+                    y[4 + i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1, __builtin_bit_cast(bf16x8, B1[i]), f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
 #pragma unroll
-                for (int t = 0; t < 3; ++t) av[t] = __builtin_bit_cast(bf16x8, u32x4{As[t][0], As[t][1], As[t][2], As[t][3]});
-                // h h products and the five corrections in separate fp32 accumulators (see pass_kernel)
+                for (int i = 0; i < NB; ++i)
+                    y[4 + i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a2, __builtin_bit_cast(bf16x8, B2[i]), y[4 + i], 0, 0, 0);
+            }
+            f32x4 q4 = y[0] * y[0], q4b = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-                for (int ta = 0; ta < MT; ++ta) {
+            for (int i = 1; i < D; ++i) {
+                if (i & 1) q4b = __builtin_elementwise_fma(y[i], y[i], q4b);
+                else q4 = __builtin_elementwise_fma(y[i], y[i], q4);
+            }
+            q4 += q4b;
+            // register v <-> data row n16 + 4 v + kk
+            v2f lg[2], uu[2], rr[2], w[2];
 #pragma unroll
-                    for (int tb = 0; tb + ta < MT; ++tb) {
+            for (int h = 0; h < 2; ++h) {
+                const v2f qh = v2f{q4[2 * h], q4[2 * h + 1]};
+                lg[h] = pk_const_minus_scaled(qh, pch);                 // log2 rho
+                if constexpr (SMM) uu[h] = v2f{pua * __builtin_amdgcn_rcpf(qh.x + pub), pua * __builtin_amdgcn_rcpf(qh.y + pub)};
+            }
+            v2f mx[2], ssum[2];
+            if constexpr (LINE && VMP_PASS_PIPE >= 3) {
+                row16_max4(lg[0], lg[1], mx[0], mx[1]);
 #pragma unroll
-                        for (int ft = 0; ft < FT; ++ft) {
-                            if (ta + tb == 0) acc[0][ft] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[ta], b[ft][tb], acc[0][ft], 0, 0, 0);
-                            else acs[0][ft] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[ta], b[ft][tb], acs[0][ft], 0, 0, 0);
-                        }
+                for (int h = 0; h < 2; ++h) lg[h] = v2f{__builtin_amdgcn_exp2f(lg[h].x - mx[h].x), __builtin_amdgcn_exp2f(lg[h].y - mx[h].y)};
+                row16_sum4(lg[0], lg[1], ssum[0], ssum[1]);
+            } else {
+#pragma unroll
+                for (int h = 0; h < 2; ++h) {
+                    mx[h] = row16_max2(lg[h]);
+                    lg[h] = v2f{__builtin_amdgcn_exp2f(lg[h].x - mx[h].x), __builtin_amdgcn_exp2f(lg[h].y - mx[h].y)};
+                    ssum[h] = row16_sum2(lg[h]);
+                }
+            }
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                v2f inv = v2f{__builtin_amdgcn_rcpf(ssum[h].x), __builtin_amdgcn_rcpf(ssum[h].y)};
+                if constexpr (!FULL) {
+                    const bool va = row0 + n16 + 8 * h + kk < hi, vb = row0 + n16 + 8 * h + 4 + kk < hi;
+                    inv = v2f{va ? inv.x : 0.f, vb ? inv.y : 0.f};
+                }
+                rr[h] = lg[h] * inv;
+                w[h] = SMM ? rr[h] * uu[h] : rr[h];
+            }
+            // ---- stores: for fixed v the 64 lanes cover rows n16 + 4 v .. + 3 x 16 components = 256 contiguous bytes
+#pragma unroll
+            for (int v = 0; v < 4; ++v) {
+                const float rv = rr[v >> 1][v & 1];
+                if constexpr (FULL) {
+                    float* __restrict__ ro = a.r_out + tbase + (long long)(n16 + 4 * v) * 16;
+                    __builtin_nontemporal_store(rv, ro);
+                    if constexpr (SMM) __builtin_nontemporal_store(uu[v >> 1][v & 1], a.u_out + tbase + (long long)(n16 + 4 * v) * 16);
+                    if constexpr (!LINE)
+                        if (a.logr_out) a.logr_out[tbase + (long long)(n16 + 4 * v) * 16] = logf(rv);
+                } else {
+                    const bool sv = (row0 + n16 + 4 * v + kk < hi) && i16 < K;
+                    const long long o = tbase + (long long)(n16 + 4 * v) * K;
+                    if (sv) {
+                        a.r_out[o] = rv;
+                        if constexpr (SMM) a.u_out[o] = uu[v >> 1][v & 1];
+                        if (a.logr_out) a.logr_out[o] = logf(rv);
                     }
                 }
             }
-            };   // body
-            if (full) body(std::integral_constant<bool, true>{});
-            else body(std::integral_constant<bool, false>{});
-        }
+            if constexpr (LINE) {
+                if (a.logr_out) {                        // one wave-uniform test per sub-tile, not one per store
+#pragma unroll
+                    for (int v = 0; v < 4; ++v) a.logr_out[tbase + (long long)(n16 + 4 * v) * 16] = logf(rr[v >> 1][v & 1]);
+                }
+            }
+            if constexpr (STATS) {
+                unsigned t3[3];
+#pragma unroll
+                for (int h = 0; h < 2; ++h) {
+                    split_bf16<MT>(w[h], t3);
+#pragma unroll
+                    for (int t = 0; t < 3; ++t) As[t][2 * jj + h] = t3[t];
+                }
+                if constexpr (SMM) nsum += (rr[0].x + rr[0].y) + (rr[1].x + rr[1].y);
+#pragma unroll
+                for (int ft = 0; ft < FT; ++ft) {
+                    const f32x4 fa = *reinterpret_cast<const f32x4*>(&xl[offA[ft] + n16]);
+                    const f32x4 fb = *reinterpret_cast<const f32x4*>(&xl[offB[ft] + n16]);
+                    const f32x4 pr = fa * fb;
+#pragma unroll
+                    for (int h = 0; h < 2; ++h) {
+                        split_bf16<MT>(v2f{pr[2 * h], pr[2 * h + 1]}, t3);
+#pragma unroll
+                        for (int t = 0; t < 3; ++t) Bs[ft][t][2 * jj + h] = t3[t];
+                    }
+                }
+            }
+        };
+        using std::integral_constant;
+        subtile(integral_constant<int, 0>{});
+        subtile(integral_constant<int, 1>{});
 
+        if constexpr (STATS) {
+            bf16x8 b[FT][3];
+#pragma unroll
+            for (int ft = 0; ft < FT; ++ft)
+#pragma unroll
+                for (int t = 0; t < 3; ++t)
+                    b[ft][t] = __builtin_bit_cast(bf16x8, u32x4{Bs[ft][t][0], Bs[ft][t][1], Bs[ft][t][2], Bs[ft][t][3]});
+            bf16x8 av[3];
+#pragma unroll
+            for (int t = 0; t < 3; ++t) av[t] = __builtin_bit_cast(bf16x8, u32x4{As[t][0], As[t][1], As[t][2], As[t][3]});
+            // h h products and the five corrections in separate fp32 accumulators (see pass_kernel)
+#pragma unroll
+            for (int ta = 0; ta < MT; ++ta) {
+#pragma unroll
+                for (int tb = 0; tb + ta < MT; ++tb) {
+#pragma unroll
+                    for (int ft = 0; ft < FT; ++ft) {
+                        if (ta + tb == 0) acc[0][ft] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[ta], b[ft][tb], acc[0][ft], 0, 0, 0);
+                        else acs[0][ft] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[ta], b[ft][tb], acs[0][ft], 0, 0, 0);
+                    }
+                }
+            }
+        }
+    };   // body
+
+    auto flush = [&]() __attribute__((always_inline)) {
         if constexpr (STATS) {
             // fp32 accumulators -> fp64 every VMP_MOM_FLUSH-th tile (default 2 = 128 rows; the fp64 conversions and additions run at a fraction of
             // the fp32 rate: 48 of them per tile were ~5 % of the kernel) and after the wave's last tile
@@ -1050,6 +1115,35 @@ __device__ __forceinline__ void pass_xdl_body(const PassArgs& a) {
             }
         }
         __builtin_amdgcn_wave_barrier();
+    };
+
+    using std::integral_constant;
+    // ---- whole tiles, K == 16.  A tile's r (and u) stores are issued after the request for the next tile's rows and the loop has no
+    // inner trip count, so the wait ahead of the next staging is a counted one: it covers the row loads and leaves the stores in
+    // flight (gfx950 counts loads and stores in the one vmcnt).  The compiler emits that count itself (vmcnt(16), with u vmcnt(32)):
+    // nothing is waited for by hand.  The logr_out stores sit in a wave-uniform branch, where its count stays the conservative one.
+    if (K == 16) {
+        for (; row0 + TR <= hi; row0 += TR) {
+#if VMP_PASS_PIPE == 1
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // attribution build: the wait of the rolled loop
+#endif
+            stage(integral_constant<bool, true>{});
+            body(integral_constant<bool, true>{}, integral_constant<int, 0>{});
+            body(integral_constant<bool, true>{}, integral_constant<int, 32>{});
+            flush();
+        }
+    }
+    // ---- general form: the ragged last tile, every tile of K < 16
+    for (; row0 < hi; row0 += TR) {
+        trows = (hi - row0 < TR) ? (int)(hi - row0) : TR;
+        stage(integral_constant<bool, false>{});
+#pragma unroll 1
+        for (int n0 = 0; n0 < trows; n0 += 32) {
+            const bool full = (K == 16) && (n0 + 32 <= trows);
+            if (full) body(integral_constant<bool, true>{}, n0);
+            else body(integral_constant<bool, false>{}, n0);
+        }
+        flush();
     }
 
     PASS_TS(2);

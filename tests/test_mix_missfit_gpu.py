@@ -85,6 +85,23 @@ def test_one_iteration_shape_sweep(N, D, K):
     assert torch.isfinite(loop.filled()).all()
 
 
+@pytest.mark.parametrize('N,D,K', [(270371, 2, 3), (270371, 3, 17)])
+def test_second_chunk_of_a_wave_and_waves_without_rows(N, D, K):
+    """A wave owns more than one chunk only above N = 262144: here the pass has 512 blocks, 2048 waves and 136 rows per wave, so
+    1988 waves run a full chunk of 128 rows and a ragged one of 8 - the second flush reads the wave's fp64 words back and adds to
+    them - the K > 16 form walks each chunk again per tile, one wave has 3 rows, and the last 59 waves have none and write zeros.
+    One iteration against the truth under the file's bar rule, and two runs with equal bits."""
+    x, r0, miss, truth = _case(N, D, K, 1)
+    loop = _loop(x, r0, miss)
+    r = loop.step(want_logr=True)
+    stats = loop.stats
+    assert (r.double().sum(1) - 1).abs().max().item() < 1e-6
+    _check('1 iteration N=%d D=%d K=%d' % (N, D, K), truth, r=r, logr=loop.logr, x_fill=loop.filled(), stats=stats, theta=loop.theta())
+    assert _observed_bits_kept(loop.filled(), x, miss)
+    again = _loop(x, r0, miss)
+    assert torch.equal(again.step(), r) and torch.equal(again.stats, stats)
+
+
 @pytest.mark.parametrize('N,D,K', [(1031, 8, 16), (513, 5, 33)])
 def test_five_iterations_and_run_equals_steps(N, D, K):
     x, r0, miss, truth = _case(N, D, K, 5)

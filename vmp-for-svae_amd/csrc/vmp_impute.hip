@@ -19,11 +19,8 @@
 // advances 4 rows per iteration over a contiguous range of rows that depends on (N, blocks) only.  The packs are staged in LDS once per block
 // (K = 64, D = 8: 14.6 KB).  K <= 16: the lane's component is resident in its VGPRs, loaded once per kernel; only G_k[D_o] is read
 // from LDS per cell.  K > 16: the lane reloads its component per tile and walks its tiles with a lane-local online log-sum-exp that rescales its running sum_k e_k xhat^(k); the 16 lanes are combined once per row
-// (row16_max, then D + 1 row16_sum).  The row sum is the scoring kernel's: fp64 per lane in row order, lanes 0, 16, 32, 48, the
-// waves of a block, then (second launch, one wave) the blocks in a fixed order - no atomics, the same geometry whichever outputs
-// are requested.
-#include "vmp_common.h"
-#include "vmp_linalg.h"
+// (row16_max, then D + 1 row16_sum).  The row sum is the deterministic one of vmp_mix_stream.h.
+#include "vmp_mix_stream.h"
 
 using namespace vmp;
 
@@ -33,10 +30,7 @@ constexpr int IMP_NW = 4;                 // waves per block
 constexpr int IMP_MAX_BLOCKS = 2048;
 constexpr int IMP_ROWS_PER_BLOCK = 64 * IMP_NW;
 
-inline int impute_blocks(int64_t N) {
-    const int64_t b = (N + IMP_ROWS_PER_BLOCK - 1) / IMP_ROWS_PER_BLOCK;
-    return (int)(b < 1 ? 1 : (b > IMP_MAX_BLOCKS ? IMP_MAX_BLOCKS : b));
-}
+inline int impute_blocks(int64_t N) { return stream_blocks(N, IMP_ROWS_PER_BLOCK, IMP_MAX_BLOCKS); }
 
 // ---------------------------------------------------------------------------------------------------------
 // impute packs:  [ mu_k (D) | Lambda_k lower, row-major packed (D(D+1)/2) | log w | nu | log det Lambda | 1 / nu | G_k[0..D] ]
@@ -68,30 +62,12 @@ __device__ __forceinline__ void write_impute_pack(const ImputePackArgs& a, int k
     using G = IGeo<D>;
     const double PI = 3.14159265358979323846;
     const float qnan = __builtin_nanf("");
-    double A[D * D], W[D * D];
-    const float* S = a.S + k * D * D;
-#pragma unroll
-    for (int i = 0; i < D; ++i)
-#pragma unroll
-        for (int j = 0; j < D; ++j) A[i * D + j] = 0.5 * ((double)S[i * D + j] + (double)S[j * D + i]);
-    ok = chol_lower<D>(A) && ok;
-    double sumlog = 0.0;
-#pragma unroll
-    for (int i = 0; i < D; ++i) sumlog += log(A[i * D + i]);
-    tri_inv_lower<D>(A, W);
+    double W[D * D], sumlog;
+    ok = spd_factor_inverse<D>(a.S + k * D * D, W, sumlog) && ok;
     float* p = a.pack + k * G::PACK;
 #pragma unroll
     for (int j = 0; j < D; ++j) p[j] = ok ? a.m[k * D + j] : qnan;
-    int idx = D;
-#pragma unroll
-    for (int i = 0; i < D; ++i)
-#pragma unroll
-        for (int j = 0; j <= i; ++j) {           // (S^-1)_ij = sum_{p >= i} W_pi W_pj   (W = L^-1 lower, j <= i)
-            double s = 0.0;
-#pragma unroll
-            for (int q = i; q < D; ++q) s += W[q * D + i] * W[q * D + j];
-            p[idx++] = ok ? (float)(scale * s) : qnan;
-        }
+    packed_inverse_from_factor<D>(W, scale, ok, p + D);
     p[G::LW] = ok ? (float)lw : qnan;
     p[G::NU] = ok ? (float)nu : qnan;
     p[G::LDET] = ok ? (float)(D * log(scale) - 2.0 * sumlog) : qnan;
@@ -224,26 +200,12 @@ __device__ __forceinline__ float impute_cell(const ImputeParams<D>& p, const flo
     return n_obs == 0 ? p.lw : l;                // nothing observed: the weight alone (log det Lambda_mm = log det Lambda exactly)
 }
 
-template <int D>
-__device__ __forceinline__ void store_row(float* __restrict__ p, const float (&o)[D], bool vec) {
-    if constexpr (D % 4 == 0) {
-        if (vec) {
-#pragma unroll
-            for (int j = 0; j < D / 4; ++j) reinterpret_cast<float4*>(p)[j] = make_float4(o[4 * j], o[4 * j + 1], o[4 * j + 2], o[4 * j + 3]);
-            return;
-        }
-    }
-#pragma unroll
-    for (int j = 0; j < D; ++j) p[j] = o[j];
-}
-
 // The packs are staged in LDS once per block.  KTMAX = 1: K <= 16, the lane's component is loaded from there into registers once per
 // kernel;  KTMAX = 4: the lane walks ceil(K / 16) tiles and reloads per tile.  G_k[D_o] is read from LDS per cell in both forms (a
 // select chain over registers is turned into an indexed private-memory load by the compiler: scratch inside the row loop).
 template <int D, int KTMAX>
 __global__ __launch_bounds__(IMP_NW * WAVE) void impute_kernel(ImputeArgs a) {
     using G = IGeo<D>;
-    __shared__ double wsum[IMP_NW];
     __shared__ float lds[KTMAX * 16 * G::STRIDE];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -319,38 +281,10 @@ __global__ __launch_bounds__(IMP_NW * WAVE) void impute_kernel(ImputeArgs a) {
             }
         }
     }
-    if (!a.partials) return;
-    // lanes 0, 16, 32, 48 hold the sums of the rows = kk (mod 4) of the wave's range
-    const double w = (readlane_d(acc, 0) + readlane_d(acc, 16)) + (readlane_d(acc, 32) + readlane_d(acc, 48));
-    if (lane == 0) wsum[wave] = w;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double t = wsum[0];
-#pragma unroll
-        for (int j = 1; j < IMP_NW; ++j) t += wsum[j];
-        a.partials[blockIdx.x] = t;
-    }
+    if (a.partials) wave_block_sum<IMP_NW>(acc, lane, wave, a.partials);
 }
 
-// fixed-order sum of the per-block partials: lane l adds blocks l, l + 64, ...; the 64 lane sums are added in lane order
-__global__ __launch_bounds__(WAVE) void impute_sum_kernel(const double* partials, int nblk, double* out) {
-    __shared__ double part[WAVE];
-    double s = 0.0;
-    for (int j = threadIdx.x; j < nblk; j += WAVE) s += partials[j];
-    part[threadIdx.x] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double t = part[0];
-        for (int j = 1; j < WAVE; ++j) t += part[j];
-        *out = t;
-    }
-}
-
-int impute_dims(const char* who, int D, int K) {
-    if (D < 1 || D > VMP_MAX_D) { set_error("%s: D=%d outside compiled range 1..%d", who, D, VMP_MAX_D); return VMP_E_DIM; }
-    if (K < 1 || K > VMP_MAX_K) { set_error("%s: K=%d outside compiled range 1..%d", who, K, VMP_MAX_K); return VMP_E_DIM; }
-    return 0;
-}
+__global__ __launch_bounds__(WAVE) void impute_sum_kernel(const double* partials, int nblk, double* out) { block_sum(partials, nblk, out); }
 
 template <int D>
 int launch_impute(const ImputeArgs& a, int blocks, hipStream_t s) {
@@ -368,7 +302,7 @@ int vmp_mixture_impute_pack_words(int D) { return (D < 1 || D > VMP_MAX_D) ? 0 :
 
 int vmp_mixture_impute_pack_niw(int D, int K, const float* alpha, const float* beta, const float* m, const float* C, const float* v,
                                 float* pack, void* stream) {
-    int rc = impute_dims("vmp_mixture_impute_pack_niw", D, K);
+    int rc = stream_dims("vmp_mixture_impute_pack_niw", D, K);
     if (rc) return rc;
     if (!alpha || !beta || !m || !C || !v || !pack) { set_error("vmp_mixture_impute_pack_niw: null pointer"); return VMP_E_BADARG; }
     ImputePackArgs a{K, alpha, beta, m, C, v, pack};
@@ -382,7 +316,7 @@ int vmp_mixture_impute_pack_niw(int D, int K, const float* alpha, const float* b
 
 int vmp_mixture_impute_pack_t(int D, int K, const float* log_w, const float* mu, const float* sigma, const float* nu, float* pack,
                               void* stream) {
-    int rc = impute_dims("vmp_mixture_impute_pack_t", D, K);
+    int rc = stream_dims("vmp_mixture_impute_pack_t", D, K);
     if (rc) return rc;
     if (!log_w || !mu || !sigma || !nu || !pack) { set_error("vmp_mixture_impute_pack_t: null pointer"); return VMP_E_BADARG; }
     ImputePackArgs a{K, log_w, nullptr, mu, sigma, nu, pack};
@@ -401,17 +335,12 @@ size_t vmp_mixture_impute_workspace_bytes(int64_t N, int D, int K) {
 
 int vmp_mixture_impute(const float* x, const uint8_t* mask, int64_t N, int D, int K, const float* pack, float* x_out,
                        float* logp_out, float* resp_out, double* sum_out, void* ws, size_t ws_bytes, void* stream) {
-    int rc = impute_dims("vmp_mixture_impute", D, K);
+    int rc = stream_dims("vmp_mixture_impute", D, K);
     if (rc) return rc;
     if (N <= 0) { set_error("vmp_mixture_impute: N must be positive (got %lld)", (long long)N); return VMP_E_BADARG; }
     if (!x || !mask || !pack) { set_error("vmp_mixture_impute: null pointer (%s)", !x ? "x" : !mask ? "mask" : "pack"); return VMP_E_BADARG; }
     if (!x_out && !logp_out && !resp_out && !sum_out) { set_error("vmp_mixture_impute: no output requested"); return VMP_E_BADARG; }
-    if (sum_out && (!ws || ws_bytes < vmp_mixture_impute_workspace_bytes(N, D, K))) {
-        set_error("vmp_mixture_impute: workspace too small for the row sum (%zu bytes, need %zu)", ws ? ws_bytes : (size_t)0,
-                  vmp_mixture_impute_workspace_bytes(N, D, K));
-        return VMP_E_WS;
-    }
-    if (sum_out && (reinterpret_cast<uintptr_t>(ws) & 7)) { set_error("vmp_mixture_impute: workspace not 8-byte aligned"); return VMP_E_BADARG; }
+    if ((rc = sum_workspace_check("vmp_mixture_impute", sum_out, ws, ws_bytes, vmp_mixture_impute_workspace_bytes(N, D, K))) != 0) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int blocks = impute_blocks(N);
     const long long waves = (long long)blocks * IMP_NW;
@@ -419,7 +348,7 @@ int vmp_mixture_impute(const float* x, const uint8_t* mask, int64_t N, int D, in
     a.x = x; a.mask = mask; a.pack = pack; a.x_out = x_out; a.logp = logp_out; a.resp = resp_out;
     a.partials = sum_out ? static_cast<double*>(ws) : nullptr;
     a.N = N; a.K = K;
-    a.rpw = ((N + waves - 1) / waves + 3) / 4 * 4;
+    a.rpw = rows_per_wave(N, waves, 4);
     a.vec_in = aligned16(x); a.vec_out = aligned16(x_out);
     rc = -1;
     VMP_SWITCH_DIM(D, DD, rc = launch_impute<DD>(a, blocks, s));

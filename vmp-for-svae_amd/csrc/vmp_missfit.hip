@@ -23,8 +23,7 @@
 // data row n4 + kk (vmp_impute.hip).  K <= 16: the component is resident in VGPRs and a cell is evaluated once.  K > 16: a chunk of
 // rows is walked twice - first all tiles of a row for the softmax (r, log r and x_fill are written), then tile by tile with the cell
 // evaluated again and r read back (the lane's own store), so that one set of accumulators serves every tile.
-#include "vmp_common.h"
-#include "vmp_linalg.h"
+#include "vmp_mix_stream.h"
 
 using namespace vmp;
 
@@ -35,11 +34,7 @@ constexpr int FIT_MAX_BLOCKS = 512;
 constexpr int FIT_CHUNK = 128;            // rows of a wave between two fp32 -> fp64 flushes: VMP_MOM_FLUSH (2) tiles of 64 rows in vmp_mix.hip
 constexpr int FIT_RED_GROUPS = 16;        // wave groups of the reduction block
 
-inline int fit_blocks(int64_t N) {
-    const int64_t per = (int64_t)FIT_NW * FIT_CHUNK;
-    const int64_t b = (N + per - 1) / per;
-    return (int)(b < 1 ? 1 : (b > FIT_MAX_BLOCKS ? FIT_MAX_BLOCKS : b));
-}
+inline int fit_blocks(int64_t N) { return stream_blocks(N, (int64_t)FIT_NW * FIT_CHUNK, FIT_MAX_BLOCKS); }
 
 // fit pack: [ m_k (D) | Lbar_k = v_k C_k^-1 lower, row-major packed (D(D+1)/2) | c_k ]
 template <int D>
@@ -54,14 +49,6 @@ struct FGeo {
 
 inline int fit_pack_words(int D) { return D + D * (D + 1) / 2 + 1; }
 inline int fit_moment_words(int D) { return 1 + D + D * (D + 1) / 2; }
-
-__device__ double fit_digamma(double x) {
-    double r = 0.0;
-    while (x < 10.0) { r -= 1.0 / x; x += 1.0; }
-    const double f = 1.0 / (x * x);
-    return r + log(x) - 0.5 / x
-           - f * (1.0 / 12 - f * (1.0 / 120 - f * (1.0 / 252 - f * (1.0 / 240 - f * (1.0 / 132 - f * (691.0 / 32760))))));
-}
 
 struct FitPackArgs {
     int K;
@@ -79,36 +66,18 @@ __global__ __launch_bounds__(WAVE) void fit_pack_kernel(FitPackArgs a) {
     const float qnan = __builtin_nanf("");
     double asum = 0.0;
     for (int j = 0; j < a.K; ++j) asum += a.alpha[j];
-    double A[D * D], W[D * D];
-    const float* Ck = a.C + k * D * D;
-#pragma unroll
-    for (int i = 0; i < D; ++i)
-#pragma unroll
-        for (int j = 0; j < D; ++j) A[i * D + j] = 0.5 * ((double)Ck[i * D + j] + (double)Ck[j * D + i]);
-    const bool ok = chol_lower<D>(A);
-    double sumlog = 0.0;
-#pragma unroll
-    for (int i = 0; i < D; ++i) sumlog += log(A[i * D + i]);
-    tri_inv_lower<D>(A, W);
+    double W[D * D], sumlog;
+    const bool ok = spd_factor_inverse<D>(a.C + k * D * D, W, sumlog);
     const double vk = a.v[k], bk = a.beta[k];
     float* p = a.pack + k * G::PACK;
 #pragma unroll
     for (int j = 0; j < D; ++j) p[j] = ok ? a.m[k * D + j] : qnan;
-    int idx = D;
-#pragma unroll
-    for (int i = 0; i < D; ++i)
-#pragma unroll
-        for (int j = 0; j <= i; ++j) {           // (C^-1)_ij = sum_{q >= i} W_qi W_qj   (W = L^-1 lower, j <= i)
-            double s = 0.0;
-#pragma unroll
-            for (int q = i; q < D; ++q) s += W[q * D + i] * W[q * D + j];
-            p[idx++] = ok ? (float)(vk * s) : qnan;
-        }
+    packed_inverse_from_factor<D>(W, vk, ok, p + D);
     const double logdetP = -2.0 * sumlog;
     const double ld = (logdetP > log(1e-20)) ? logdetP : 0.0;
     double sdg = 0.0;
-    for (int i = 0; i < D; ++i) sdg += fit_digamma(0.5 * (vk + 1.0 + i));
-    const double elp = fit_digamma((double)a.alpha[k]) - fit_digamma(asum);
+    for (int i = 0; i < D; ++i) sdg += digamma_d(0.5 * (vk + 1.0 + i));
+    const double elp = digamma_d((double)a.alpha[k]) - digamma_d(asum);
     const double c = elp + 0.5 * (sdg + D * 0.69314718055994530942 + ld) - 0.5 * (D / bk);
     p[G::C] = ok ? (float)c : qnan;
 }
@@ -235,19 +204,6 @@ __device__ __forceinline__ void fit_moments(const float (&dh)[D], const bool (&m
         }
 }
 
-template <int D>
-__device__ __forceinline__ void fit_store_row(float* __restrict__ p, const float (&o)[D], bool vec) {
-    if constexpr (D % 4 == 0) {
-        if (vec) {
-#pragma unroll
-            for (int j = 0; j < D / 4; ++j) reinterpret_cast<float4*>(p)[j] = make_float4(o[4 * j], o[4 * j + 1], o[4 * j + 2], o[4 * j + 3]);
-            return;
-        }
-    }
-#pragma unroll
-    for (int j = 0; j < D; ++j) p[j] = o[j];
-}
-
 // the four lanes that own component k add their sums; lane kk = 0 adds the result to the wave's fp64 words (first: replaces them)
 template <int D>
 __device__ __forceinline__ void fit_flush(float (&acc)[FGeo<D>::MW], double* __restrict__ dst, bool first, bool owner) {
@@ -339,7 +295,7 @@ __global__ __launch_bounds__(FIT_NW * WAVE) void fit_kernel(FitArgs a) {
                     const float xs = row16_sum(ax[d] * f) * inv;
                     o[d] = miss[d] ? xs : x[d];
                 }
-                if (valid && i16 == 0) fit_store_row<D>(a.x_fill + n * D, o, a.vec_out != 0);
+                if (valid && i16 == 0) store_row<D>(a.x_fill + n * D, o, a.vec_out != 0);
             }
             float rk = 0.f;
 #pragma unroll
@@ -421,12 +377,6 @@ __global__ __launch_bounds__(FIT_RED_GROUPS * WAVE) void fit_reduce_kernel(FitRe
     a.stats[(long long)k * G::SW + j] = out;
 }
 
-int fit_dims(const char* who, int D, int K) {
-    if (D < 1 || D > VMP_MAX_D) { set_error("%s: D=%d outside compiled range 1..%d", who, D, VMP_MAX_D); return VMP_E_DIM; }
-    if (K < 1 || K > VMP_MAX_K) { set_error("%s: K=%d outside compiled range 1..%d", who, K, VMP_MAX_K); return VMP_E_DIM; }
-    return 0;
-}
-
 template <int D>
 int launch_fit(const FitArgs& a, int blocks, hipStream_t s) {
     const dim3 grid(blocks), block(FIT_NW * WAVE);
@@ -438,7 +388,7 @@ int launch_fit(const FitArgs& a, int blocks, hipStream_t s) {
 // every refusal of the pass, decided on the host
 int fit_pass_check(const char* who, const float* x, const uint8_t* mask, int64_t N, int D, int K, const float* pack, const float* r_out,
                    const void* ws, size_t ws_bytes) {
-    int rc = fit_dims(who, D, K);
+    int rc = stream_dims(who, D, K);
     if (rc) return rc;
     if (N <= 0) { set_error("%s: N must be positive (got %lld)", who, (long long)N); return VMP_E_BADARG; }
     if (!x || !mask || !pack) { set_error("%s: null pointer (%s)", who, !x ? "x" : !mask ? "mask" : "pack"); return VMP_E_BADARG; }
@@ -460,7 +410,7 @@ int vmp_mixture_fit_pack_words(int D) { return (D < 1 || D > VMP_MAX_D) ? 0 : fi
 
 int vmp_mixture_fit_pack(int D, int K, const float* alpha, const float* beta, const float* m, const float* C, const float* v,
                          float* pack, void* stream) {
-    int rc = fit_dims("vmp_mixture_fit_pack", D, K);
+    int rc = stream_dims("vmp_mixture_fit_pack", D, K);
     if (rc) return rc;
     if (!alpha || !beta || !m || !C || !v || !pack) { set_error("vmp_mixture_fit_pack: null pointer"); return VMP_E_BADARG; }
     FitPackArgs a{K, alpha, beta, m, C, v, pack};
@@ -488,7 +438,7 @@ int vmp_mixture_fit_pass(const float* x, const uint8_t* mask, int64_t N, int D, 
     a.x = x; a.mask = mask; a.pack = pack; a.r = r_out; a.logr = logr_out; a.x_fill = x_fill_out;
     a.slab = static_cast<double*>(ws);
     a.N = N; a.K = K;
-    a.rpw = ((N + waves - 1) / waves + 3) / 4 * 4;
+    a.rpw = rows_per_wave(N, waves, 4);
     a.vec_in = aligned16(x); a.vec_out = aligned16(x_fill_out);
     rc = -1;
     VMP_SWITCH_DIM(D, DD, rc = launch_fit<DD>(a, blocks, s));

@@ -1174,14 +1174,6 @@ __global__ __launch_bounds__(MAX_NW1 * WAVE) void pass_xdl_kernel(PassArgs a) {
 // ---------------------------------------------------------------------------------------------------------
 // K-sized posterior update (one block per component), fp64.
 // ---------------------------------------------------------------------------------------------------------
-__device__ double digamma_d(double x) {
-    double r = 0.0;
-    while (x < 10.0) { r -= 1.0 / x; x += 1.0; }
-    const double f = 1.0 / (x * x);
-    return r + log(x) - 0.5 / x
-           - f * (1.0 / 12 - f * (1.0 / 120 - f * (1.0 / 252 - f * (1.0 / 240 - f * (1.0 / 132 - f * (691.0 / 32760))))));
-}
-
 template <int D>
 __device__ void write_pack(float* pack, int k, const double* m, const double* W /*lower, row-major full DxD*/,
                            double c, double h, double ua, double ub) {

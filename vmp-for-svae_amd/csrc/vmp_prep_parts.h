@@ -2,6 +2,7 @@
 // the launches that run them beside other work (round 6: vmp_step.hip step_final_kernel).  See vmp_prep.hip's header comment.
 #pragma once
 #include "vmp_common.h"
+#include "vmp_linalg.h"
 #include "vmp_step_parts.h"
 
 namespace vmp {
@@ -23,14 +24,6 @@ __device__ __forceinline__ void prep_sync() {
 }
 
 __device__ __forceinline__ double softplus_d(double x) { return x > 0.0 ? x + log1p(exp(-x)) : log1p(exp(x)); }
-
-__device__ inline double digamma_dd(double x) {
-    double r = 0.0;
-    while (x < 10.0) { r -= 1.0 / x; x += 1.0; }
-    const double f = 1.0 / (x * x);
-    return r + log(x) - 0.5 / x
-           - f * (1.0 / 12 - f * (1.0 / 120 - f * (1.0 / 252 - f * (1.0 / 240 - f * (1.0 / 132 - f * (691.0 / 32760))))));
-}
 
 // L_k = tril(raw) with softplus on the diagonal (svae.py:347-352), rounded to fp32 as the tensors the reference holds
 template <int L>
@@ -258,7 +251,7 @@ __device__ __forceinline__ void theta_pack_body(const ThetaArgs& a, const int k)
     const int i = lane / L, j = lane % L;
     const bool in = lane < L * L;
     const double asum = wave_sum_d(lane < K ? (double)a.alpha[lane] + 1.0 : 0.0);            // dirichlet.natural_to_standard
-    const double dg = lane < 2 ? digamma_dd(lane == 0 ? (double)a.alpha[k] + 1.0 : asum) : 0.0;
+    const double dg = lane < 2 ? digamma_d(lane == 0 ? (double)a.alpha[k] + 1.0 : asum) : 0.0;
     const double elp = __shfl(dg, 0) - __shfl(dg, 1);
     const double beta = (double)a.beta[k], nu = (double)a.vhat[k] - (double)(L + 2);         // niw.natural_to_standard
     const double inv_nu = 1.0 / nu;
@@ -324,7 +317,7 @@ __device__ __forceinline__ void smm_theta_pack_body(const SmmThetaArgs& a, const
     const int i = lane / L, j = lane % L;
     const bool in = lane < L * L;
     const double asum = wave_sum_d(lane < K ? (double)a.alpha[lane] + 1.0 : 0.0);            // dirichlet.natural_to_standard
-    const double dg = lane < 2 ? digamma_dd(lane == 0 ? (double)a.alpha[k] + 1.0 : asum) : 0.0;
+    const double dg = lane < 2 ? digamma_d(lane == 0 ? (double)a.alpha[k] + 1.0 : asum) : 0.0;
     const double elp = __shfl(dg, 0) - __shfl(dg, 1);
     const float* __restrict__ raw = a.Lraw + (size_t)k * L * L;
     double lij = 0.0;

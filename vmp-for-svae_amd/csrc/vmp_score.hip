@@ -7,16 +7,11 @@
 // Two K-sized kernels build the score pack (fp64 inside, rounded once on the way out, one thread per component as pack_kernel of
 // vmp_mix.hip); one streaming kernel reads x once and writes N numbers (and, on request, the (N,K) predictive responsibilities).
 //
-// Lane map of the streaming kernel (the E-part's, vmp_mix.hip): lane l = (i16 = l & 15, kk = l >> 4) owns component
-// k = i16 + 16 t of every component tile t < KT = ceil(K / 16) - W_k, m_k, c_k, h_k, a_k resident in its VGPRs, loaded once per
-// kernel - and, per loop iteration, the two data rows n8 + kk and n8 + 4 + kk: the 16 lanes of a DPP row cover one data row,
-// max and sum over k are row_ror all-reduces (vmp_common.h), and a wave advances 8 rows per iteration over a contiguous range
-// of rows that depends on (N, blocks) only.  No LDS in the loop, no scalar loads in the loop, no packed fp32 (Makefile).
-// The row sum: the lanes with i16 = 0 add their rows' fp32 results into an fp64 register in row order; lanes 0, 16, 32, 48, then
-// the waves of a block, then (second launch, one wave) the blocks are added in a fixed order - no atomics, and the same
-// geometry whichever outputs are requested, so the sum is bit-identical from run to run and from one output set to another.
-#include "vmp_common.h"
-#include "vmp_linalg.h"
+// Lane map of the streaming kernel (vmp_mix_stream.h; the E-part's, vmp_mix.hip): the lane's components - W_k, m_k, c_k, h_k, a_k of
+// every tile t < KT = ceil(K / 16) - are resident in its VGPRs, loaded once per kernel, and per loop iteration it owns the two data
+// rows n8 + kk and n8 + 4 + kk: a wave advances 8 rows per iteration.  No LDS in the loop, no scalar loads in the loop, no packed
+// fp32 (Makefile).  The row sum is the deterministic one of vmp_mix_stream.h.
+#include "vmp_mix_stream.h"
 
 using namespace vmp;
 
@@ -26,10 +21,7 @@ constexpr int SCORE_NW = 4;               // waves per block
 constexpr int SCORE_MAX_BLOCKS = 2048;    // 8 waves per SIMD on 256 CUs
 constexpr int SCORE_ROWS_PER_BLOCK = 64 * SCORE_NW;   // below that a block is not worth its launch slot
 
-inline int score_blocks(int64_t N) {
-    const int64_t b = (N + SCORE_ROWS_PER_BLOCK - 1) / SCORE_ROWS_PER_BLOCK;
-    return (int)(b < 1 ? 1 : (b > SCORE_MAX_BLOCKS ? SCORE_MAX_BLOCKS : b));
-}
+inline int score_blocks(int64_t N) { return stream_blocks(N, SCORE_ROWS_PER_BLOCK, SCORE_MAX_BLOCKS); }
 
 // ---------------------------------------------------------------------------------------------------------
 // score packs:  [ m_k (D) | W_k lower, row-major packed (D(D+1)/2) | c_k | h_k | a_k | 0 ]   (natural-log units)
@@ -39,22 +31,6 @@ struct ScorePackArgs {
     const float *w, *beta, *m, *S, *nu;     // NIW: alpha, beta, m, C, v;  explicit: log_w, -, mu, sigma, nu
     float* pack;
 };
-
-// A = L L^T (A symmetrised), W = L^-1, sumlog = sum_i log L_ii; false when A is not SPD
-template <int D>
-__device__ __forceinline__ bool scale_factor(const float* S, double (&W)[D * D], double& sumlog) {
-    double A[D * D];
-#pragma unroll
-    for (int i = 0; i < D; ++i)
-#pragma unroll
-        for (int j = 0; j < D; ++j) A[i * D + j] = 0.5 * ((double)S[i * D + j] + (double)S[j * D + i]);
-    const bool ok = chol_lower<D>(A);
-    sumlog = 0.0;
-#pragma unroll
-    for (int i = 0; i < D; ++i) sumlog += log(A[i * D + i]);
-    tri_inv_lower<D>(A, W);
-    return ok;
-}
 
 template <int D>
 __device__ __forceinline__ void write_score_pack(float* pack, int k, const float* m, const double (&W)[D * D], bool ok,
@@ -84,7 +60,7 @@ __global__ __launch_bounds__(WAVE) void score_pack_niw_kernel(ScorePackArgs a) {
     double asum = 0.0;
     for (int j = 0; j < a.K; ++j) asum += a.w[j];
     double W[D * D], sumlog;
-    bool ok = scale_factor<D>(a.S + k * D * D, W, sumlog);
+    bool ok = spd_factor_inverse<D>(a.S + k * D * D, W, sumlog);
     const double beta = a.beta[k], nup = (double)a.nu[k] + 1.0 - D;
     ok = ok && nup > 0.0;
     const double sa = beta / (1.0 + beta), h = 0.5 * (nup + D), s = nup * sa;
@@ -100,7 +76,7 @@ __global__ __launch_bounds__(WAVE) void score_pack_t_kernel(ScorePackArgs a) {
     if (k >= a.K) return;
     const double PI = 3.14159265358979323846;
     double W[D * D], sumlog;
-    bool ok = scale_factor<D>(a.S + k * D * D, W, sumlog);
+    bool ok = spd_factor_inverse<D>(a.S + k * D * D, W, sumlog);
     const double nu = a.nu[k];
     ok = ok && nu > 0.0;
     const double h = 0.5 * (nu + D);
@@ -167,7 +143,6 @@ __device__ __forceinline__ float score_row(const float (&t)[KT], float (&e)[KT],
 template <int D, int KT>
 __global__ __launch_bounds__(SCORE_NW * WAVE) void score_kernel(ScoreArgs a) {
     using G = Geo<D>;
-    __shared__ double wsum[SCORE_NW];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int i16 = lane & 15, kk = lane >> 4;
@@ -222,38 +197,10 @@ __global__ __launch_bounds__(SCORE_NW * WAVE) void score_kernel(ScoreArgs a) {
             }
         }
     }
-    if (!a.partials) return;
-    // lanes 0, 16, 32, 48 hold the sums of the rows = kk (mod 4) of the wave's range
-    const double w = (readlane_d(acc, 0) + readlane_d(acc, 16)) + (readlane_d(acc, 32) + readlane_d(acc, 48));
-    if (lane == 0) wsum[wave] = w;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double s = wsum[0];
-#pragma unroll
-        for (int j = 1; j < SCORE_NW; ++j) s += wsum[j];
-        a.partials[blockIdx.x] = s;
-    }
+    if (a.partials) wave_block_sum<SCORE_NW>(acc, lane, wave, a.partials);
 }
 
-// fixed-order sum of the per-block partials: lane l adds blocks l, l + 64, ...; the 64 lane sums are added in lane order
-__global__ __launch_bounds__(WAVE) void score_sum_kernel(const double* partials, int nblk, double* out) {
-    __shared__ double part[WAVE];
-    double s = 0.0;
-    for (int j = threadIdx.x; j < nblk; j += WAVE) s += partials[j];
-    part[threadIdx.x] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double t = part[0];
-        for (int j = 1; j < WAVE; ++j) t += part[j];
-        *out = t;
-    }
-}
-
-int score_dims(const char* who, int D, int K) {
-    if (D < 1 || D > VMP_MAX_D) { set_error("%s: D=%d outside compiled range 1..%d", who, D, VMP_MAX_D); return VMP_E_DIM; }
-    if (K < 1 || K > VMP_MAX_K) { set_error("%s: K=%d outside compiled range 1..%d", who, K, VMP_MAX_K); return VMP_E_DIM; }
-    return 0;
-}
+__global__ __launch_bounds__(WAVE) void score_sum_kernel(const double* partials, int nblk, double* out) { block_sum(partials, nblk, out); }
 
 template <int D>
 int launch_score(const ScoreArgs& a, int blocks, hipStream_t s) {
@@ -273,7 +220,7 @@ extern "C" {
 
 int vmp_mix_score_pack_niw(int D, int K, const float* alpha, const float* beta, const float* m, const float* C, const float* v,
                            float* pack, void* stream) {
-    int rc = score_dims("vmp_mix_score_pack_niw", D, K);
+    int rc = stream_dims("vmp_mix_score_pack_niw", D, K);
     if (rc) return rc;
     if (!alpha || !beta || !m || !C || !v || !pack) { set_error("vmp_mix_score_pack_niw: null pointer"); return VMP_E_BADARG; }
     ScorePackArgs a{K, alpha, beta, m, C, v, pack};
@@ -287,7 +234,7 @@ int vmp_mix_score_pack_niw(int D, int K, const float* alpha, const float* beta, 
 
 int vmp_mix_score_pack_t(int D, int K, const float* log_w, const float* mu, const float* sigma, const float* nu, float* pack,
                          void* stream) {
-    int rc = score_dims("vmp_mix_score_pack_t", D, K);
+    int rc = stream_dims("vmp_mix_score_pack_t", D, K);
     if (rc) return rc;
     if (!log_w || !mu || !sigma || !nu || !pack) { set_error("vmp_mix_score_pack_t: null pointer"); return VMP_E_BADARG; }
     ScorePackArgs a{K, log_w, nullptr, mu, sigma, nu, pack};
@@ -307,23 +254,18 @@ size_t vmp_mix_score_workspace_bytes(int64_t N, int D, int K) {
 int vmp_mix_score(const float* x, int64_t N, int D, int K, const float* pack, float* logp_out, float* resp_out,
                   double* sum_out, void* ws, size_t ws_bytes, void* stream) {
     if (N <= 0) { set_error("vmp_mix_score: N must be positive (got %lld)", (long long)N); return VMP_E_BADARG; }
-    int rc = score_dims("vmp_mix_score", D, K);
+    int rc = stream_dims("vmp_mix_score", D, K);
     if (rc) return rc;
     if (!x || !pack) { set_error("vmp_mix_score: null pointer (%s)", !x ? "x" : "pack"); return VMP_E_BADARG; }
     if (!logp_out && !resp_out && !sum_out) { set_error("vmp_mix_score: no output requested"); return VMP_E_BADARG; }
-    if (sum_out && (!ws || ws_bytes < vmp_mix_score_workspace_bytes(N, D, K))) {
-        set_error("vmp_mix_score: workspace too small for the row sum (%zu bytes, need %zu)", ws ? ws_bytes : (size_t)0,
-                  vmp_mix_score_workspace_bytes(N, D, K));
-        return VMP_E_WS;
-    }
-    if (sum_out && (reinterpret_cast<uintptr_t>(ws) & 7)) { set_error("vmp_mix_score: workspace not 8-byte aligned"); return VMP_E_BADARG; }
+    if ((rc = sum_workspace_check("vmp_mix_score", sum_out, ws, ws_bytes, vmp_mix_score_workspace_bytes(N, D, K))) != 0) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int blocks = score_blocks(N);
     const long long waves = (long long)blocks * SCORE_NW;
     ScoreArgs a{};
     a.x = x; a.pack = pack; a.logp = logp_out; a.resp = resp_out; a.partials = sum_out ? static_cast<double*>(ws) : nullptr;
     a.N = N; a.K = K;
-    a.rpw = ((N + waves - 1) / waves + 7) / 8 * 8;
+    a.rpw = rows_per_wave(N, waves, 8);
     a.vec_ok = aligned16(x);
     rc = -1;
     VMP_SWITCH_DIM(D, DD, rc = launch_score<DD>(a, blocks, s));

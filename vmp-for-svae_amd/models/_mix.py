@@ -151,27 +151,32 @@ def _score_dims(x, m, what):
     return N, D, K
 
 
+_NIW = (('alpha_k', 'beta_k', 'm_k', 'C_k', 'v_k'), lambda K, D: ((K,), (K,), (K, D), (K, D, D), (K,)))
+_STUDENT = (('log_w', 'mu', 'sigma', 'nu'), lambda K, D: ((K,), (K, D), (K, D, D), (K,)))
+
+
+def _k_pack(entry, words_entry, ops, names, shapes, device):
+    """One K-sized pack (score, impute or fit) from K-sized operands: shapes checked BEFORE the library or the device is touched,
+    then dev_f32, the (K, words_entry(D)) buffer and the C entry point"""
+    K, D = next(shp for shp in shapes if len(shp) == 2)
+    ops = [_kd(t, n, shp) for t, n, shp in zip(ops, names, shapes)]
+    ops = [L.dev_f32(t.detach().to(torch.float32), n) for t, n in zip(ops, names)]
+    pack = torch.empty(K, getattr(L.lib(), words_entry)(D), dtype=torch.float32, device=device)
+    L.check(getattr(L.lib(), entry)(D, K, *[L.ptr(t) for t in ops], L.ptr(pack), L.stream()), entry)
+    return pack
+
+
 def score_pack_niw(alpha_k, beta_k, m_k, C_k, v_k):
     """Score pack of the GMM posterior predictive (vmp_mix_score_pack_niw; Bishop 10.81-10.82) from the NIW posterior
     (alpha (K), beta (K), m (K,D), C (K,D,D), v (K)) = gmm.inference's theta."""
-    K, D = m_k.shape
-    ops = [_kd(t, n, shp) for t, n, shp in ((alpha_k, 'alpha_k', (K,)), (beta_k, 'beta_k', (K,)), (m_k, 'm_k', (K, D)),
-                                            (C_k, 'C_k', (K, D, D)), (v_k, 'v_k', (K,)))]
-    ops = [L.dev_f32(t.detach().to(torch.float32), n) for t, n in zip(ops, ('alpha_k', 'beta_k', 'm_k', 'C_k', 'v_k'))]
-    pack = torch.empty(K, L.lib().vmp_mix_pack_words(D), dtype=torch.float32, device=m_k.device)
-    L.check(L.lib().vmp_mix_score_pack_niw(D, K, *[L.ptr(t) for t in ops], L.ptr(pack), L.stream()), 'vmp_mix_score_pack_niw')
-    return pack
+    return _k_pack('vmp_mix_score_pack_niw', 'vmp_mix_pack_words', (alpha_k, beta_k, m_k, C_k, v_k), _NIW[0], _NIW[1](*m_k.shape),
+                   m_k.device)
 
 
 def score_pack_t(log_w, mu, sigma, nu):
     """Score pack of an explicit Student-t mixture (vmp_mix_score_pack_t; reference student_t.py:31-37): log_w (K), mu (K,D),
     sigma (K,D,D) scale matrices, nu (K) degrees of freedom."""
-    K, D = mu.shape
-    ops = [_kd(t, n, shp) for t, n, shp in ((log_w, 'log_w', (K,)), (mu, 'mu', (K, D)), (sigma, 'sigma', (K, D, D)), (nu, 'nu', (K,)))]
-    ops = [L.dev_f32(t.detach().to(torch.float32), n) for t, n in zip(ops, ('log_w', 'mu', 'sigma', 'nu'))]
-    pack = torch.empty(K, L.lib().vmp_mix_pack_words(D), dtype=torch.float32, device=mu.device)
-    L.check(L.lib().vmp_mix_score_pack_t(D, K, *[L.ptr(t) for t in ops], L.ptr(pack), L.stream()), 'vmp_mix_score_pack_t')
-    return pack
+    return _k_pack('vmp_mix_score_pack_t', 'vmp_mix_pack_words', (log_w, mu, sigma, nu), _STUDENT[0], _STUDENT[1](*mu.shape), mu.device)
 
 
 def mixture_score(x, pack, want_logp=True, want_resp=False, want_sum=True):
@@ -202,28 +207,37 @@ def _impute_dims(x, miss, m, what):
     return N, D, K
 
 
-def _impute_pack(entry, ops, names, shapes, K, D, device):
-    ops = [_kd(t, n, shp) for t, n, shp in zip(ops, names, shapes)]
-    ops = [L.dev_f32(t.detach().to(torch.float32), n) for t, n in zip(ops, names)]
-    pack = torch.empty(K, L.lib().vmp_mixture_impute_pack_words(D), dtype=torch.float32, device=device)
-    L.check(getattr(L.lib(), entry)(D, K, *[L.ptr(t) for t in ops], L.ptr(pack), L.stream()), entry)
-    return pack
-
-
 def impute_pack_niw(alpha_k, beta_k, m_k, C_k, v_k):
     """Impute pack of the GMM posterior predictive (vmp_mixture_impute_pack_niw) from the NIW posterior (alpha (K), beta (K), m (K,D),
     C (K,D,D), v (K)) = gmm.inference's theta: the mixture score_pack_niw scores."""
-    K, D = m_k.shape
-    return _impute_pack('vmp_mixture_impute_pack_niw', (alpha_k, beta_k, m_k, C_k, v_k), ('alpha_k', 'beta_k', 'm_k', 'C_k', 'v_k'),
-                        ((K,), (K,), (K, D), (K, D, D), (K,)), K, D, m_k.device)
+    return _k_pack('vmp_mixture_impute_pack_niw', 'vmp_mixture_impute_pack_words', (alpha_k, beta_k, m_k, C_k, v_k), _NIW[0],
+                   _NIW[1](*m_k.shape), m_k.device)
 
 
 def impute_pack_t(log_w, mu, sigma, nu):
     """Impute pack of an explicit Student-t mixture (vmp_mixture_impute_pack_t): log_w (K), mu (K,D), sigma (K,D,D) scale matrices,
     nu (K) degrees of freedom."""
-    K, D = mu.shape
-    return _impute_pack('vmp_mixture_impute_pack_t', (log_w, mu, sigma, nu), ('log_w', 'mu', 'sigma', 'nu'),
-                        ((K,), (K, D), (K, D, D), (K,)), K, D, mu.device)
+    return _k_pack('vmp_mixture_impute_pack_t', 'vmp_mixture_impute_pack_words', (log_w, mu, sigma, nu), _STUDENT[0],
+                   _STUDENT[1](*mu.shape), mu.device)
+
+
+def _masked_operands(x, miss, pack, words_entry, hint):
+    """(x fp32 on the device, uint8 mask, pack, N, D, K) of a streaming pass over partly observed rows, validated: a pack of another
+    kind (a score pack is D + D(D+1)/2 + 4 words) would make the kernel read past its end"""
+    x = L.dev_f32(x, 'x')
+    if not torch.is_tensor(pack) or pack.dim() != 2:
+        raise L.VmpError('pack must be a (K, words) tensor from %s' % hint)
+    K = pack.shape[0]
+    N, D = _dims(x, K)
+    dev = x.device
+    pack = L.dev_f32(pack, 'pack', (K, getattr(L.lib(), words_entry)(D)))
+    if pack.device != dev:
+        raise L.VmpError('pack is on %s, x on %s' % (pack.device, dev))
+    if not torch.is_tensor(miss) or tuple(miss.shape) != (N, D):
+        raise L.VmpError('the missing-data mask must be (%d,%d)' % (N, D))
+    if miss.device != dev:
+        raise L.VmpError('the missing-data mask is on %s, x on %s' % (miss.device, dev))
+    return x, _mask_u8(miss), pack, N, D, K
 
 
 def mixture_impute(x, miss, pack, want_x=True, want_logp=True, want_resp=False, want_sum=False, inplace=False):
@@ -237,21 +251,8 @@ def mixture_impute(x, miss, pack, want_x=True, want_logp=True, want_resp=False, 
     What a missing slot of x holds is never read into arithmetic (NaN there is fine).  A row whose every weight is -inf gets
     logp = -inf, resp = 0 and 0 in its missing entries.  Everything stays on the device: no host synchronisation."""
     xin = x
-    x = L.dev_f32(x, 'x')
-    if not torch.is_tensor(pack) or pack.dim() != 2:
-        raise L.VmpError('pack must be a (K, words) tensor from impute_pack_niw / impute_pack_t')
-    K = pack.shape[0]
-    N, D = _dims(x, K)
+    x, mask, pack, N, D, K = _masked_operands(x, miss, pack, 'vmp_mixture_impute_pack_words', 'impute_pack_niw / impute_pack_t')
     dev = x.device
-    # a score pack (D + D(D+1)/2 + 4 words) passed by mistake would make the kernel read past its end
-    pack = L.dev_f32(pack, 'pack', (K, L.lib().vmp_mixture_impute_pack_words(D)))
-    if pack.device != dev:
-        raise L.VmpError('pack is on %s, x on %s' % (pack.device, dev))
-    if not torch.is_tensor(miss) or tuple(miss.shape) != (N, D):
-        raise L.VmpError('the missing-data mask must be (%d,%d)' % (N, D))
-    if miss.device != dev:
-        raise L.VmpError('the missing-data mask is on %s, x on %s' % (miss.device, dev))
-    mask = _mask_u8(miss)
     x_out = None
     if want_x:
         if inplace and x.data_ptr() != xin.data_ptr():
@@ -281,13 +282,8 @@ def _mask_u8(miss):
 def fit_pack(alpha_k, beta_k, m_k, C_k, v_k):
     """Fit pack of the NIW posterior (vmp_mixture_fit_pack): [m | v C^-1 packed lower | E log pi + 1/2 E log|Lambda| - D / (2 beta)]
     per component - what mixture_fit_pass evaluates the E-step on partly observed rows from."""
-    K, D = m_k.shape
-    names = ('alpha_k', 'beta_k', 'm_k', 'C_k', 'v_k')
-    ops = [_kd(t, n, shp) for t, n, shp in zip((alpha_k, beta_k, m_k, C_k, v_k), names, ((K,), (K,), (K, D), (K, D, D), (K,)))]
-    ops = [L.dev_f32(t.detach().to(torch.float32), n) for t, n in zip(ops, names)]
-    pack = torch.empty(K, L.lib().vmp_mixture_fit_pack_words(D), dtype=torch.float32, device=m_k.device)
-    L.check(L.lib().vmp_mixture_fit_pack(D, K, *[L.ptr(t) for t in ops], L.ptr(pack), L.stream()), 'vmp_mixture_fit_pack')
-    return pack
+    return _k_pack('vmp_mixture_fit_pack', 'vmp_mixture_fit_pack_words', (alpha_k, beta_k, m_k, C_k, v_k), _NIW[0], _NIW[1](*m_k.shape),
+                   m_k.device)
 
 
 def mixture_fit_pass(x, miss, pack, want_logr=False, want_fill=False, want_stats=True):
@@ -296,20 +292,8 @@ def mixture_fit_pass(x, miss, pack, want_logr=False, want_fill=False, want_stats
     the missing entries integrated out; x_fill is x with its missing entries replaced by sum_k r_nk E_q[x_m | k]; stats are the raw
     moments [Nk | Wk | sx | sxx] of the completed rows, the conditional covariances included - the input of finalize().  What a
     missing slot of x holds is never read into arithmetic.  No host synchronisation."""
-    x = L.dev_f32(x, 'x')
-    if not torch.is_tensor(pack) or pack.dim() != 2:
-        raise L.VmpError('pack must be a (K, words) tensor from fit_pack')
-    K = pack.shape[0]
-    N, D = _dims(x, K)
+    x, mask, pack, N, D, K = _masked_operands(x, miss, pack, 'vmp_mixture_fit_pack_words', 'fit_pack')
     dev = x.device
-    pack = L.dev_f32(pack, 'pack', (K, L.lib().vmp_mixture_fit_pack_words(D)))
-    if pack.device != dev:
-        raise L.VmpError('pack is on %s, x on %s' % (pack.device, dev))
-    if not torch.is_tensor(miss) or tuple(miss.shape) != (N, D):
-        raise L.VmpError('the missing-data mask must be (%d,%d)' % (N, D))
-    if miss.device != dev:
-        raise L.VmpError('the missing-data mask is on %s, x on %s' % (miss.device, dev))
-    mask = _mask_u8(miss)
     f32 = dict(dtype=torch.float32, device=dev)
     r = torch.empty(N, K, **f32)
     logr = torch.empty(N, K, **f32) if want_logr else None

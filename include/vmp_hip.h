@@ -229,6 +229,42 @@ int    vmp_mixture_impute(const float* x, const uint8_t* mask, int64_t N, int D,
                           float* logp_out, float* resp_out, double* sum_out, void* ws, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Mixture sampling (csrc/vmp_sample.hip): seeded draws and multiple imputation under a mixture of Student-t densities, one launch
+ * ------------------------------------------------------------------------------------------------
+ * `draws` independent draws of the missing entries of every row from p(x_m | x_o) under an impute pack (the notation of "Mixture
+ * imputation" above); a row with nothing observed is a draw from the mixture itself.  For row n and draw s:
+ *   component  resp_k = exp(l_k - logsumexp l), the numbers vmp_mixture_impute returns;  z = the first k with
+ *              sum_{j<=k} resp_j > u_z, or, if rounding leaves the total below u_z, the last k with resp_k > 0;
+ *   scale      g ~ Gamma(shape a = (nu_z + D_o)/2, rate 1/2) (chi-square with nu_z + D_o degrees of freedom) by Marsaglia-Tsang
+ *              (2000) on a' = a (a >= 1) or a + 1 (a < 1): d = a' - 1/3, c = 1/sqrt(9 d); attempt t = 0 .. 7 takes a normal n_t and a
+ *              uniform u_t, w = 1 + c n_t, v = w^3, and is accepted if w > 0 and log u_t < n_t^2/2 + d - d v + d log v; gamma = d v of
+ *              the first accepted attempt (d itself if all 8 are rejected: probability <= 0.0484^8 < 3.1e-11, 0.0484 being the
+ *              rejection probability at a' = 1, where it is largest); g = 2 gamma, times u_b^(1/a) when a < 1; g >= FLT_MIN;
+ *   entries    x_m = xhat_m^(z) + sqrt((nu_z + q_z) / g) R_z^-T eps, eps_i standard normal, indexed by the coordinate i (observed
+ *              coordinates discard theirs); observed entries are copied bit for bit.
+ * This is the conditional Student-t t_{nu+D_o}(xhat, (nu + q)/(nu + D_o) Lambda_mm^-1) of each component, mixed by resp.
+ * Random stream: Philox4x32-7 (the generator of the in-kernel noise below), key = seed, counter = (row low, row high, s, 0x6d78a500 + b)
+ * with row = row0 + n the absolute row index and b the block - nothing else enters, so rows [a, b) drawn with row0 = a are rows a .. b
+ * of the whole call.  A uniform is (top 24 bits of a word + 1/2) 2^-24, rounded once to fp32 and kept at most 1 - 2^-24 (the one
+ * value that would round to 1.0): never 0, never 1; a normal pair is
+ * r (cos, sin) with r = sqrt(-2 log((top 20 bits + 1/2) 2^-20)) and the angle = low 12 bits x 2^-12 revolutions of ONE word
+ * (oracle/philox.py box_muller8).
+ *   b = 0:       word 0 -> u_z, word 1 -> u_b
+ *   b = 1:       word t -> (eps_2t, eps_2t+1), t = 0 .. 3
+ *   b = 16 + t:  attempt t: word 0 -> n_t (the cosine of its pair), word 1 -> u_t
+ * x (N,D), mask (N,D) uint8, nonzero = missing; x == NULL && mask == NULL: every entry of every row is missing (plain draws from the
+ * mixture).  What a missing slot of x holds never enters arithmetic.  x_out (draws,N,D); z_out (draws,N) int32 or NULL.  A row whose
+ * every log w is -inf gets 0 in its missing entries and z = -1; a NaN pack row as the builders write it (log w
+ * included) makes every l_k term of the row's softmax NaN: NaN draws and z = -1.  With nothing observed (D_o = 0, and always when
+ * x == NULL) l_k = log w_k alone, so a pack row with a finite log w but NaN in mu, Lambda or nu is chosen with its weight and gives NaN
+ * entries with z = that k, while the other components draw normally.  No workspace, no atomics,
+ * one launch: every output is bit-identical from run to run and whether or not z_out is requested.
+ * Errors (decided before any launch): VMP_E_DIM (D, K outside 1..VMP_MAX_D / 1..VMP_MAX_K), VMP_E_BADARG (N < 1, draws < 1, row0 < 0,
+ * exactly one of x and mask NULL, pack or x_out NULL).                                                                       */
+int    vmp_mixture_sample(const float* x, const uint8_t* mask, int64_t N, int D, int K, const float* impute_pack, uint64_t seed,
+                          int64_t row0, int draws, float* x_out, int32_t* z_out, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Mixture fitting on partly observed rows (csrc/vmp_missfit.hip): variational Bayes with the missing entries as latent variables
  * ------------------------------------------------------------------------------------------------
  * The variational GMM of models/gmm.py (NIW posterior (alpha, beta, m, C, v) per component, C the inverse scale, P = C^-1) on rows

@@ -45,6 +45,7 @@ _SIGNATURES = {
     'vmp_mixture_impute_pack_t': (_c.c_int, [_c.c_int, _c.c_int] + [_P] * 6),
     'vmp_mixture_impute_workspace_bytes': (_c.c_size_t, [_c.c_int64, _c.c_int, _c.c_int]),
     'vmp_mixture_impute': (_c.c_int, [_P, _P, _c.c_int64, _c.c_int, _c.c_int, _P, _P, _P, _P, _P, _P, _c.c_size_t, _P]),
+    'vmp_mixture_sample': (_c.c_int, [_P, _P, _c.c_int64, _c.c_int, _c.c_int, _P, _c.c_uint64, _c.c_int64, _c.c_int, _P, _P, _P]),
     'vmp_mixture_fit_pack_words': (_c.c_int, [_c.c_int]),
     'vmp_mixture_fit_pack': (_c.c_int, [_c.c_int, _c.c_int] + [_P] * 7),
     'vmp_mixture_fit_workspace_bytes': (_c.c_size_t, [_c.c_int64, _c.c_int, _c.c_int]),

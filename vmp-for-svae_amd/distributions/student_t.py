@@ -44,3 +44,13 @@ def mixture_impute(y, miss, mu, sigma, v, log_pi, return_resp=False):
     pack = _mix.impute_pack_t(log_pi, mu, sigma, v)
     y_out, logp, resp, _ = _mix.mixture_impute(y, miss, pack, want_resp=return_resp)
     return (y_out, logp, resp) if return_resp else (y_out, logp)
+
+
+def mixture_sample(n, seed, mu, sigma, v, log_pi, want_z=False):
+    """n seeded rows (n,D) from the mixture sum_k pi_k S(. | mu_k, sigma_k, v_k) in one streaming HIP pass
+    (vmp_mixture_impute_pack_t + vmp_mixture_sample); with want_z also the (n,) int32 components.  Row i is a function of
+    (seed, i) only; conditional draws of partly observed rows are models._mix.mixture_sample on the same pack."""
+    from ..models import _mix
+    pack = _mix.impute_pack_t(log_pi, mu, sigma, v)
+    y, z = _mix.mixture_draw(n, pack, seed, want_z=want_z)
+    return (y, z) if want_z else y

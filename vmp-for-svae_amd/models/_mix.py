@@ -270,6 +270,68 @@ def mixture_impute(x, miss, pack, want_x=True, want_logp=True, want_resp=False, 
     return (xin if (want_x and inplace) else x_out), logp, resp, total
 
 
+def _draw_counts(seed, draws, row0):
+    """(seed, draws, row0) of a sampling pass as Python ints, refused BEFORE the library or the device is touched"""
+    seed, draws, row0 = int(seed), int(draws), int(row0)
+    if not 0 <= seed < 1 << 64:
+        raise L.VmpError('seed must be in 0 .. 2^64 - 1 (got %d)' % seed)
+    if draws < 1:
+        raise L.VmpError('draws must be >= 1 (got %d)' % draws)
+    if row0 < 0:
+        raise L.VmpError('row0 must be >= 0 (got %d)' % row0)
+    return seed, draws, row0
+
+
+def _impute_pack_dim(pack):
+    """D of an impute pack, from its width (2 D + D (D + 1) / 2 + 5 words; a score pack or a fit pack has no such D)"""
+    if not torch.is_tensor(pack) or pack.dim() != 2 or pack.shape[0] < 1:
+        raise L.VmpError('pack must be a (K, words) tensor from impute_pack_niw / impute_pack_t')
+    for D in range(1, L.MAX_D + 1):
+        if 2 * D + D * (D + 1) // 2 + 5 == pack.shape[1]:
+            return D
+    raise L.VmpError('pack has shape %s: %d words per component is no impute pack (impute_pack_niw / impute_pack_t; a score pack or a '
+                     'fit pack does not do)' % (tuple(pack.shape), pack.shape[1]))
+
+
+def _sample_launch(x, mask, pack, N, D, K, seed, draws, row0, want_z):
+    x_out = torch.empty(draws, N, D, dtype=torch.float32, device=pack.device)
+    z = torch.empty(draws, N, dtype=torch.int32, device=pack.device) if want_z else None
+    L.check(L.lib().vmp_mixture_sample(L.ptr(x), L.ptr(mask), N, D, K, L.ptr(pack), seed, row0, draws, L.ptr(x_out), L.ptr(z),
+                                       L.stream()), 'vmp_mixture_sample')
+    return x_out, z
+
+
+def mixture_sample(x, miss, pack, seed, draws=1, row0=0, want_z=False):
+    """`draws` seeded draws of the missing entries of every row of x (N,D) - miss (N,D), nonzero / True = missing - from
+    p(x_missing | x_observed) under an impute pack, in one streaming pass (vmp_mixture_sample): (x_draws (draws,N,D), z (draws,N)
+    int32 or None) - multiple imputation.  Observed entries are copied bit for bit; z is the component each draw came from (-1 in a
+    row whose every weight is -inf, whose missing entries are 0).  The random stream is a function of (seed, row0 + n, draw) only:
+    rows [a, b) drawn with row0 = a are rows a .. b of the whole call, and two calls with the same arguments return the same bits.
+    What a missing slot of x holds is never read into arithmetic.  Everything stays on the device: no host synchronisation."""
+    seed, draws, row0 = _draw_counts(seed, draws, row0)
+    D = _impute_pack_dim(pack)
+    if not torch.is_tensor(x) or x.dim() != 2 or x.shape[1] != D:
+        raise L.VmpError('x has shape %s, expected (N,%d) for this pack' % (tuple(x.shape) if torch.is_tensor(x) else type(x), D))
+    x, mask, pack, N, D, K = _masked_operands(x, miss, pack, 'vmp_mixture_impute_pack_words', 'impute_pack_niw / impute_pack_t')
+    return _sample_launch(x, mask, pack, N, D, K, seed, draws, row0, want_z)
+
+
+def mixture_draw(n, pack, seed, row0=0, want_z=False):
+    """n seeded rows from the mixture of an impute pack itself (vmp_mixture_sample without x and mask: every entry missing):
+    (x (n,D), z (n,) int32 or None).  Row i is a function of (seed, row0 + i) only.  No host synchronisation."""
+    seed, _, row0 = _draw_counts(seed, 1, row0)
+    n = int(n)
+    if n < 1:
+        raise L.VmpError('n must be >= 1 (got %d)' % n)
+    D = _impute_pack_dim(pack)
+    K = pack.shape[0]
+    if not 1 <= K <= L.MAX_K:
+        raise L.VmpError('K=%d outside compiled range 1..%d' % (K, L.MAX_K))
+    pack = L.dev_f32(pack, 'pack')
+    x_out, z = _sample_launch(None, None, pack, n, D, K, seed, 1, row0, want_z)
+    return x_out[0], (z[0] if want_z else None)
+
+
 def _mask_u8(miss):
     """(N,D) uint8 view / copy of a missing-data mask of any dtype (nonzero = missing), as mixture_impute normalises it"""
     if miss.dtype == torch.bool:
@@ -520,6 +582,26 @@ class VMPLoop(object):
         _impute_dims(x_new, miss, self.post['m'], 'impute')
         x_out, logp, _, _ = mixture_impute(x_new, miss, self.impute_pack())
         return x_out, logp
+
+    def sample(self, n, seed, want_z=False):
+        """n seeded rows (n,D) from the mixture impute() fills from - the GMM's posterior predictive, the SMM's plug-in mixture - of the
+        current posterior (mixture_draw on impute_pack()); with want_z also the component of each row.  One streaming launch, no host
+        synchronisation."""
+        x, z = mixture_draw(n, self.impute_pack(), seed, want_z=want_z)
+        return (x, z) if want_z else x
+
+    def impute_draws(self, x_new, miss, draws, seed, want_z=False):
+        """`draws` completed copies (draws,M,D) of the partly observed rows x_new (M,D) with mask miss (M,D; nonzero = missing), their
+        missing entries drawn from p(x_missing | x_observed) under the current posterior (mixture_sample on impute_pack()) - multiple
+        imputation, where impute() returns the conditional mean; with want_z also the (draws,M) components.  One streaming launch,
+        no host synchronisation."""
+        if self.iterations == 0:
+            raise L.VmpError('no posterior to impute from yet: run at least one iteration')
+        if not torch.is_tensor(x_new) or x_new.dim() != 2 or x_new.shape[1] != self.D or x_new.shape[0] < 1:
+            raise L.VmpError('x_new has shape %s, expected (M >= 1, %d)' % (tuple(x_new.shape) if torch.is_tensor(x_new) else type(x_new), self.D))
+        _impute_dims(x_new, miss, self.post['m'], 'impute_draws')
+        x, z = mixture_sample(x_new, miss, self.impute_pack(), seed, draws=draws, want_z=want_z)
+        return (x, z) if want_z else x
 
     def run_until(self, x_val, tol, check_every=5, max_iterations=1000):
         """run(check_every) and score(x_val) in turn until the score improves by less than `tol` (absolute, nats per row) over

@@ -158,6 +158,26 @@ def predictive_impute(x, miss, alpha_k, beta_k, m_k, C_k, v_k, return_resp=False
     return (x_out, logp, resp) if return_resp else (x_out, logp)
 
 
+def predictive_sample(n, seed, alpha_k, beta_k, m_k, C_k, v_k, want_z=False):
+    """n seeded rows (n,D) from the posterior predictive of the variational GMM (the Student-t mixture predictive_logprob scores), in
+    one streaming HIP pass (vmp_mixture_impute_pack_niw + vmp_mixture_sample); with want_z also the (n,) int32 components.  Row i
+    is a function of (seed, i) only."""
+    pack = _mix.impute_pack_niw(alpha_k, beta_k, m_k, C_k, v_k)
+    x, z = _mix.mixture_draw(n, pack, seed, want_z=want_z)
+    return (x, z) if want_z else x
+
+
+def predictive_impute_draws(x, miss, draws, seed, alpha_k, beta_k, m_k, C_k, v_k, want_z=False):
+    """Multiple imputation: `draws` completed copies (draws,N,D) of the rows of x (N,D) - miss (N,D), nonzero = missing - with the
+    missing entries drawn from p(x_m | x_o) under the posterior predictive of the variational GMM, where predictive_impute fills in
+    its mean.  One streaming HIP pass (vmp_mixture_impute_pack_niw + vmp_mixture_sample); with want_z also the (draws,N) int32
+    components.  What the missing slots of x hold is never read into arithmetic."""
+    _mix._impute_dims(x, miss, m_k, 'predictive_impute_draws')
+    pack = _mix.impute_pack_niw(alpha_k, beta_k, m_k, C_k, v_k)
+    xd, z = _mix.mixture_sample(x, miss, pack, seed, draws=draws, want_z=want_z)
+    return (xd, z) if want_z else xd
+
+
 class _Handle(object):
     """Stand-in for a TF fetch: call it to get the current value."""
 

@@ -141,6 +141,36 @@ def heldout_impute(x, miss, alpha_k, beta_k, m_k, C_k, v_k, kappa_k, return_resp
     return (x_out, logp, resp) if return_resp else (x_out, logp)
 
 
+def _plugin_pack(K, D, alpha_k, beta_k, m_k, C_k, v_k, kappa_k):
+    """impute pack of the plug-in mixture of heldout_impute, its operands' shapes checked first"""
+    for t, n, shp in ((alpha_k, 'alpha_k', (K,)), (beta_k, 'beta_k', (K,)), (m_k, 'm_k', (K, D)), (C_k, 'C_k', (K, D, D)),
+                      (v_k, 'v_k', (K,)), (kappa_k, 'kappa_k', (K,))):
+        _mix._kd(t, n, shp)
+    return _mix.impute_pack_t(torch.log(alpha_k / alpha_k.sum()), m_k, C_k / v_k[:, None, None], kappa_k)
+
+
+def heldout_sample(n, seed, alpha_k, beta_k, m_k, C_k, v_k, kappa_k, want_z=False):
+    """n seeded rows (n,D) from the plug-in Student-t mixture of heldout_logprob (mu_k = m_k, sigma_k = C_k / v_k, nu_k = kappa_k,
+    log_w_k = log(alpha_k / sum alpha)) in one streaming HIP pass (vmp_mixture_impute_pack_t + vmp_mixture_sample); with want_z
+    also the (n,) int32 components.  Row i is a function of (seed, i) only."""
+    if not torch.is_tensor(m_k) or m_k.dim() != 2:
+        raise L.VmpError('heldout_sample: m_k must be (K,D)')
+    pack = _plugin_pack(m_k.shape[0], m_k.shape[1], alpha_k, beta_k, m_k, C_k, v_k, kappa_k)
+    x, z = _mix.mixture_draw(n, pack, seed, want_z=want_z)
+    return (x, z) if want_z else x
+
+
+def heldout_impute_draws(x, miss, draws, seed, alpha_k, beta_k, m_k, C_k, v_k, kappa_k, want_z=False):
+    """Multiple imputation under the plug-in Student-t mixture of heldout_impute: `draws` completed copies (draws,N,D) of the rows of
+    x (N,D) (miss (N,D), nonzero = missing), the missing entries drawn from p(x_m | x_o), where heldout_impute fills in the
+    conditional location.  One streaming HIP pass (vmp_mixture_impute_pack_t + vmp_mixture_sample); with want_z also the (draws,N)
+    int32 components."""
+    N, D, K = _mix._impute_dims(x, miss, m_k, 'heldout_impute_draws')
+    pack = _plugin_pack(K, D, alpha_k, beta_k, m_k, C_k, v_k, kappa_k)
+    xd, z = _mix.mixture_sample(x, miss, pack, seed, draws=draws, want_z=want_z)
+    return (xd, z) if want_z else xd
+
+
 def inference(x, K, kappa_init, seed, name='inference', r_init=None):
     """reference smm.py:199-245: as gmm.inference with u_nk initialised to ones and constant kappa."""
     N, D = x.shape

@@ -309,6 +309,45 @@ int    vmp_mixture_fit_iterate(const float* x, const uint8_t* mask, int64_t N, i
                                float* pi, float* pack, double* stats, void* ws, size_t ws_bytes, int iterations, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Mixture initialisation (csrc/vmp_seed.hip): seeded k-means++ centres and the responsibilities of the nearest centre, on the device
+ * ------------------------------------------------------------------------------------------------
+ * D^2-seeding (Arthur & Vassilvitskii 2007) of K centres from the rows of x (N,D) fp32, any alignment, as a pure function of (seed,
+ * row index, round); optional mask (N,D) uint8, nonzero = missing, with fill (D) fp32, the value a centre takes in a coordinate its
+ * row does not have.  What a missing slot of x holds never enters arithmetic (NaN and +-Inf there are as good as 0).
+ *   o(n) the observed coordinates of row n, D_o(n) their number (without a mask: all D);  x~_n = row n with fill in its missing slots;
+ *   dist2(n, c) = (D / D_o(n)) sum_{i in o(n)} (x_ni - c_i)^2,  0 when D_o(n) = 0     (the partial-distance rule).
+ * Rounds j = 0 .. K-1; before round 0 the weight is w_n = 1 if D_o(n) > 0, else 0:
+ *   1. E_nj = -log u(seed, n, j);
+ *   2. s_n = E_nj / w_n, +inf where w_n = 0;
+ *   3. i_j = the row with the smallest s_n, ties to the lowest n (every s_n = +inf: row 0);
+ *   4. c_j = x~_{i_j};
+ *   5. w_n <- dist2(n, c_0) after round 0,  w_n <- min(w_n, dist2(n, c_j)) after every later round.
+ * An exponential race: row n wins with probability w_n / sum w - exact D^2-sampling; round 0 is a uniform draw over the rows that
+ * observe something.  The uniform is drawn as in "Mixture sampling": Philox4x32-7 (oracle/philox.py philox4x32), key = seed,
+ * counter = (n low, n high, j, 0x6b6d2b00), word 0, u = (top 24 bits + 1/2) 2^-24 rounded once to fp32 and kept at most 1 - 2^-24.
+ * The fourth counter word differs from every other one of csrc/: 0 (cell noise), 0x5bb5a3c1 (categorical draw), 0x6d78a500 + b (sampling).
+ * Assignment: z_n = the k with the smallest dist2(n, c_k), ties to the lowest k;  r_nk = (1 - smooth) [k = z_n] + smooth / K in
+ * fp32 (the one-hot entry is (1 - smooth) + smooth / K), 0 <= smooth < 1;  a row with D_o(n) = 0 gets z = -1 and r = 1 / K.
+ * The pick is a lexicographic minimum of (s, n): it does not depend on grid, block or wave geometry; no atomics; every output is
+ * bit-identical from run to run and whichever optional outputs are requested.
+ *
+ * vmp_mixture_seed_centers: centers_out (K,D) = c_j (the bits of x~ at the chosen rows); index_out (K) int64 = i_j or NULL;
+ *   mind2_out (N) = w after the last round, or NULL.  N < K is legal: the centres then repeat.  ONE call enqueues K + 1 launches back
+ *   to back, no host work in between: launch j = 0 .. K first reduces the per-block minima of launch j - 1 to i_{j-1} (every block
+ *   the same reduction), reads c_{j-1} from x, and then streams the rows once - w is updated with c_{j-1} and, for j < K, the
+ *   block's minimum of round j is left in ws; launch K without mind2_out is one block.  w lives in ws
+ *   (vmp_mixture_seed_workspace_bytes, 8-byte aligned): per row a round reads x, the mask and w and writes w.
+ * vmp_mixture_seed_assign: one launch; r_out (N,K), z_out (N) int32 or NULL; mask as above or NULL; no workspace.
+ * Errors (decided before any launch): VMP_E_DIM (D, K outside 1..VMP_MAX_D / 1..VMP_MAX_K), VMP_E_BADARG (N < 1; x, centers_out,
+ *   centers or r_out NULL; exactly one of mask and fill NULL; smooth outside [0, 1) or NaN; ws not 8-byte aligned), VMP_E_WS (ws NULL
+ *   or too small).                                                                                                          */
+size_t vmp_mixture_seed_workspace_bytes(int64_t N, int D, int K);
+int    vmp_mixture_seed_centers(const float* x, const uint8_t* mask, const float* fill, int64_t N, int D, int K, uint64_t seed,
+                                float* centers_out, int64_t* index_out, float* mind2_out, void* ws, size_t ws_bytes, void* stream);
+int    vmp_mixture_seed_assign(const float* x, const uint8_t* mask, int64_t N, int D, int K, const float* centers, float smooth,
+                               float* r_out, int32_t* z_out, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * T2: SVAE E-step fused with the ELBO regulariser (models/svae.py:14-119 and :229-252)
  * ------------------------------------------------------------------------------------------------
  * Per (n,k) cell:  Pt = diag(-2 eta2d_n) + P_k,  ht = eta1_n + h_k,  Lt = chol(Pt),

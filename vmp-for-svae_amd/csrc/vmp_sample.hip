@@ -21,8 +21,8 @@
 // l_k = log w_k alone: a row whose log w is finite but whose mu, Lambda or nu is NaN is chosen with its weight and gives NaN entries
 // with z = that k, the other components draw normally.
 //
-// Random stream: Philox4x32 at VMP_PHILOX_ROUNDS rounds (the generator of vmp_svae.hip, restated here because that file is not a
-// header), key = seed, counter = (row low, row high, s, SAMPLE_TAG + b) with row = row0 + n the ABSOLUTE row index, s the draw and b
+// Random stream: Philox4x32 at VMP_PHILOX_ROUNDS rounds (the generator of vmp_svae.hip, restated in vmp_philox.h because that file
+// is not a header), key = seed, counter = (row low, row high, s, SAMPLE_TAG + b) with row = row0 + n the ABSOLUTE row index, s the draw and b
 // the block; nothing else enters (not the grid, the wave, N or the outputs requested), so rows [a, b) drawn with row0 = a are rows
 // a .. b of the whole call.  SAMPLE_TAG + b differs from the fourth counter word of the cell noise (0) and of the categorical draw of
 // subsample_kernel (SUBSAMPLE_TAG).  A uniform is (top 24 bits of a word + 1/2) 2^-24; in fp32 that is rounded once (ties to even),
@@ -40,6 +40,7 @@
 // row16 reduction), then each lane evaluates the cell of ITS z again for R, y, q and xhat - only cdf_k is kept per component - and
 // does the gamma draw and the R^-T solve on its own.  x == NULL (plain draws): the K-loop evaluates no cell, l_k = log w_k.
 #include "vmp_mix_stream.h"
+#include "vmp_philox.h"
 
 using namespace vmp;
 
@@ -67,24 +68,11 @@ struct SGeo {
     static constexpr int STRIDE = PACK | 1;        // LDS stride: odd, so that the 16 components of a tile fall into 16 banks
 };
 
-#ifndef VMP_PHILOX_ROUNDS
-#define VMP_PHILOX_ROUNDS 7
-#endif
 __device__ __forceinline__ void sample_philox(unsigned (&c)[4], unsigned long long row, unsigned s, unsigned b, unsigned long long seed) {
-    unsigned k0 = (unsigned)seed, k1 = (unsigned)(seed >> 32);
     c[0] = (unsigned)row; c[1] = (unsigned)(row >> 32); c[2] = s; c[3] = SAMPLE_TAG + b;
-#pragma unroll
-    for (int r = 0; r < VMP_PHILOX_ROUNDS; ++r) {
-        if (r) { k0 += 0x9E3779B9u; k1 += 0xBB67AE85u; }
-        const unsigned long long p0 = (unsigned long long)0xD2511F53u * c[0];
-        const unsigned long long p1 = (unsigned long long)0xCD9E8D57u * c[2];
-        const unsigned n0 = (unsigned)(p1 >> 32) ^ c[1] ^ k0, n2 = (unsigned)(p0 >> 32) ^ c[3] ^ k1;
-        c[1] = (unsigned)p1; c[3] = (unsigned)p0; c[0] = n0; c[2] = n2;
-    }
+    philox_rounds(c, seed);
 }
-__device__ __forceinline__ float sample_uniform(unsigned w) {
-    return fminf(fmaf((float)(w >> 8), 5.9604644775390625e-08f, 2.98023223876953125e-08f), 0.99999994f);     // in (0, 1): never 1.0
-}
+__device__ __forceinline__ float sample_uniform(unsigned w) { return philox_uniform24(w); }     // in (0, 1): never 1.0
 __device__ __forceinline__ float sample_radius(unsigned w) {
     const float u1 = fmaf((float)(w >> 12), 9.5367431640625e-07f, 4.76837158203125e-07f);       // (a + 1/2) 2^-20, exact
     return sqrtf(-2.0f * logf(u1));

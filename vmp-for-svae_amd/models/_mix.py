@@ -372,10 +372,96 @@ def mean_filled(x, mask):
     """x with every missing entry replaced by its column's mean over the observed entries (0 for a column with none): the copy the
     masked loop takes the moments of r_init from."""
     gone = mask != 0
+    mean = _observed_mean(x, gone)
+    return torch.where(gone, mean[None, :].expand_as(x), x).contiguous()
+
+
+def _observed_mean(x, gone):
+    """(D,) column means of x over the entries that `gone` (N,D) bool does not flag (0 for a column with none), in x's dtype"""
     xz = torch.where(gone, torch.zeros((), dtype=x.dtype, device=x.device), x)
     cnt = (~gone).sum(0)
-    mean = (xz.double().sum(0) / cnt.clamp_min(1).double()).to(x.dtype)
-    return torch.where(gone, mean[None, :].expand_as(x), x).contiguous()
+    return (xz.double().sum(0) / cnt.clamp_min(1).double()).to(x.dtype)
+
+
+def _seed_operands(x, miss, K, what):
+    """(x fp32 on the device, uint8 mask or None) of a seeding call: shapes and devices are refused BEFORE the library or a device is
+    touched, CPU tensors by the operand check"""
+    if not torch.is_tensor(x) or x.dim() != 2 or x.shape[0] < 1:
+        raise L.VmpError('%s: x must be (N >= 1, D), got %s' % (what, tuple(x.shape) if torch.is_tensor(x) else type(x)))
+    if miss is not None:
+        if not torch.is_tensor(miss) or tuple(miss.shape) != tuple(x.shape):
+            raise L.VmpError('%s: the missing-data mask has shape %s, expected %s'
+                             % (what, tuple(miss.shape) if torch.is_tensor(miss) else type(miss), tuple(x.shape)))
+        if miss.device != x.device:
+            raise L.VmpError('%s: the missing-data mask is on %s, x on %s' % (what, miss.device, x.device))
+    _dims(x, K)
+    x = L.dev_f32(x, 'x')
+    return x, (None if miss is None else _mask_u8(miss))
+
+
+def seed_centers(x, K, seed, miss=None, want_index=False, want_mind2=False):
+    """K seeded k-means++ centres (D^2-seeding) from the rows of x (N,D) on the device (vmp_mixture_seed_centers; include/vmp_hip.h
+    "Mixture initialisation"): (centers (K,D), index (K,) int64 or None, mind2 (N,) or None) - the chosen rows and every row's squared
+    distance to its nearest centre.  A pure function of (seed, row index, round): the same bits from run to run.  miss (N,D),
+    nonzero = missing, on x's device: distances run over the observed coordinates (scaled by D / D_o), a row with none is never
+    chosen, and a centre takes its column's mean over the observed entries - the fill of mean_filled - where its row has a gap.
+    K + 1 launches enqueued by one call, no host synchronisation."""
+    K, seed = int(K), int(seed)
+    if not 0 <= seed < 1 << 64:
+        raise L.VmpError('seed must be in 0 .. 2^64 - 1 (got %d)' % seed)
+    x, mask = _seed_operands(x, miss, K, 'seed_centers')
+    N, D = x.shape
+    dev = x.device
+    fill = None if mask is None else _observed_mean(x, mask != 0).contiguous()
+    centers = torch.empty(K, D, dtype=torch.float32, device=dev)
+    index = torch.empty(K, dtype=torch.int64, device=dev) if want_index else None
+    mind2 = torch.empty(N, dtype=torch.float32, device=dev) if want_mind2 else None
+    nb = L.lib().vmp_mixture_seed_workspace_bytes(N, D, K)
+    ws = L.workspace(dev, nb)
+    L.check(L.lib().vmp_mixture_seed_centers(L.ptr(x), L.ptr(mask), L.ptr(fill), N, D, K, seed, L.ptr(centers), L.ptr(index),
+                                             L.ptr(mind2), L.ptr(ws), nb, L.stream()), 'vmp_mixture_seed_centers')
+    return centers, index, mind2
+
+
+def seed_assign(x, centers, miss=None, smooth=0.0, want_z=False):
+    """Responsibilities of the nearest centre (vmp_mixture_seed_assign): (r (N,K), z (N,) int32 or None) with z_n the nearest of
+    centers (K,D) by the distance of seed_centers (ties to the lowest k) and r_nk = (1 - smooth) [k = z_n] + smooth / K,
+    0 <= smooth < 1; a row without an observed entry gets z = -1 and r = 1 / K.  One streaming launch, no host synchronisation."""
+    smooth = float(smooth)
+    if not 0.0 <= smooth < 1.0:
+        raise L.VmpError('smooth must be in [0, 1) (got %r)' % smooth)
+    if not torch.is_tensor(x) or x.dim() != 2:
+        raise L.VmpError('seed_assign: x must be (N,D)')
+    if not torch.is_tensor(centers) or centers.dim() != 2 or centers.shape[1] != x.shape[1]:
+        raise L.VmpError('seed_assign: centers has shape %s, expected (K,%d)'
+                         % (tuple(centers.shape) if torch.is_tensor(centers) else type(centers), x.shape[1]))
+    if centers.device != x.device:
+        raise L.VmpError('seed_assign: centers is on %s, x on %s' % (centers.device, x.device))
+    K = centers.shape[0]
+    x, mask = _seed_operands(x, miss, K, 'seed_assign')
+    N, D = x.shape
+    centers = L.dev_f32(centers, 'centers', (K, D))
+    r = torch.empty(N, K, dtype=torch.float32, device=x.device)
+    z = torch.empty(N, dtype=torch.int32, device=x.device) if want_z else None
+    L.check(L.lib().vmp_mixture_seed_assign(L.ptr(x), L.ptr(mask), N, D, K, L.ptr(centers), smooth, L.ptr(r), L.ptr(z), L.stream()),
+            'vmp_mixture_seed_assign')
+    return r, z
+
+
+INITS = ('random', 'kmeans++')
+
+
+def check_init(init):
+    """the `init` keyword of gmm.inference / gmm.inference_missing / smm.inference, refused on the host"""
+    if init not in INITS:
+        raise L.VmpError('init=%r: expected one of %s' % (init, ', '.join(repr(i) for i in INITS)))
+    return init
+
+
+def seeded_r_init(x, K, seed, miss=None, smooth=0.0):
+    """r_init (N,K) of init='kmeans++': seed_centers, then seed_assign - on the device, no host synchronisation"""
+    centers, _, _ = seed_centers(x, K, seed, miss=miss)
+    return seed_assign(x, centers, miss=miss, smooth=smooth)[0]
 
 
 def default_prior(K, D, device):
@@ -442,6 +528,16 @@ class VMPLoop(object):
         L.check(seed_fn(L.ptr(self.x), L.ptr(self.r), L.ptr(self.u), L.ptr(self.pivot), self.N, D, K,
                         L.ptr(self.ws), self.nb, L.stream()), 'vmp_mix_stats_ws')
         self.pack64 = torch.empty(K, L.lib().vmp_mix_pack_words(D), dtype=torch.float64, device=dev) if self.accurate else None
+
+    @classmethod
+    def from_seed(cls, x, K, flavour, seed, kappa=None, prior=None, accurate=False, miss=None, smooth=0.0):
+        """The loop started from the data: r_init = seed_assign on the K centres of seed_centers(x, K, seed) - k-means++ on the
+        device, a pure function of (x, miss, K, seed) - instead of responsibilities the caller has to invent.  The refusals of the
+        constructor come first."""
+        if miss is not None:
+            cls._check_miss(x, miss, flavour, accurate)
+        r0 = seeded_r_init(x, K, seed, miss=miss, smooth=smooth)
+        return cls(x, r0, flavour, kappa=kappa, prior=prior, accurate=accurate, miss=miss)
 
     @staticmethod
     def _check_miss(x, miss, flavour, accurate):

@@ -194,14 +194,19 @@ def _dirichlet_init(N, K, seed, device):
     return (e / e.sum(1, keepdim=True)).to(device)
 
 
-def inference_missing(x, miss, K, seed, name='inference_missing', r_init=None):
+def inference_missing(x, miss, K, seed, name='inference_missing', r_init=None, init='random'):
     """inference() on partly observed rows: miss (N,D), nonzero = missing, on x's device; what the missing slots of x hold is never
     read into arithmetic.  The missing entries are latent variables of the variational posterior, q(z_n, x_n,m) = q(z_n) q(x_n,m | z_n):
     every iteration is the NIW update of inference() on the moments of the completed rows (conditional means and covariances) and an
     E-step on the marginal of the observed entries, in one streaming HIP pass (csrc/vmp_missfit.hip) - unlike e_step_missing_data,
     which zeroes the missing differences inside the full precision and cannot feed an M-step.  Returns (step, log_r_nk, theta,
-    (x_k, S_k, pi), x_filled): inference()'s four, and a handle for x with its missing entries replaced by sum_k r_nk E[x_m | x_o, k]."""
+    (x_k, S_k, pi), x_filled): inference()'s four, and a handle for x with its missing entries replaced by sum_k r_nk E[x_m | x_o, k].
+    init='kmeans++': r_init comes from _mix.seed_centers / seed_assign on the observed entries, as in inference()."""
+    _mix.check_init(init)
     N, D = x.shape
+    if r_init is None and init == 'kmeans++':
+        _mix.VMPLoop._check_miss(x, miss, L.VMP_GMM, False)
+        r_init = _mix.seeded_r_init(x, K, seed, miss=miss)
     if r_init is None:
         r_init = _dirichlet_init(N, K, seed, x.device)
     loop = _mix.VMPLoop(x, r_init, L.VMP_GMM, miss=miss)
@@ -212,12 +217,17 @@ def inference_missing(x, miss, K, seed, name='inference_missing', r_init=None):
     return (step, _Handle(lambda: loop.logr), _Handle(loop.theta), _Handle(loop.aux), _Handle(loop.filled))
 
 
-def inference(x, K, seed, name='inference', r_init=None):
+def inference(x, K, seed, name='inference', r_init=None, init='random'):
     """reference gmm.py:230-269.  Returns (step, log_r_nk, theta, (x_k, S_k, pi)) where `step()` executes one
     VMP iteration (M-step, E-step, assign) and returns the new r_nk; the other three are handles that are
     CALLED to fetch the values of the last executed iteration.  `r_init` replaces the TF-RNG Dirichlet(1)
-    draw of gmm.py:246-249 (default: torch Dirichlet(1) with `seed`)."""
+    draw of gmm.py:246-249 (default: torch Dirichlet(1) with `seed`).  init='kmeans++' (when no r_init is given): r_init is built on
+    the device instead - k-means++ centres drawn with `seed` and the one-hot responsibilities of the nearest centre
+    (_mix.seed_centers / seed_assign): no host random numbers, no copy, and a start that already separates the clusters."""
+    _mix.check_init(init)
     N, D = x.shape
+    if r_init is None and init == 'kmeans++':
+        r_init = _mix.seeded_r_init(x, K, seed)
     if r_init is None:
         g = torch.Generator(device='cpu').manual_seed(int(seed))
         e = -torch.log(torch.rand(N, K, generator=g).clamp_min(1e-30))

@@ -171,9 +171,12 @@ def heldout_impute_draws(x, miss, draws, seed, alpha_k, beta_k, m_k, C_k, v_k, k
     return (xd, z) if want_z else xd
 
 
-def inference(x, K, kappa_init, seed, name='inference', r_init=None):
-    """reference smm.py:199-245: as gmm.inference with u_nk initialised to ones and constant kappa."""
+def inference(x, K, kappa_init, seed, name='inference', r_init=None, init='random'):
+    """reference smm.py:199-245: as gmm.inference with u_nk initialised to ones and constant kappa (init='kmeans++' as there)."""
+    _mix.check_init(init)
     N, D = x.shape
+    if r_init is None and init == 'kmeans++':
+        r_init = _mix.seeded_r_init(x, K, seed)
     if r_init is None:
         g = torch.Generator(device='cpu').manual_seed(int(seed))
         e = -torch.log(torch.rand(N, K, generator=g).clamp_min(1e-30))

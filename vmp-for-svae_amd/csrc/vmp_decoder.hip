@@ -825,9 +825,15 @@ __device__ __forceinline__ u32x4 trt_read(const unsigned char* __restrict__ img,
 // BT = bf16 terms per operand on the backward DATA path (dh1 = W2 dO, dh0 = W1 dh1pre, dx = W0 dh0pre + Ws dO): 3 = the six
 // products of fp32 accuracy; 2 = three products, relative error <= 2^-16 per product.  The consumers of that path are sums
 // over rows (the weight gradients, which take (h, m) terms of it anyway) and dL/dx, which the E-step backward and the
-// encoder sum over samples, components and rows - for batches of >= 2^19 sample rows the 2-term form's rounding is below
-// the fp32 rounding of those sums (gated by the 21-gradient bars of tests/test_fullsize_gpu.py at N = 65 536 and 1e5),
-// and it saves 34 of 195 MFMAs and 64 of 840 VALU instructions per 16-row tile.  Small batches keep BT = 3.
+// encoder sum over samples, components and rows.  Decoder mode takes BT = 2 from 2^19 sample rows: measured against the fp64
+// truth at 524 307 rows (tests/test_decoder_tiles_gpu.py: every UT / FS, both sides of the threshold) the nine parameter
+// gradients then are off by up to 8.9e-6 of their largest element (BT = 3 one data row below: <= 2e-7) - inside the 1e-5 bar of
+// the decoder tests, though not "below the fp32 rounding of those sums" as this comment once claimed - and per-row dx by
+// 0.8e-5 .. 1.5e-5, which is the error of the 2-term arithmetic itself (restated in tests/decoder_truth.py: 0.8e-5 .. 1.5e-5);
+// the 21-gradient bars of tests/test_fullsize_gpu.py at N = 65 536 and 1e5 gate the whole step.  It saves 34 of 195 MFMAs and
+// 64 of 840 VALU instructions per 16-row tile.  Small batches keep BT = 3, and so does gradient-input mode at every size: its
+// upstream gradients are free inputs, the row sums may cancel, and at 524 307 rows with independent upstream gradients the
+// 2-term form left db0, db1, dW0 and dW1 at 1.0e-5 .. 1.7e-5 (dec_bwd_launch; the GIN instances are built for BT = 3 only).
 template <int UT, bool FS, bool GIN, int BT>
 __global__ __launch_bounds__(BWD_THREADS, 2) void dec_bwd_kernel(DecArgs a) {
     DEC_TS(0);
@@ -1296,11 +1302,11 @@ int dec_bwd_launch(const DecArgs& a0, int blocks, hipStream_t s) {
 #ifndef VMP_DEC_BT2_ROWS
 #define VMP_DEC_BT2_ROWS (1u << 19)   // sample rows from which the backward data path uses 2-term operands (0xffffffff: never)
 #endif
-    const bool bt2 = a.R >= (unsigned)VMP_DEC_BT2_ROWS;
+    const bool bt2 = !GIN && a.R >= (unsigned)VMP_DEC_BT2_ROWS;      // gradient-input mode: 3-term at every size (see dec_bwd_kernel)
 #define DEC_BWD_L(UTV, FSV, BTV)                                                                                      \
     do {                                                                                                              \
-        if (const int rc_ = set_dyn_lds(reinterpret_cast<const void*>(dec_bwd_kernel<UTV, FSV, GIN, BTV>), (size_t)lds, "dec_bwd_kernel")) return rc_; \
-        hipLaunchKernelGGL((dec_bwd_kernel<UTV, FSV, GIN, BTV>), dim3(blocks), dim3(BWD_THREADS), lds, s, a);         \
+        if (const int rc_ = set_dyn_lds(reinterpret_cast<const void*>(dec_bwd_kernel<UTV, FSV, GIN, (GIN ? 3 : BTV)>), (size_t)lds, "dec_bwd_kernel")) return rc_; \
+        hipLaunchKernelGGL((dec_bwd_kernel<UTV, FSV, GIN, (GIN ? 3 : BTV)>), dim3(blocks), dim3(BWD_THREADS), lds, s, a); \
     } while (0)
 #define DEC_BWD(UTV)                                                                                                  \
     do {                                                                                                              \

@@ -11,63 +11,17 @@ under the counted wait, row0 and the prefetch handed from the straight-line loop
 tile - is reached by the large shapes: 200 037 rows (104 rows per wave: one whole tile, then 40 rows) and 400 037 rows (split plan,
 240 / 152 rows per wave: three or two whole tiles with a flush between them, then a ragged tail), the latter in both flavours with
 D in {2, 5, 8} and once with want_logr."""
-import functools
-
 import numpy as np
 import pytest
 import torch
 
 import parity_log
 import test_mix_gpu as T
+from mix_pass_truth import loop as _loop, one_step as _one_step, truth as _truth      # shared with tests/test_mix_tiled_pass_gpu.py
 
 pytestmark = pytest.mark.gpu
 
-KAPPA = 5.0
 SHAPES = [(64, 16), (65, 16), (127, 16), (63, 16), (1024 + 17, 16), (1024 + 17, 10)]
-
-
-@functools.lru_cache(maxsize=None)
-def _truth(N, D, K, smm):
-    """inputs, the fp64 oracle's (r, u) after one iteration, the posterior they give, and (SMM) the error of the oracle in the
-    reference's own fp32 on that r: computed once per shape and shared, never modified"""
-    from oracle import mixtures
-    x, r0 = T._synth(N, D, K, seed=N + D + K)
-    xo, ro = torch.as_tensor(x).double(), torch.as_tensor(r0).double()
-    if not smm:
-        r1 = mixtures.gmm_inference_step_chunked(xo, ro)[0]
-        th = mixtures.gmm_inference_step_chunked(xo, r1)[2]
-        return x, r0, r1.numpy(), None, [t.numpy() for t in th], 0.0
-    uo = torch.ones(N, K, dtype=torch.float64)
-    r1, u1 = mixtures.smm_inference_step_chunked(xo, ro, uo, KAPPA)[:2]
-    th = mixtures.smm_inference_step_chunked(xo, r1, u1, KAPPA)[2]
-    r32 = mixtures.smm_inference_step_chunked(torch.as_tensor(x), torch.as_tensor(r0), torch.ones(N, K), KAPPA)[0]
-    return x, r0, r1.numpy(), u1.numpy(), [t.numpy() for t in th[:5]], float((r32.double() - r1).abs().max())
-
-
-def _loop(x, r0, smm, K):
-    from vmp_for_svae_amd import _lib as L
-    from vmp_for_svae_amd.models import _mix
-    return _mix.VMPLoop(T.dev(x), T.dev(r0), L.VMP_SMM if smm else L.VMP_GMM,
-                        kappa=torch.full((K,), KAPPA, device='cuda') if smm else None)
-
-
-def _one_step(N, D, K, flavour):
-    smm = flavour == 'smm'
-    x, r0, r1, u1, th1, ref32 = _truth(N, D, K, smm)
-    what = '%s N=%d D=%d K=%d ' % (flavour, N, D, K)
-    if smm:
-        parity_log.record('abs', ref32, None, what + 'r_nk: fp32 oracle (reference dtype) vs fp64 truth')
-    bar_r = max(1e-5, ref32)                                      # test_vmp_steps_vs_oracle: 1e-5, or the reference's own fp32 error
-    loop = _loop(x, r0, smm, K)
-    r = loop.step()
-    assert torch.isfinite(r).all(), what
-    assert float((r.double().sum(1) - 1.0).abs().max()) <= 1e-6, what
-    assert T.abserr(r, r1, what + 'r_nk', bar_r) <= bar_r, what
-    if smm:
-        assert T.relerr(loop.u, u1, what + 'u_nk', 2e-5) <= 2e-5, what          # test_smm_golden's bar on u
-    loop.finalize()                                               # the moments of the fused pass, through the posterior they give
-    for n_, t, o in zip(('alpha', 'beta', 'm', 'C', 'v'), loop.theta()[:5], th1):
-        assert T.relerr(t, o, what + n_, 1e-5) <= 1e-5, what + n_
 
 
 @pytest.mark.parametrize('flavour', ['gmm', 'smm'])

@@ -15,7 +15,7 @@ for N in [int(a) for a in sys.argv[1:]] or (2048, 125000, 1000000):
     loop = _mix.VMPLoop(x, r0, L.VMP_GMM)
     for _ in range(20): loop.step()
     tp = torch.zeros(128, dtype=torch.int64, device='cuda')
-    tf = torch.zeros(8, dtype=torch.int64, device='cuda')
+    tf = torch.zeros(16, dtype=torch.int64, device='cuda')
     h.vmp_debug_set_pass_timestamps(ctypes.c_void_p(tp.data_ptr()))
     h.vmp_debug_set_finalize_timestamps(ctypes.c_void_p(tf.data_ptr()))
     rows = []

@@ -686,7 +686,7 @@ struct FinArgs {
     unsigned long long iter;
     int* status;
 #ifdef VMP_DEBUG_TS
-    long long* dbg_t;          // exploration builds only: 8 timestamps of block 0 / thread 0
+    long long* dbg_t;          // exploration builds only: 16 timestamps of block 0 (0..7: thread 0; 8..15: the arms of phase C)
 #endif
 };
 
@@ -694,6 +694,12 @@ struct FinArgs {
 #define FIN_TS(i) do { if (a.dbg_t && blockIdx.x == 0 && tid == 0) { a.dbg_t[i] = clock64(); if ((i) == 0) a.dbg_t[6] = wall_clock64(); if ((i) == 5) a.dbg_t[7] = wall_clock64(); } } while (0)
 #else
 #define FIN_TS(i) do { } while (0)
+#endif
+// slot 8..15 of the same table, written by thread `t`: the arms of phase C (tools/fin_ts.py)
+#ifdef VMP_DEBUG_TS
+#define FIN_TSX(i, t) do { if (a.dbg_t && blockIdx.x == 0 && tid == (t)) a.dbg_t[i] = clock64(); } while (0)
+#else
+#define FIN_TSX(i, t) do { } while (0)
 #endif
 
 template <int D>
@@ -1266,17 +1272,16 @@ __device__ __forceinline__ void st_pack(const FinArgs& a, int idx, double v) {
     if (a.pack64) a.pack64[idx] = v;
 }
 
-// One block per component (k), `nthreads` threads (>= 192, a multiple of 64; the stand-alone kernel: 1024, the head of the
-// one-launch step: the streaming block's 512).  Phase A: all threads reduce the per-block partials in a fixed order.
-// Phase B: 64 lanes build S_k, C_k element-wise.  Phase C: wave 0 factorises C_k while lanes 64.. evaluate
-// the digamma / lgamma terms.  Phase D: constants + pack.
+// One block per component (k), `nthreads` threads (>= 192, a multiple of 64).  Phase A: all threads reduce the per-block partials
+// in a fixed order.  Phase B: 64 lanes build S_k, C_k element-wise.  Phase C: wave 0 factorises C_k while wave 1 evaluates the
+// digammas and everything of the constants that does not need the factorisation, thread 128 the lgamma terms.  Phase D: c alone.
 template <int D>
 __device__ void finalize_block(const FinArgs& a, const int k, const int tid, const int nthreads) {
     using G = Geo<D>;
     __shared__ double part[FIN_MAX_GROUPS][64];
     __shared__ double st[G::SW];           // canonical: Nk, Wk, sx[D], sxx[D*D]
     __shared__ double ntot;                // sum_j N_j over all components
-    __shared__ double Ck[D * D], mk[D], sp[D + 4], scal[8];
+    __shared__ double Ck[D * D], mk[D], sp[8], scal[8];
     __shared__ double alpha0s[VMP_MAX_K];
     const int K = a.K;
     const int FIN_GROUPS = nthreads >> 6;
@@ -1300,10 +1305,15 @@ __device__ void finalize_block(const FinArgs& a, const int k, const int tid, con
         constexpr int PX = G::PF + 1;
         const int f = tid & 63, g = tid >> 6;
         // all loads of a chunk are issued before the first add (fixed summation order: b ascending).  The rows of this
-        // component are contiguous: partials[k][b][PX].  The order of the additions does not depend on the thread count: there are
-        // always FIN_MAX_GROUPS LOGICAL groups (group lg sums blocks lg, lg + 16, ..), a block of fewer waves takes several each -
-        // the head of the one-launch step (512 threads) is bit-identical to the stand-alone kernel (1024).
+        // component are contiguous: partials[k][b][PX].  The order of the additions is fixed: FIN_MAX_GROUPS
+        // groups (group lg sums blocks lg, lg + 16, ..), one per wave of the launch, then the groups ascending.
         const double* __restrict__ mine = a.partials + (long long)k * MAX_BLOCKS * PX;
+        // where feature f of a partial row goes in st[]: a triangle entry (lo, hi) fills both (lo, hi) and (hi, lo)
+        int lo = 0, hi = f - (1 + D);
+#pragma unroll
+        for (int j = 0; j < D; ++j)
+            if (lo == j && hi >= D - j) { hi -= D - j; lo = j + 1; }
+        hi += lo;
         for (int lg = g; lg < FIN_MAX_GROUPS; lg += FIN_GROUPS) {
             double s = 0.0;
             for (int b0 = lg; b0 < a.nblk; b0 += FIN_MAX_GROUPS * 16) {
@@ -1329,18 +1339,15 @@ __device__ void finalize_block(const FinArgs& a, const int k, const int tid, con
         }
         __syncthreads();
         FIN_TS(1);
+        // the 64 summing lanes write the canonical layout themselves (no second staging round through part[0][])
         if (tid < 64) {
             double t1 = 0.0;
             for (int gg = 0; gg < FIN_MAX_GROUPS; ++gg) t1 += part[gg][tid];
-            part[0][tid] = t1;
-        }
-        __syncthreads();
-        if (tid == 0) { st[0] = part[0][G::F]; st[1] = part[0][0]; ntot = part[0][G::PF]; }
-        if (tid < D) st[2 + tid] = part[0][1 + tid];
-        if (tid < D * D) {
-            const int d = tid / D, e = tid % D;
-            const int lo = d < e ? d : e, hi = d < e ? e : d;
-            st[2 + D + tid] = part[0][1 + D + lo * D - lo * (lo - 1) / 2 + (hi - lo)];
+            if (f == G::F) st[0] = t1;
+            if (f == 0) st[1] = t1;
+            if (f == G::PF) ntot = t1;
+            if (f >= 1 && f < 1 + D) st[2 + (f - 1)] = t1;
+            if (f >= 1 + D && f < G::F) { st[2 + D + lo * D + hi] = t1; st[2 + D + hi * D + lo] = t1; }
         }
     } else {
         for (int i = tid; i < G::SW; i += nthreads) st[i] = a.stats_in[(long long)k * G::SW + i];
@@ -1494,49 +1501,73 @@ __device__ void finalize_block(const FinArgs& a, const int k, const int tid, con
                 if (i >= tid) st_pack(a, p + i * (i + 1) / 2 + tid, X[i] * sv);      // W = sqrt(v) L^{-1}, lower
         }
         if (tid == 0) { scal[0] = -2.0 * sumlog; scal[1] = ok ? 1.0 : 0.0; }
-    } else if (tid >= 64 && tid < 64 + D + 2) {
+        FIN_TSX(8, 0);
+    } else if (tid < 128) {
         // all digammas in ONE wave and ONE code path (different branches of a wave run one after the other: four
-        // special-function evaluations in sequence were most of this phase)
+        // special-function evaluations in sequence were most of this phase).  The branch takes the WHOLE wave - lanes past D + 1
+        // evaluate a dummy - and must keep doing so: the readlane_d broadcasts below read the registers of lanes D and D + 1
+        // whatever the exec mask says, and a lane that the branch had left out would hold no digamma there.
         const int i = tid - 64;
-        double arg = 0.5 * (v_k + (smm ? 0.0 : 1.0) + i);             // gmm.py:128-129 / smm.py:107-108
+        double arg = i < D ? 0.5 * (v_k + (smm ? 0.0 : 1.0) + i) : 16.0;  // gmm.py:128-129 / smm.py:107-108
         if (i == D) arg = alpha_k;
         if (i == D + 1) {
+            FIN_TSX(11, 64 + D + 1);
             double asum = 0.0;
             for (int j = 0; j < K; ++j) asum += alpha0s[j];
             arg = asum + ntot;
+            FIN_TSX(12, 64 + D + 1);
         }
-        sp[i] = digamma_d(arg);
+        const double dg = digamma_d(arg);
+        // ... and, while wave 0 factorises, everything of the constants that does not wait for log det P: what is left behind the
+        // barrier is phase D's last few operations.  Same operations on the same values in the same order as when one thread did
+        // all of it there: sums by ascending i, D / beta_k and the products with it formed where they were.
+        const double elp = readlane_d(dg, D) - readlane_d(dg, D + 1);
+        double sdg = 0.0;
+#pragma unroll
+        for (int j = 0; j < D; ++j) sdg += readlane_d(dg, j);
+        if (i == 0) {
+            const double LOG2 = 0.69314718055994530942;
+            const double db = D / beta_k;
+            sp[0] = elp; sp[1] = sdg + D * LOG2; sp[2] = db;
+            if (a.pi) a.pi[k] = (float)exp(elp);
+            if (a.pack) {
+                const int p = k * G::PACK + D + G::TRI;
+                const double LOG2E = 1.4426950408889634074;  // the pass kernel evaluates 2^(c - h q)
+                const double h = smm ? 0.5 * (D + kap) : 0.5;
+                st_pack(a, p + 1, h * LOG2E);
+                st_pack(a, p + 2, smm ? D + kap : 1.0);                                     // smm.py:134-137
+                st_pack(a, p + 3, smm ? db + kap : 1.0);
+            }
+        }
+        FIN_TSX(9, 64);
     } else if (tid == 128 && smm) {
-        sp[D + 2] = lgamma(0.5 * (D + kap)) - lgamma(0.5 * kap);
+        const double PI = 3.14159265358979323846;
+        FIN_TSX(13, 128);
+        sp[3] = lgamma(0.5 * (D + kap)) - lgamma(0.5 * kap);
+        FIN_TSX(14, 128);
+        sp[4] = log(kap * PI);
+        sp[5] = log(kap);
+        FIN_TSX(10, 128);
     }
     __syncthreads();
     FIN_TS(4);
     // ---- phase D
-    if (tid == 0) {
-        const double LOG2 = 0.69314718055994530942, PI = 3.14159265358979323846;
-        const double elp = sp[D] - sp[D + 1];
-        double sdg = 0.0;
-        for (int i = 0; i < D; ++i) sdg += sp[i];
-        double c, h = 0.5, ua = 1.0, ub = 1.0;
+    if (tid == 0 && a.pack) {
+        const double elp = sp[0], db = sp[2];
+        double c;
         const double logdetP = scal[0];
         if (!smm) {
             // gmm.py:120-121: log det P replaced by 0 when det P <= 1e-20
             const double ld = (logdetP > log(1e-20)) ? logdetP : 0.0;
-            c = elp + 0.5 * (sdg + D * LOG2 + ld) - 0.5 * (D / beta_k);
+            c = elp + 0.5 * (sp[1] + ld) - 0.5 * db;
         } else {
-            h = 0.5 * (D + kap);
+            const double h = 0.5 * (D + kap);
             // smm.py:122-124 (note the precedence of line 124: ... - (0.5 (D+kappa) m - log kappa))
-            c = sp[D + 2] - 0.5 * D * log(kap * PI) + elp + 0.5 * (sdg + D * LOG2 + logdetP) - h * (D / beta_k) + log(kap);
-            ua = D + kap;                                                                   // smm.py:134-137
-            ub = D / beta_k + kap;
+            c = sp[3] - 0.5 * D * sp[4] + elp + 0.5 * (sp[1] + logdetP) - h * db + sp[5];
         }
         if (scal[1] == 0.0) c = nan("");
-        if (a.pi) a.pi[k] = (float)exp(elp);
-        if (a.pack) {
-            const int p = k * G::PACK + D + G::TRI;
-            const double LOG2E = 1.4426950408889634074;  // the pass kernel evaluates 2^(c - h q)
-            st_pack(a, p, c * LOG2E); st_pack(a, p + 1, h * LOG2E); st_pack(a, p + 2, ua); st_pack(a, p + 3, ub);
-        }
+        const double LOG2E = 1.4426950408889634074;
+        st_pack(a, k * G::PACK + D + G::TRI, c * LOG2E);
     }
     if (a.pack && tid < D) st_pack(a, k * G::PACK + tid, mk[tid]);
     FIN_TS(5);

@@ -309,6 +309,46 @@ int    vmp_mixture_fit_iterate(const float* x, const uint8_t* mask, int64_t N, i
                                float* pi, float* pack, double* stats, void* ws, size_t ws_bytes, int iterations, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Variational lower bound (csrc/vmp_bound.hip): the free energy of the Gaussian-mixture fit, complete or partly observed rows
+ * ------------------------------------------------------------------------------------------------
+ * Gaussian mixture only.  theta = (alpha, beta, m, C, v) the NIW posterior, prior = (alpha0, beta0, m0, C0, v0), Lbar_k = v_k C_k^-1,
+ * o(n) the observed entries of row n (D_o(n) of them; without a mask all D):
+ *   bound   = data - kl_pi - sum_k kl_nw_k
+ *   data    = sum_n [ logsumexp_k log rho_nk - 1/2 D_o(n) log 2 pi ]
+ *   log rho_nk = c_k - 1/2 q_o - sum_i log R_ii       the cell of "Mixture fitting on partly observed rows", from the fit pack
+ *                                                      [ m | Lbar packed lower | c_k ] of vmp_mixture_fit_pack; a complete row:
+ *                                                      c_k - 1/2 (x_n - m_k)^T Lbar_k (x_n - m_k)
+ *   kl_pi   = lgamma(sum alpha) - sum lgamma(alpha) - lgamma(sum alpha0) + sum lgamma(alpha0) + sum_k (alpha_k - alpha0_k) E log pi_k
+ *   kl_nw_k = 1/2 D log(beta / beta0) - 1/2 D + 1/2 D beta0 / beta + 1/2 beta0 (m - m0)^T Lbar (m - m0)
+ *             + logB(C, v) - logB(C0, v0) + 1/2 (v - v0) E log|Lambda| - 1/2 v D + 1/2 tr(C0 Lbar)
+ *   logB(C, nu) = 1/2 nu log|C| - 1/2 nu D log 2 - 1/4 D (D - 1) log pi - sum_{i=1..D} lgamma((nu + 1 - i) / 2)
+ * with E log pi and E log|Lambda| the expectations of the E-step, as vmp_mixture_fit_pack computes them (digamma arguments
+ * (v + 1 + i) / 2, log det P replaced by 0 where det P <= 1e-20).  It is the free energy of the state after an iteration: theta from
+ * the M-step, r from the E-step at that theta (the log-sum-exp is the optimum over q(z_n) q(x_n,m | z_n)).  With the reference's
+ * v_k = v_0 + N_k + 1 the M-step is not the exact optimum, so the bound need not rise at every single iteration.
+ *
+ * vmp_mixture_bound_pass: one streaming pass over x (N,D) (any alignment) and, if mask != NULL, mask (N,D) uint8, nonzero = missing,
+ *   then a one-wave launch that adds the per-block sums.  data_out (1) fp64, required; lse_out (N) fp32 = logsumexp_k log rho_nk
+ *   (without the 2 pi term), optional.  Per row the log-sum-exp is fp32; the rows are added in fp64 in a fixed order - lanes, waves,
+ *   blocks; no atomics, one geometry whichever outputs are requested: data_out is bit-identical from run to run and with or without
+ *   lse_out.  mask == NULL: nothing is factored, log rho = c - 1/2 d^T Lbar d.  With a mask the pass does the part of the fit pass's
+ *   cell that log rho needs: the factor and the forward substitution - no back-substitution, no inverse, no moments, no r.  The
+ *   value in a missing slot of x never enters arithmetic.  A row whose every term is -inf contributes -inf; a NaN pack gives NaN.
+ *   ws (vmp_mixture_bound_workspace_bytes: one fp64 word per block, 8-byte aligned) is always needed.
+ * vmp_mixture_bound_terms: one launch, one thread per component, fp64 inside:  out (2 + K) fp64 = [ kl_pi | sum_k kl_nw_k |
+ *   kl_nw_0 .. kl_nw_{K-1} ], the sums over k taken by one thread in k order.  A component whose C or C0 is not symmetric positive
+ *   definite gives NaN.
+ * Errors (decided before any launch): VMP_E_DIM (D, K outside 1..VMP_MAX_D / 1..VMP_MAX_K), VMP_E_BADARG (N < 1; x, fit_pack or
+ *   data_out NULL; a NULL prior, posterior or out of the terms; ws not 8-byte aligned), VMP_E_WS (ws NULL or too small).
+ *   vmp_mixture_bound_workspace_bytes is 0 outside the compiled range.                                                        */
+size_t vmp_mixture_bound_workspace_bytes(int64_t N, int D, int K);
+int    vmp_mixture_bound_pass(const float* x, const uint8_t* mask, int64_t N, int D, int K, const float* fit_pack, float* lse_out,
+                              double* data_out, void* ws, size_t ws_bytes, void* stream);
+int    vmp_mixture_bound_terms(int D, int K, const float* alpha0, const float* beta0, const float* m0, const float* C0, const float* v0,
+                               const float* alpha, const float* beta, const float* m, const float* C, const float* v, double* out,
+                               void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Mixture initialisation (csrc/vmp_seed.hip): seeded k-means++ centres and the responsibilities of the nearest centre, on the device
  * ------------------------------------------------------------------------------------------------
  * D^2-seeding (Arthur & Vassilvitskii 2007) of K centres from the rows of x (N,D) fp32, any alignment, as a pure function of (seed,

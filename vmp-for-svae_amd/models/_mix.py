@@ -368,6 +368,104 @@ def mixture_fit_pass(x, miss, pack, want_logr=False, want_fill=False, want_stats
     return r, logr, x_fill, stats
 
 
+def _bound_dims(x, miss, pack_or_m, what, pack=False):
+    """(N, D, K) of a lower-bound call, refused BEFORE the library or a device is touched: x (N >= 1, D), an optional mask (N,D) on
+    x's device and either the component locations (K,D) or a fit pack (K, D + D(D+1)/2 + 1) - a score or impute pack is wider and
+    would make the kernel read past its end"""
+    if pack:
+        if not torch.is_tensor(x) or x.dim() != 2:
+            raise L.VmpError('%s: x must be (N,D)' % what)
+        if not torch.is_tensor(pack_or_m) or pack_or_m.dim() != 2:
+            raise L.VmpError('%s: pack must be a (K, words) tensor from fit_pack' % what)
+        K = pack_or_m.shape[0]
+        N, D = _dims(x, K)
+        words = D + D * (D + 1) // 2 + 1
+        if pack_or_m.shape[1] != words:
+            raise L.VmpError('%s: pack has shape %s, expected (%d,%d): %d words per component is no fit pack for D=%d (fit_pack; a score '
+                             'pack or an impute pack does not do)' % (what, tuple(pack_or_m.shape), K, words, pack_or_m.shape[1], D))
+        if N < 1:
+            raise L.VmpError('%s: x has no rows' % what)
+    else:
+        N, D, K = _score_dims(x, pack_or_m, what)
+    if miss is not None:
+        if not torch.is_tensor(miss) or tuple(miss.shape) != (N, D):
+            raise L.VmpError('%s: the missing-data mask has shape %s, expected %s'
+                             % (what, tuple(miss.shape) if torch.is_tensor(miss) else type(miss), (N, D)))
+        if miss.device != x.device:
+            raise L.VmpError('%s: the missing-data mask is on %s, x on %s' % (what, miss.device, x.device))
+    return N, D, K
+
+
+def mixture_bound(x, miss, pack, want_rows=False):
+    """The data term of the variational lower bound in one streaming pass (vmp_mixture_bound_pass) over the rows of x (N,D) under a
+    fit pack: (data 0-dim fp64 on the device, lse (N,) fp32 or None), data = sum_n [logsumexp_k log rho_nk - 1/2 D_o(n) log 2 pi] and
+    lse_n the log-sum-exp alone.  miss (N,D), nonzero = missing, on x's device: the missing entries are integrated out as in
+    mixture_fit_pass and what their slots of x hold is never read into arithmetic; miss=None: every entry observed, nothing is
+    factored.  The sum is deterministic: the same bits from run to run and with or without want_rows.  No host synchronisation."""
+    N, D, K = _bound_dims(x, miss, pack, 'mixture_bound', pack=True)
+    x = L.dev_f32(x, 'x')
+    dev = x.device
+    pack = L.dev_f32(pack, 'pack', (K, L.lib().vmp_mixture_fit_pack_words(D)))
+    if pack.device != dev:
+        raise L.VmpError('pack is on %s, x on %s' % (pack.device, dev))
+    mask = None if miss is None else _mask_u8(miss)
+    data = torch.empty((), dtype=torch.float64, device=dev)
+    lse = torch.empty(N, dtype=torch.float32, device=dev) if want_rows else None
+    nb = L.lib().vmp_mixture_bound_workspace_bytes(N, D, K)
+    ws = L.workspace(dev, nb)
+    L.check(L.lib().vmp_mixture_bound_pass(L.ptr(x), L.ptr(mask), N, D, K, L.ptr(pack), L.ptr(lse), L.ptr(data), L.ptr(ws), nb,
+                                           L.stream()), 'vmp_mixture_bound_pass')
+    return data, lse
+
+
+def _niw_shapes(ops, names, K, D):
+    return [_kd(t, n, shp) for t, n, shp in zip(ops, names, _NIW[1](K, D))]
+
+
+def bound_terms(prior, theta):
+    """The K-sized terms of the variational lower bound (vmp_mixture_bound_terms): a (2+K,) fp64 device tensor
+    [KL(q(pi) || p(pi)) | sum_k KL(q(mu, Lambda)_k || p) | the K terms of that sum] from prior = (alpha_0, beta_0, m_0, C_0, v_0) and
+    theta = (alpha_k, beta_k, m_k, C_k, v_k); fp64 inside, the sums in k order.  One launch, no host synchronisation."""
+    if len(prior) != 5 or len(theta) != 5:
+        raise L.VmpError('bound_terms: prior and theta are (alpha, beta, m, C, v)')
+    m_k = theta[2]
+    if not torch.is_tensor(m_k) or m_k.dim() != 2:
+        raise L.VmpError('bound_terms: m_k must be (K,D)')
+    K, D = m_k.shape
+    theta = _niw_shapes(theta, _NIW[0], K, D)
+    a0, b0, m0, C0, v0 = prior
+    if torch.is_tensor(b0) and b0.numel() == K:
+        b0 = b0.reshape(K)
+    prior = _niw_shapes((a0, b0, m0, C0, v0), ('alpha_0', 'beta_0', 'm_0', 'C_0', 'v_0'), K, D)
+    if not (1 <= D <= L.MAX_D):
+        raise L.VmpError('D=%d outside the compiled range 1..%d' % (D, L.MAX_D))
+    if not (1 <= K <= L.MAX_K):
+        raise L.VmpError('K=%d outside the compiled range 1..%d' % (K, L.MAX_K))
+    dev = m_k.device
+    theta = [L.dev_f32(t.detach().to(torch.float32), n) for t, n in zip(theta, _NIW[0])]
+    prior = _prior(prior, K, D, dev)
+    out = torch.empty(2 + K, dtype=torch.float64, device=dev)
+    L.check(L.lib().vmp_mixture_bound_terms(D, K, *[L.ptr(t) for t in prior], *[L.ptr(t) for t in theta], L.ptr(out), L.stream()),
+            'vmp_mixture_bound_terms')
+    return out
+
+
+def lower_bound(x, theta, prior=None, miss=None):
+    """The variational lower bound (free energy) of the Gaussian-mixture posterior theta = (alpha_k, beta_k, m_k, C_k, v_k) on the rows
+    of x (N,D): a 0-dim fp64 device tensor, data - KL(q(pi) || p(pi)) - sum_k KL(q(mu, Lambda)_k || p) (include/vmp_hip.h "Variational
+    lower bound") with q(z) - and, under a mask, q(x_m | z) - at their optimum for theta: the free energy of a loop after step().
+    miss (N,D), nonzero = missing, on x's device; prior=None: default_prior.  fit_pack, mixture_bound, bound_terms and one
+    subtraction, all on the device: no host synchronisation."""
+    if len(theta) != 5:
+        raise L.VmpError('lower_bound: theta is (alpha_k, beta_k, m_k, C_k, v_k)')
+    N, D, K = _bound_dims(x, miss, theta[2], 'lower_bound')
+    theta = _niw_shapes(theta, _NIW[0], K, D)
+    prior = default_prior(K, D, x.device) if prior is None else prior
+    terms = bound_terms(prior, theta)
+    data, _ = mixture_bound(x, miss, fit_pack(*theta))
+    return data - (terms[0] + terms[1])
+
+
 def mean_filled(x, mask):
     """x with every missing entry replaced by its column's mean over the observed entries (0 for a column with none): the copy the
     masked loop takes the moments of r_init from."""
@@ -713,6 +811,41 @@ class VMPLoop(object):
             done += n
             hist.append((self.iterations, self.score(x_val)))
             if len(hist) > 1 and hist[-1][1] - hist[-2][1] < tol:
+                break
+        return hist
+
+    def _check_bound(self, need_posterior):
+        """the refusals of lower_bound() / run_until_bound(), on the host: nothing here looks at a device"""
+        if self.flavour != L.VMP_GMM:
+            raise L.VmpError('the lower bound is for the Gaussian mixture (VMP_GMM): the Student-t E-step of the reference is not the '
+                             'E-step of a bound')
+        if need_posterior and self.iterations == 0:
+            raise L.VmpError('no posterior to bound yet: run at least one iteration')
+
+    def lower_bound(self):
+        """The variational lower bound (free energy, nats) of the current posterior on the loop's own x, mask and prior - the state
+        step() leaves: theta from the M-step, r from the E-step at that theta (lower_bound() above).  Plain, masked and accurate=True
+        Gaussian loops; the pass is the fp32 one in all three.  Two K-sized launches, one streaming launch over x with its one-wave
+        sum, one scalar read-back."""
+        self._check_bound(True)
+        return lower_bound(self.x, self.theta(), prior=self.prior, miss=self.miss).item()
+
+    def run_until_bound(self, tol, check_every=5, max_iterations=1000):
+        """run(check_every) and lower_bound() in turn until the bound improves by less than tol * max(1, |bound|) over the previous
+        check, or `max_iterations` iterations of this call are done - convergence on the quantity the loop optimises, without
+        held-out rows.  Returns [(iterations, bound), ...] with `iterations` the loop's running count, as run_until does.  A plain
+        host loop: one scalar read-back per check."""
+        self._check_bound(False)
+        check_every = int(check_every)
+        if check_every < 1:
+            raise L.VmpError('check_every must be >= 1')
+        hist, done = [], 0
+        while done < max_iterations:
+            n = min(check_every, max_iterations - done)
+            self.run(n)
+            done += n
+            hist.append((self.iterations, self.lower_bound()))
+            if len(hist) > 1 and hist[-1][1] - hist[-2][1] < tol * max(1.0, abs(hist[-1][1])):
                 break
         return hist
 

@@ -145,6 +145,15 @@ def predictive_logprob(x, alpha_k, beta_k, m_k, C_k, v_k, return_resp=False):
     return (logp, total, resp) if return_resp else (logp, total)
 
 
+def lower_bound(x, alpha_k, beta_k, m_k, C_k, v_k, miss=None, prior=None):
+    """The variational lower bound (free energy, nats) of the NIW posterior (alpha_k, beta_k, m_k, C_k, v_k) that inference()'s theta
+    handle returns, on the rows of x (N,D): what the iteration optimises, to judge convergence without held-out rows and to compare
+    fits of the same data (another K, seed or init).  miss (N,D), nonzero = missing, for the theta of inference_missing(); prior
+    defaults to the one inference() hard-codes.  Two K-sized launches (vmp_mixture_fit_pack, vmp_mixture_bound_terms) and one
+    streaming HIP pass over x with its one-wave sum (vmp_mixture_bound_pass).  Returns a 0-dim fp64 DEVICE tensor (deterministic; no host synchronisation)."""
+    return _mix.lower_bound(x, (alpha_k, beta_k, m_k, C_k, v_k), prior=prior, miss=miss)
+
+
 def predictive_impute(x, miss, alpha_k, beta_k, m_k, C_k, v_k, return_resp=False):
     """Fill the missing entries of the rows of x (N,D) - miss (N,D), nonzero = missing, the convention of missing_data_mask - from
     the posterior predictive of the variational GMM (the Student-t mixture predictive_logprob scores): each missing block gets

@@ -349,6 +349,51 @@ int    vmp_mixture_bound_terms(int D, int K, const float* alpha0, const float* b
                                void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Mixture fitting on weighted rows (csrc/vmp_wfit.hip): counts, coresets, importance weights and 0/1 folds over resident rows
+ * ------------------------------------------------------------------------------------------------
+ * Gaussian mixture only.  Weights w (N) fp32, finite, >= 0: w_n makes row n count as w_n identical rows (integer weights reproduce
+ * the fit on the replicated rows); they need not sum to N.  With log rho_nk, the completed rows xhat^(k) and Cov^(k) exactly as in
+ * "Mixture fitting on partly observed rows" (a complete row: log rho_nk = c_k - 1/2 (x_n - m_k)^T Lbar_k (x_n - m_k), xhat = x_n,
+ * Cov = 0) and D_o(n) the number of observed entries of row n:
+ *   r_nk = softmax_k log rho_nk                     UNCHANGED: a weight does not enter a row's own responsibilities
+ *   Nk   = Wk = sum_n w_n r_nk
+ *   sx   = sum_n w_n r_nk xhat_n^(k)
+ *   sxx  = sum_n w_n r_nk ( xhat_n^(k) xhat_n^(k)^T + Cov_n^(k) )
+ *   data = sum_n w_n ( logsumexp_k log rho_nk - 1/2 D_o(n) log 2 pi )             the data term of "Variational lower bound"
+ *   lower bound = data - kl_pi - sum_k kl_nw_k      the two KL terms from vmp_mixture_bound_terms, unchanged
+ * A row with w_n = 0 is removed by a SELECT, not by a multiplication: whatever its x holds - NaN and +-Inf in observed slots
+ * included - reaches neither the moments nor data.  Its r (log r, x_fill) is still written, as whatever the E-step gives: the
+ * responsibilities of a held-out row.  Negative or non-finite weights are the caller's to refuse (models/_mix.py check_weights).
+ *
+ * vmp_mixture_wfit_pass: one streaming pass over x (N,D) (any alignment), w (N) and, if mask != NULL, mask (N,D) uint8, nonzero =
+ *   missing, under a FIT pack (vmp_mixture_fit_pack).  mask == NULL: nothing is factored.  Outputs, all optional but at least one:
+ *   r_out (N,K); logr_out (N,K) = log r (needs r_out); x_fill_out (N,D) as in vmp_mixture_fit_pass (needs a mask); stats_out
+ *   (K, vmp_mix_stats_words(D)) fp64 = [Nk | Wk = Nk | sx | sxx] (needs r_out); bound_out (1) fp64 = data.  r_out == NULL (and so
+ *   stats_out == NULL) is the bound-only form: no moments are formed.  The moments are accumulated as in vmp_mixture_fit_pass (fp32 on
+ *   xhat - m_k, flushed to fp64 every 128 rows of a wave, the waves added in a fixed order by a second launch that undoes the shift);
+ *   the rows' terms of data are added in fp64 in a fixed order - lanes, waves, blocks, the blocks by a one-wave launch.  No atomics,
+ *   one geometry whichever outputs are requested: moments and data are bit-identical from run to run and for every set of optional
+ *   outputs.  ws (vmp_mixture_wfit_workspace_bytes: the fp64 moments of every wave and one fp64 word per block, 8-byte aligned) is
+ *   always needed.
+ * vmp_mixture_wfit_iterate: `iterations` x (vmp_mix_finalize on stats -> vmp_mixture_fit_pack -> vmp_mixture_wfit_pass with stats_out =
+ *   stats, bound_out = bound) enqueued back to back, no host work in between; stats holds the weighted moments of the current r on
+ *   entry (vmp_mix_stats of r_nk w_n: the moments are linear in r) and of the last r on return.  logr, x_fill, xbar, S, pi and bound
+ *   may be NULL; r and stats may not.
+ * Errors (decided before any launch): VMP_E_DIM (D, K outside 1..VMP_MAX_D / 1..VMP_MAX_K), VMP_E_BADARG (N < 1; x, w or pack NULL; no
+ *   output; stats_out or logr_out without r_out; x_fill_out without mask; ws not 8-byte aligned; a NULL prior, posterior, r or stats
+ *   of the iteration; iterations < 0), VMP_E_WS (ws NULL or too small).  vmp_mixture_wfit_workspace_bytes is 0 outside the compiled
+ *   range.                                                                                                                   */
+size_t vmp_mixture_wfit_workspace_bytes(int64_t N, int D, int K);
+int    vmp_mixture_wfit_pass(const float* x, const float* w, const uint8_t* mask, int64_t N, int D, int K, const float* pack,
+                             float* r_out, float* logr_out, float* x_fill_out, double* stats_out, double* bound_out, void* ws,
+                             size_t ws_bytes, void* stream);
+int    vmp_mixture_wfit_iterate(const float* x, const float* w, const uint8_t* mask, int64_t N, int D, int K, const float* alpha0,
+                                const float* beta0, const float* m0, const float* C0, const float* v0, float* r, float* logr,
+                                float* x_fill, float* alpha, float* beta, float* m, float* C, float* v, float* xbar, float* S,
+                                float* pi, float* pack, double* stats, double* bound, void* ws, size_t ws_bytes, int iterations,
+                                void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Mixture initialisation (csrc/vmp_seed.hip): seeded k-means++ centres and the responsibilities of the nearest centre, on the device
  * ------------------------------------------------------------------------------------------------
  * D^2-seeding (Arthur & Vassilvitskii 2007) of K centres from the rows of x (N,D) fp32, any alignment, as a pure function of (seed,

@@ -55,6 +55,10 @@ _SIGNATURES = {
     'vmp_mixture_bound_workspace_bytes': (_c.c_size_t, [_c.c_int64, _c.c_int, _c.c_int]),
     'vmp_mixture_bound_pass': (_c.c_int, [_P, _P, _c.c_int64, _c.c_int, _c.c_int, _P, _P, _P, _P, _c.c_size_t, _P]),
     'vmp_mixture_bound_terms': (_c.c_int, [_c.c_int, _c.c_int] + [_P] * 11 + [_P]),
+    'vmp_mixture_wfit_workspace_bytes': (_c.c_size_t, [_c.c_int64, _c.c_int, _c.c_int]),
+    'vmp_mixture_wfit_pass': (_c.c_int, [_P, _P, _P, _c.c_int64, _c.c_int, _c.c_int, _P, _P, _P, _P, _P, _P, _P, _c.c_size_t, _P]),
+    'vmp_mixture_wfit_iterate': (_c.c_int, [_P, _P, _P, _c.c_int64, _c.c_int, _c.c_int] + [_P] * 5 + [_P] * 3 + [_P] * 8
+                                 + [_P, _P, _P, _P, _c.c_size_t, _c.c_int, _P]),
     'vmp_mixture_seed_workspace_bytes': (_c.c_size_t, [_c.c_int64, _c.c_int, _c.c_int]),
     'vmp_mixture_seed_centers': (_c.c_int, [_P, _P, _P, _c.c_int64, _c.c_int, _c.c_int, _c.c_uint64, _P, _P, _P, _P, _c.c_size_t, _P]),
     'vmp_mixture_seed_assign': (_c.c_int, [_P, _P, _c.c_int64, _c.c_int, _c.c_int, _P, _c.c_float, _P, _P, _P]),

@@ -450,20 +450,111 @@ def bound_terms(prior, theta):
     return out
 
 
-def lower_bound(x, theta, prior=None, miss=None):
+def lower_bound(x, theta, prior=None, miss=None, weights=None):
     """The variational lower bound (free energy) of the Gaussian-mixture posterior theta = (alpha_k, beta_k, m_k, C_k, v_k) on the rows
     of x (N,D): a 0-dim fp64 device tensor, data - KL(q(pi) || p(pi)) - sum_k KL(q(mu, Lambda)_k || p) (include/vmp_hip.h "Variational
     lower bound") with q(z) - and, under a mask, q(x_m | z) - at their optimum for theta: the free energy of a loop after step().
     miss (N,D), nonzero = missing, on x's device; prior=None: default_prior.  fit_pack, mixture_bound, bound_terms and one
-    subtraction, all on the device: no host synchronisation."""
+    subtraction, all on the device: no host synchronisation.  weights (N,) fp32 >= 0 on x's device: row n counts w_n times in the
+    data term and a row of weight 0 not at all (the bound-only form of mixture_wfit_pass; include/vmp_hip.h "Mixture fitting on
+    weighted rows"); weights=None is the unweighted pass, unchanged."""
     if len(theta) != 5:
         raise L.VmpError('lower_bound: theta is (alpha_k, beta_k, m_k, C_k, v_k)')
     N, D, K = _bound_dims(x, miss, theta[2], 'lower_bound')
+    if weights is not None:
+        _weights_dims(x, weights, 'lower_bound')
     theta = _niw_shapes(theta, _NIW[0], K, D)
     prior = default_prior(K, D, x.device) if prior is None else prior
     terms = bound_terms(prior, theta)
-    data, _ = mixture_bound(x, miss, fit_pack(*theta))
+    if weights is not None:
+        data = mixture_wfit_pass(x, weights, fit_pack(*theta), miss=miss, want_r=False, want_stats=False, want_bound=True)[4]
+    else:
+        data, _ = mixture_bound(x, miss, fit_pack(*theta))
     return data - (terms[0] + terms[1])
+
+
+def _weights_dims(x, weights, what):
+    """shape and device of the (N,) row weights, refused BEFORE the library or a device is touched"""
+    if not torch.is_tensor(x) or x.dim() != 2:
+        raise L.VmpError('%s: x must be (N,D)' % what)
+    if not torch.is_tensor(weights) or tuple(weights.shape) != (x.shape[0],):
+        raise L.VmpError('%s: the weights have shape %s, expected %s'
+                         % (what, tuple(weights.shape) if torch.is_tensor(weights) else type(weights), (x.shape[0],)))
+    if weights.device != x.device:
+        raise L.VmpError('%s: the weights are on %s, x on %s' % (what, weights.device, x.device))
+    if weights.dtype != torch.float32:
+        raise L.VmpError('%s: the weights must be float32 (got %s)' % (what, weights.dtype))
+
+
+def check_weights(x, weights):
+    """The row weights of a weighted fit, checked once (the loop's constructor calls this; a pass never does): shape (N,), fp32, on
+    x's device, and - one read-back of three flags - finite, >= 0 and not all zero.  Returns the weights."""
+    _weights_dims(x, weights, 'weights')
+    flags = torch.stack([torch.isfinite(weights).all(), (weights >= 0).all(), (weights > 0).any()]).tolist()
+    if not flags[0]:
+        raise L.VmpError('weights: every weight must be finite (found NaN or Inf)')
+    if not flags[1]:
+        raise L.VmpError('weights: every weight must be >= 0 (found a negative weight)')
+    if not flags[2]:
+        raise L.VmpError('weights: every weight is zero - nothing to fit')
+    return weights
+
+
+def mixture_wfit_pass(x, weights, pack, miss=None, want_r=True, want_logr=False, want_fill=False, want_stats=True, want_bound=False):
+    """One streaming pass (vmp_mixture_wfit_pass) over the rows of x (N,D), their weights (N,) fp32 >= 0 and, if given, their mask
+    miss (N,D; nonzero = missing) under a fit pack: (r (N,K), logr (N,K), x_fill (N,D), stats (K, 2+D+D*D) fp64, bound 0-dim fp64);
+    outputs that are not wanted are None.  r is the E-step of mixture_fit_pass - a weight does not enter a row's own
+    responsibilities; stats are the raw moments [Nk | Wk | sx | sxx] with every row counted w_n times; bound is the data term
+    sum_n w_n (logsumexp_k log rho_nk - 1/2 D_o(n) log 2 pi) of the lower bound.  A row of weight 0 reaches neither stats nor bound,
+    whatever its x holds; its r is that of a held-out row.  miss=None: complete rows, nothing is factored.  want_logr and want_stats
+    need want_r, want_fill needs a mask; want_r=False with want_bound is the bound-only form.  The weights are taken as they are
+    (check_weights is the loop's business).  stats and bound are the same bits from run to run and for every set of outputs.  No host
+    synchronisation."""
+    what = 'mixture_wfit_pass'
+    N, D, K = _bound_dims(x, miss, pack, what, pack=True)
+    _weights_dims(x, weights, what)
+    if not (want_r or want_logr or want_fill or want_stats or want_bound):
+        raise L.VmpError('%s: no output requested' % what)
+    if (want_stats or want_logr) and not want_r:
+        raise L.VmpError('%s: want_stats and want_logr need want_r (the moments are those of the r the pass writes)' % what)
+    if want_fill and miss is None:
+        raise L.VmpError('%s: want_fill needs a mask (a complete row has nothing to fill)' % what)
+    x = L.dev_f32(x, 'x')
+    dev = x.device
+    pack = L.dev_f32(pack, 'pack', (K, L.lib().vmp_mixture_fit_pack_words(D)))
+    if pack.device != dev:
+        raise L.VmpError('pack is on %s, x on %s' % (pack.device, dev))
+    w = L.dev_f32(weights, 'weights', (N,))
+    mask = None if miss is None else _mask_u8(miss)
+    f32 = dict(dtype=torch.float32, device=dev)
+    r = torch.empty(N, K, **f32) if want_r else None
+    logr = torch.empty(N, K, **f32) if want_logr else None
+    x_fill = torch.empty(N, D, **f32) if want_fill else None
+    stats = torch.empty((K, L.lib().vmp_mix_stats_words(D)), dtype=torch.float64, device=dev) if want_stats else None
+    bound = torch.empty((), dtype=torch.float64, device=dev) if want_bound else None
+    nb = L.lib().vmp_mixture_wfit_workspace_bytes(N, D, K)
+    ws = L.workspace(dev, nb)
+    L.check(L.lib().vmp_mixture_wfit_pass(L.ptr(x), L.ptr(w), L.ptr(mask), N, D, K, L.ptr(pack), L.ptr(r), L.ptr(logr), L.ptr(x_fill),
+                                          L.ptr(stats), L.ptr(bound), L.ptr(ws), nb, L.stream()), 'vmp_mixture_wfit_pass')
+    return r, logr, x_fill, stats, bound
+
+
+def weighted_mean_filled(x, mask, w):
+    """The copy of x a weighted loop takes the moments of r_init from: a missing entry (mask (N,D) or None) holds its column's
+    weighted mean over the observed entries of the rows that count (sum_n w_n x_nd / sum_n w_n; 0 for a column with none) - with
+    integer weights the fill mean_filled gives on the replicated rows - and a row of weight 0 is all zeros, so that what it holds
+    (NaN included) cannot reach 0 * x."""
+    drop = (w == 0)[:, None]
+    gone = drop.expand_as(x) if mask is None else ((mask != 0) | drop)
+    zero = torch.zeros((), dtype=x.dtype, device=x.device)
+    if mask is None:
+        return torch.where(gone, zero, x).contiguous()
+    wd = torch.where(gone, torch.zeros((), dtype=torch.float64, device=x.device), w.double()[:, None].expand_as(x))
+    num = (torch.where(gone, zero, x).double() * wd).sum(0)
+    den = wd.sum(0)
+    mean = torch.where(den > 0, num / den.clamp_min(1e-300), torch.zeros_like(num)).to(x.dtype)
+    out = torch.where(mask != 0, mean[None, :].expand_as(x), x)
+    return torch.where(drop, zero, out).contiguous()
 
 
 def mean_filled(x, mask):
@@ -591,10 +682,19 @@ class VMPLoop(object):
     variables of the posterior (include/vmp_hip.h "Mixture fitting on partly observed rows").  An iteration is vmp_mix_finalize on
     the (K, stats words) moments of the completed rows, vmp_mixture_fit_pack, and the streaming vmp_mixture_fit_pass with its
     fixed-order reduction; run() enqueues them through vmp_mixture_fit_iterate.  filled() returns x with its gaps filled.  miss=None
-    is the loop described above, unchanged."""
+    is the loop described above, unchanged.
+    weights=w (GMM only; (N,) fp32 on x's device, finite, >= 0, not all zero - check_weights, one read-back, here and nowhere else):
+    row n counts as w_n identical rows (include/vmp_hip.h "Mixture fitting on weighted rows") - counts of binned data, coresets,
+    importance weights, and 0/1 folds over the same resident x.  A row of weight 0 is held out: it reaches nothing the fit adds up,
+    whatever it holds, and its r is what the E-step gives.  An iteration is vmp_mix_finalize -> vmp_mixture_fit_pack ->
+    vmp_mixture_wfit_pass, with or without miss=; run() goes through vmp_mixture_wfit_iterate; the pass leaves the data term of the
+    lower bound behind, so lower_bound() costs one K-sized launch and no further pass over x.  weights=None is today's code path."""
 
-    def __init__(self, x, r_init, flavour, kappa=None, u_init=None, prior=None, accurate=False, miss=None):
+    def __init__(self, x, r_init, flavour, kappa=None, u_init=None, prior=None, accurate=False, miss=None, weights=None):
         self.miss = None
+        self.w = None
+        if weights is not None:
+            self._check_weighted(x, weights, flavour, accurate)        # before the device is touched
         if miss is not None:
             self._check_miss(x, miss, flavour, accurate)               # before the device is touched
         self.x = L.dev_f32(x, 'x')
@@ -616,6 +716,9 @@ class VMPLoop(object):
         self.accurate = bool(accurate)
         self.iterations = 0
         self.pack64 = None
+        if weights is not None:
+            self._init_weighted(weights, miss)
+            return
         if miss is not None:
             self._init_masked(miss)
             return
@@ -637,6 +740,19 @@ class VMPLoop(object):
         r0 = seeded_r_init(x, K, seed, miss=miss, smooth=smooth)
         return cls(x, r0, flavour, kappa=kappa, prior=prior, accurate=accurate, miss=miss)
 
+    @classmethod
+    def from_seed_weighted(cls, x, weights, K, flavour, seed, prior=None, accurate=False, miss=None, smooth=0.0):
+        """from_seed() for a weighted loop (its signature is pinned by the seeding tests, hence a method of its own).  The weights go
+        to the loop only: the k-means++ seeding itself is unweighted in this version - every row of x, those of weight 0 included, can
+        become a centre with the probability its distance gives it - so x must be finite in its observed slots throughout.  The
+        refusals of the constructor come first, the value check of the weights included: nothing is seeded from weights that the
+        constructor would refuse (it checks them again: two scalar read-backs on this path)."""
+        cls._check_weighted(x, weights, flavour, accurate)
+        if miss is not None:
+            cls._check_miss(x, miss, flavour, accurate)
+        r0 = seeded_r_init(x, K, seed, miss=miss, smooth=smooth)
+        return cls(x, r0, flavour, prior=prior, accurate=accurate, miss=miss, weights=weights)
+
     @staticmethod
     def _check_miss(x, miss, flavour, accurate):
         """the refusals of a masked loop, on the host: nothing here looks at a device"""
@@ -652,6 +768,37 @@ class VMPLoop(object):
                                                                                  tuple(x.shape)))
         if miss.device != x.device:
             raise L.VmpError('the missing-data mask is on %s, x on %s' % (miss.device, x.device))
+
+    @staticmethod
+    def _check_weighted(x, weights, flavour, accurate, values=True):
+        """the refusals of a weighted loop, on the host; the value check of the weights is the one read-back (check_weights);
+        values=False: shape, dtype and device only"""
+        if flavour != L.VMP_GMM:
+            raise L.VmpError('weights= is for the Gaussian mixture (VMP_GMM): the Student-t mixture has no weighted pass')
+        if accurate:
+            raise L.VmpError('weights= and accurate=True do not combine: the weighted pass has no fp64 form')
+        if values:
+            check_weights(x, weights)
+        else:
+            _weights_dims(x, weights, 'weights')
+
+    def _init_weighted(self, weights, miss):
+        """State of the loop on weighted rows, like the masked one: the moments live in self._stats (K, stats words) fp64 - seeded
+        here by vmp_mix_stats from r_init * w (the moments are linear in r) on weighted_mean_filled(x, miss, w) - and every iteration is
+        vmp_mix_finalize -> vmp_mixture_fit_pack -> vmp_mixture_wfit_pass (csrc/vmp_wfit.hip), which also leaves the data term of the
+        lower bound in self._data."""
+        dev, N, D, K = self.x.device, self.N, self.D, self.K
+        self.w = L.dev_f32(weights, 'weights', (N,))
+        self.miss = None if miss is None else _mask_u8(miss)
+        keep = (self.w != 0)[:, None]
+        rw = torch.where(keep, self.r * self.w[:, None], torch.zeros((), dtype=torch.float32, device=dev))
+        self._stats = raw_stats(weighted_mean_filled(self.x, self.miss, self.w), rw)
+        self.fpack = torch.empty(K, L.lib().vmp_mixture_fit_pack_words(D), dtype=torch.float32, device=dev)
+        self.x_fill = None if miss is None else torch.empty_like(self.x)
+        self._data = torch.empty((), dtype=torch.float64, device=dev)
+        self.nb = L.lib().vmp_mixture_wfit_workspace_bytes(N, D, K)
+        self.ws = torch.empty(self.nb, dtype=torch.uint8, device=dev)
+        self.pivot = None
 
     def _init_masked(self, miss):
         """State of the loop on partly observed rows: the moments live in self._stats (K, stats words) fp64 - seeded here from r_init
@@ -673,7 +820,7 @@ class VMPLoop(object):
                                                                       self.post if post else None)
 
     def finalize(self, stats_out=None):
-        if self.miss is not None:
+        if self.miss is not None or self.w is not None:
             L.check(L.lib().vmp_mix_finalize(L.ptr(self._stats), *_fin_tail(self.D, self.K, self.flavour, self.prior, None, self.post),
                                              L.stream()), 'vmp_mix_finalize')
             p = self.post
@@ -693,6 +840,12 @@ class VMPLoop(object):
         """E-pass with fused moments on the current pack (the second launch of an iteration)"""
         if want_logr and self.logr is None:
             self.logr = torch.empty_like(self.r)
+        if self.w is not None:
+            L.check(L.lib().vmp_mixture_wfit_pass(L.ptr(self.x), L.ptr(self.w), L.ptr(self.miss), self.N, self.D, self.K, L.ptr(self.fpack),
+                                                  L.ptr(self.r), L.ptr(self.logr if want_logr else None), L.ptr(self.x_fill),
+                                                  L.ptr(self._stats), L.ptr(self._data), L.ptr(self.ws), self.nb, L.stream()),
+                    'vmp_mixture_wfit_pass')
+            return
         if self.miss is not None:
             L.check(L.lib().vmp_mixture_fit_pass(L.ptr(self.x), L.ptr(self.miss), self.N, self.D, self.K, L.ptr(self.fpack), L.ptr(self.r),
                                                  L.ptr(self.logr if want_logr else None), L.ptr(self.x_fill), L.ptr(self._stats),
@@ -723,6 +876,15 @@ class VMPLoop(object):
         if self.accurate:
             for _ in range(int(iterations)):
                 self.step()
+            return self.r
+        if self.w is not None:
+            p = self.post
+            L.check(L.lib().vmp_mixture_wfit_iterate(L.ptr(self.x), L.ptr(self.w), L.ptr(self.miss), self.N, self.D, self.K,
+                                                     *[L.ptr(t) for t in self.prior], L.ptr(self.r), None, L.ptr(self.x_fill),
+                                                     *[L.ptr(p[k]) for k in _POST[:8]], L.ptr(self.fpack), L.ptr(self._stats),
+                                                     L.ptr(self._data), L.ptr(self.ws), self.nb, int(iterations), L.stream()),
+                    'vmp_mixture_wfit_iterate')
+            self.iterations += int(iterations)
             return self.r
         if self.miss is not None:
             p = self.post
@@ -826,8 +988,11 @@ class VMPLoop(object):
         """The variational lower bound (free energy, nats) of the current posterior on the loop's own x, mask and prior - the state
         step() leaves: theta from the M-step, r from the E-step at that theta (lower_bound() above).  Plain, masked and accurate=True
         Gaussian loops; the pass is the fp32 one in all three.  Two K-sized launches, one streaming launch over x with its one-wave
-        sum, one scalar read-back."""
+        sum, one scalar read-back.  A weighted loop: the weighted data term its own pass wrote, minus the same two KL terms."""
         self._check_bound(True)
+        if self.w is not None:          # the pass of the last iteration left its data term: one K-sized launch, no pass over x
+            terms = bound_terms(self.prior, self.theta())
+            return (self._data - (terms[0] + terms[1])).item()
         return lower_bound(self.x, self.theta(), prior=self.prior, miss=self.miss).item()
 
     def run_until_bound(self, tol, check_every=5, max_iterations=1000):
@@ -853,7 +1018,7 @@ class VMPLoop(object):
     def stats(self):
         """Raw moments of the current r (reduces the partials the last pass left in the workspace; a masked loop keeps them
         reduced: the moments of the completed rows, conditional covariances included)."""
-        if self.miss is not None:
+        if self.miss is not None or self.w is not None:
             return self._stats.clone()
         st = torch.empty((self.K, L.lib().vmp_mix_stats_words(self.D)), dtype=torch.float64, device=self.x.device)
         keep = {k: v.clone() for k, v in self.post.items()}

@@ -145,13 +145,15 @@ def predictive_logprob(x, alpha_k, beta_k, m_k, C_k, v_k, return_resp=False):
     return (logp, total, resp) if return_resp else (logp, total)
 
 
-def lower_bound(x, alpha_k, beta_k, m_k, C_k, v_k, miss=None, prior=None):
+def lower_bound(x, alpha_k, beta_k, m_k, C_k, v_k, miss=None, prior=None, weights=None):
     """The variational lower bound (free energy, nats) of the NIW posterior (alpha_k, beta_k, m_k, C_k, v_k) that inference()'s theta
     handle returns, on the rows of x (N,D): what the iteration optimises, to judge convergence without held-out rows and to compare
     fits of the same data (another K, seed or init).  miss (N,D), nonzero = missing, for the theta of inference_missing(); prior
     defaults to the one inference() hard-codes.  Two K-sized launches (vmp_mixture_fit_pack, vmp_mixture_bound_terms) and one
-    streaming HIP pass over x with its one-wave sum (vmp_mixture_bound_pass).  Returns a 0-dim fp64 DEVICE tensor (deterministic; no host synchronisation)."""
-    return _mix.lower_bound(x, (alpha_k, beta_k, m_k, C_k, v_k), prior=prior, miss=miss)
+    streaming HIP pass over x with its one-wave sum (vmp_mixture_bound_pass).  Returns a 0-dim fp64 DEVICE tensor (deterministic; no host synchronisation).
+    weights (N,) fp32 >= 0 on x's device, for the theta of inference_weighted(): row n counts w_n times in the data term, a row of
+    weight 0 not at all (the bound-only form of vmp_mixture_wfit_pass); weights=None is the unweighted pass, unchanged."""
+    return _mix.lower_bound(x, (alpha_k, beta_k, m_k, C_k, v_k), prior=prior, miss=miss, weights=weights)
 
 
 def predictive_impute(x, miss, alpha_k, beta_k, m_k, C_k, v_k, return_resp=False):
@@ -219,6 +221,28 @@ def inference_missing(x, miss, K, seed, name='inference_missing', r_init=None, i
     if r_init is None:
         r_init = _dirichlet_init(N, K, seed, x.device)
     loop = _mix.VMPLoop(x, r_init, L.VMP_GMM, miss=miss)
+
+    def step():
+        return loop.step(want_logr=True)
+
+    return (step, _Handle(lambda: loop.logr), _Handle(loop.theta), _Handle(loop.aux), _Handle(loop.filled))
+
+
+def inference_weighted(x, weights, K, seed, miss=None, r_init=None, init='random'):
+    """inference() on weighted rows: weights (N,) fp32 on x's device, finite, >= 0, not all zero - row n counts as w_n identical rows
+    (counts of binned or de-duplicated data, coresets, importance weights; a 0/1 vector is a fold over the same resident x, and a row
+    of weight 0 reaches nothing the fit adds up, whatever it holds).  A weight does not enter a row's own responsibilities; it scales
+    the row's share of the moments and of the lower bound, in one streaming HIP pass (csrc/vmp_wfit.hip).  miss (N,D), nonzero =
+    missing, as in inference_missing().  Returns (step, log_r_nk, theta, (x_k, S_k, pi), x_filled) as inference_missing() does;
+    x_filled() is for a fit with a mask.  init='kmeans++': r_init from _mix.seed_centers / seed_assign; that seeding is unweighted."""
+    _mix.check_init(init)
+    N, D = x.shape
+    if r_init is None:
+        _mix.VMPLoop._check_weighted(x, weights, L.VMP_GMM, False)                   # before anything is seeded
+        if miss is not None:
+            _mix.VMPLoop._check_miss(x, miss, L.VMP_GMM, False)
+        r_init = _mix.seeded_r_init(x, K, seed, miss=miss) if init == 'kmeans++' else _dirichlet_init(N, K, seed, x.device)
+    loop = _mix.VMPLoop(x, r_init, L.VMP_GMM, miss=miss, weights=weights)
 
     def step():
         return loop.step(want_logr=True)

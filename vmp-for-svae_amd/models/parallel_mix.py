@@ -240,8 +240,10 @@ class DistributedVMPLoop(_mix.VMPLoop):
     score() / run_until() are inherited: they score the rows THIS rank passes in under the (global) posterior; no collective is
     added - a cross-rank mean is the caller's all-reduce of (total, rows)."""
 
-    def __init__(self, x, r_init, flavour, kappa=None, u_init=None, prior=None, group=None, comm=None, exchange=None):
+    def __init__(self, x, r_init, flavour, kappa=None, u_init=None, prior=None, group=None, comm=None, exchange=None, weights=None):
         # (the data-parallel iteration keeps two launches: the exchange sits between the partial sums and the posterior)
+        if weights is not None:
+            raise L.VmpError('weights= is for the single-device loop (VMPLoop): the data-parallel iteration has no weighted pass')
         super().__init__(x, r_init, flavour, kappa=kappa, u_init=u_init, prior=prior)
         self.group, self.comm, self.exchange = group, comm, exchange
         self._stats = torch.empty((self.K, L.lib().vmp_mix_stats_words(self.D)), dtype=torch.float64,

@@ -4,8 +4,11 @@
 // Lane l = (i16 = l & 15, kk = l >> 4) owns mixture component k = i16 (+16 per extra component tile) and the data
 // rows n8+kk and n8+4+kk of a group:
 //   E-part  (packed fp32 VALU): q = ||W_k (x_n - m_k)||^2 with W_k, m_k resident in the lane's VGPRs (loaded once
-//            per kernel), the two rows of the lane packed into v_pk_fma_f32; softmax over k = all-reduce over the
-//            16 lanes of a DPP row (v_*_dpp row_ror), no scalar loads in the loop;
+//            per kernel), the two rows of the lane packed into v_pk_fma_f32; softmax over k = reductions over the
+//            16 lanes of a DPP row, no scalar loads in the loop: an all-reduce (v_*_dpp row_ror butterfly) in the
+//            general form, and on whole tiles of K = 16 a reduce-scatter of a lane's four rows into the four banks
+//            of the DPP row (half the DPP instructions, one v_rcp_f32 for the four rows), read back by
+//            row_newbcast - same pairs added in the same order, bit-identical (row16_rs4_* below);
 //   M-part  (matrix pipe): sum_n w_nk * [1 | x_n | x_n x_n^T] as a GEMM with the data row as inner index.  fp32 MFMA
 //            runs on the VALU's issue slots on gfx950 (round-1 measurement), so the operands are split into three
 //            bf16 terms each (v = h + m + l, 8 bits per term, |residual| < 2^-26 |v|) and the six products of order
@@ -109,7 +112,7 @@ __device__ __forceinline__ v2f row16_sum2(v2f v) {
     "v_" OP "_f32_dpp %1, %5, %5 " CTRL " row_mask:0xf bank_mask:0xf\n\t"  \
     "v_" OP "_f32_dpp %2, %6, %6 " CTRL " row_mask:0xf bank_mask:0xf\n\t"  \
     "v_" OP "_f32_dpp %3, %7, %7 " CTRL " row_mask:0xf bank_mask:0xf\n\t"
-__device__ __forceinline__ void row16_max4(v2f v0, v2f v1, v2f& o0, v2f& o1) {
+[[maybe_unused]] __device__ __forceinline__ void row16_max4(v2f v0, v2f v1, v2f& o0, v2f& o1) {
     float a, b, c, d;
     asm("s_nop 1\n\t" VMP_DPP4_FIRST("max", "row_ror:8") VMP_DPP4("max", "row_ror:4") VMP_DPP4("max", "row_ror:2")
         VMP_DPP4("max", "row_ror:1")
@@ -117,7 +120,7 @@ __device__ __forceinline__ void row16_max4(v2f v0, v2f v1, v2f& o0, v2f& o1) {
     o0 = v2f{a, b};
     o1 = v2f{c, d};
 }
-__device__ __forceinline__ void row16_sum4(v2f v0, v2f v1, v2f& o0, v2f& o1) {
+[[maybe_unused]] __device__ __forceinline__ void row16_sum4(v2f v0, v2f v1, v2f& o0, v2f& o1) {
     float a, b, c, d;
     asm("s_nop 1\n\t" VMP_DPP4_FIRST("add", "row_ror:8") VMP_DPP4("add", "row_ror:4") VMP_DPP4("add", "row_ror:2")
         VMP_DPP4("add", "row_ror:1")
@@ -126,11 +129,54 @@ __device__ __forceinline__ void row16_sum4(v2f v0, v2f v1, v2f& o0, v2f& o1) {
     o1 = v2f{c, d};
 }
 
+// Reduce-scatter form of the four reductions (whole tiles only): registers v = 0..3 in, ONE register out, in which the four lanes
+// of bank v (lanes 4 v .. 4 v + 3 of every DPP row) hold the reduction of register v over the row's 16 lanes.  A DPP lane i of
+// row_ror:n reads lane (i - n) mod 16 of its row; a bank-masked instruction writes the enabled banks and leaves the others.
+//   step 1 (pairs L, L + 8):   a0 = banks {0,1} <- v0, banks {2,3} <- v2;   a1 = banks {0,1} <- v1, banks {2,3} <- v3
+//   step 2 (pairs L, L + 4):   b  = banks 0, 2 <- a0 with its neighbour bank above (row_ror:12 = -4),
+//                                   banks 1, 3 <- a1 with its neighbour bank below (row_ror:4)          => bank v holds register v
+//   steps 3, 4 (pairs L ^ 2, L ^ 1 inside the bank): quad_perm [2,3,0,1], then [1,0,3,2]
+// 8 DPP instructions instead of 16.  Every addition pairs the two operands the butterfly of row16_sum4 pairs at that step
+// ((v_L + v_L+8), + the same of L +- 4, + of L +- 2, + of L +- 1; fp32 addition commutes), so the sum has the butterfly's bits
+// (tests/mix_softmax_net_model.py holds the lane maps to that).  Wait states as above: a DPP read two instructions or less after
+// the VALU write of the same VGPR gets its s_nop; TAIL pads the end for a DPP consumer the compiler places right behind the
+// statement (the maximum's: the sum's first consumer is v_rcp_f32, no DPP read).
+#define VMP_RS4(OP, TAIL)                                                                   \
+    "s_nop 1\n\t"                                                                           \
+    "v_" OP "_f32_dpp %0, %3, %3 row_ror:8 row_mask:0xf bank_mask:0x3\n\t"                \
+    "v_" OP "_f32_dpp %0, %5, %5 row_ror:8 row_mask:0xf bank_mask:0xc\n\t"                \
+    "v_" OP "_f32_dpp %1, %4, %4 row_ror:8 row_mask:0xf bank_mask:0x3\n\t"                \
+    "v_" OP "_f32_dpp %1, %6, %6 row_ror:8 row_mask:0xf bank_mask:0xc\n\t"                \
+    "v_" OP "_f32_dpp %2, %0, %0 row_ror:12 row_mask:0xf bank_mask:0x5\n\t"               \
+    "s_nop 0\n\t"                                                                           \
+    "v_" OP "_f32_dpp %2, %1, %1 row_ror:4 row_mask:0xf bank_mask:0xa\n\t"                \
+    "s_nop 1\n\t"                                                                           \
+    "v_" OP "_f32_dpp %2, %2, %2 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"      \
+    "s_nop 1\n\t"                                                                           \
+    "v_" OP "_f32_dpp %2, %2, %2 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t" TAIL
+// (a0, a1 and b are each written in full - by two complementary bank masks - before they are read: plain early-clobber outputs)
+__device__ __forceinline__ float row16_rs4_max(v2f v0, v2f v1) {
+    float a0, a1, b;
+    asm(VMP_RS4("max", "s_nop 1\n\t") : "=&v"(a0), "=&v"(a1), "=&v"(b) : "v"(v0.x), "v"(v0.y), "v"(v1.x), "v"(v1.y));
+    return b;
+}
+__device__ __forceinline__ float row16_rs4_sum(v2f v0, v2f v1) {
+    float a0, a1, b;
+    asm(VMP_RS4("add", "") : "=&v"(a0), "=&v"(a1), "=&v"(b) : "v"(v0.x), "v"(v0.y), "v"(v1.x), "v"(v1.y));
+    return b;
+}
+// register v of the consumer takes the scattered value of its row from the first lane of bank v (row_newbcast:4 v)
+template <int V>
+__device__ __forceinline__ float row16_bcast_bank(float s) {
+    return __uint_as_float(__builtin_amdgcn_update_dpp(0u, __float_as_uint(s), 0x150 + 4 * V, 0xf, 0xf, true));
+}
+
 // Exploration switch of the streaming loop of pass_xdl_body (tools/build_variant.sh ... -DVMP_PASS_PIPE=n), for the attribution in
-// profiles/NOTES_mix_pass_pipeline.md: 1 = straight-line full tiles, the staging still waits for the tile's stores;
-// 2 = + counted wait (the staging waits for the row loads only); 3 = + four-wide DPP reductions.
+// profiles/NOTES_mix_pass_pipeline.md and NOTES_mix_softmax_net.md: 1 = straight-line full tiles, the staging still waits for the
+// tile's stores; 2 = + counted wait (the staging waits for the row loads only); 3 = + four-wide DPP reductions; 4 = the reductions as
+// a reduce-scatter (row16_rs4_*) and one reciprocal for the four rows of a lane.
 #ifndef VMP_PASS_PIPE
-#define VMP_PASS_PIPE 3
+#define VMP_PASS_PIPE 4
 #endif
 
 constexpr int MOM_TERMS = 3;
@@ -1003,29 +1049,43 @@ __device__ __forceinline__ void pass_xdl_body(const PassArgs& a) {
                 lg[h] = pk_const_minus_scaled(qh, pch);                 // log2 rho
                 if constexpr (SMM) uu[h] = v2f{pua * __builtin_amdgcn_rcpf(qh.x + pub), pua * __builtin_amdgcn_rcpf(qh.y + pub)};
             }
-            v2f mx[2], ssum[2];
-            if constexpr (LINE && VMP_PASS_PIPE >= 3) {
-                row16_max4(lg[0], lg[1], mx[0], mx[1]);
+            if constexpr (LINE && VMP_PASS_PIPE >= 4) {
+                // whole tile (FULL): maximum and sum as reduce-scatters, each row's value read back from its bank; one reciprocal
+                // serves the lane's four rows.  Same maxima, same addition tree, same rcp operand: the bits of the branch below.
+                static_assert(FULL, "straight-line tiles are whole tiles");
+                const float mxs = row16_rs4_max(lg[0], lg[1]);
+                lg[0] = v2f{__builtin_amdgcn_exp2f(lg[0].x - row16_bcast_bank<0>(mxs)), __builtin_amdgcn_exp2f(lg[0].y - row16_bcast_bank<1>(mxs))};
+                lg[1] = v2f{__builtin_amdgcn_exp2f(lg[1].x - row16_bcast_bank<2>(mxs)), __builtin_amdgcn_exp2f(lg[1].y - row16_bcast_bank<3>(mxs))};
+                const float invs = __builtin_amdgcn_rcpf(row16_rs4_sum(lg[0], lg[1]));
+                rr[0] = v2f{lg[0].x * row16_bcast_bank<0>(invs), lg[0].y * row16_bcast_bank<1>(invs)};
+                rr[1] = v2f{lg[1].x * row16_bcast_bank<2>(invs), lg[1].y * row16_bcast_bank<3>(invs)};
 #pragma unroll
-                for (int h = 0; h < 2; ++h) lg[h] = v2f{__builtin_amdgcn_exp2f(lg[h].x - mx[h].x), __builtin_amdgcn_exp2f(lg[h].y - mx[h].y)};
-                row16_sum4(lg[0], lg[1], ssum[0], ssum[1]);
+                for (int h = 0; h < 2; ++h) w[h] = SMM ? rr[h] * uu[h] : rr[h];
             } else {
+                v2f mx[2], ssum[2];
+                if constexpr (LINE && VMP_PASS_PIPE >= 3) {
+                    row16_max4(lg[0], lg[1], mx[0], mx[1]);
+#pragma unroll
+                    for (int h = 0; h < 2; ++h) lg[h] = v2f{__builtin_amdgcn_exp2f(lg[h].x - mx[h].x), __builtin_amdgcn_exp2f(lg[h].y - mx[h].y)};
+                    row16_sum4(lg[0], lg[1], ssum[0], ssum[1]);
+                } else {
+#pragma unroll
+                    for (int h = 0; h < 2; ++h) {
+                        mx[h] = row16_max2(lg[h]);
+                        lg[h] = v2f{__builtin_amdgcn_exp2f(lg[h].x - mx[h].x), __builtin_amdgcn_exp2f(lg[h].y - mx[h].y)};
+                        ssum[h] = row16_sum2(lg[h]);
+                    }
+                }
 #pragma unroll
                 for (int h = 0; h < 2; ++h) {
-                    mx[h] = row16_max2(lg[h]);
-                    lg[h] = v2f{__builtin_amdgcn_exp2f(lg[h].x - mx[h].x), __builtin_amdgcn_exp2f(lg[h].y - mx[h].y)};
-                    ssum[h] = row16_sum2(lg[h]);
+                    v2f inv = v2f{__builtin_amdgcn_rcpf(ssum[h].x), __builtin_amdgcn_rcpf(ssum[h].y)};
+                    if constexpr (!FULL) {
+                        const bool va = row0 + n16 + 8 * h + kk < hi, vb = row0 + n16 + 8 * h + 4 + kk < hi;
+                        inv = v2f{va ? inv.x : 0.f, vb ? inv.y : 0.f};
+                    }
+                    rr[h] = lg[h] * inv;
+                    w[h] = SMM ? rr[h] * uu[h] : rr[h];
                 }
-            }
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                v2f inv = v2f{__builtin_amdgcn_rcpf(ssum[h].x), __builtin_amdgcn_rcpf(ssum[h].y)};
-                if constexpr (!FULL) {
-                    const bool va = row0 + n16 + 8 * h + kk < hi, vb = row0 + n16 + 8 * h + 4 + kk < hi;
-                    inv = v2f{va ? inv.x : 0.f, vb ? inv.y : 0.f};
-                }
-                rr[h] = lg[h] * inv;
-                w[h] = SMM ? rr[h] * uu[h] : rr[h];
             }
             // ---- stores: for fixed v the 64 lanes cover rows n16 + 4 v .. + 3 x 16 components = 256 contiguous bytes
 #pragma unroll

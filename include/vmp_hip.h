@@ -34,6 +34,7 @@ extern "C" {
 
 #define VMP_MAX_D 8           /* latent / data dimension of the mixture (compiled range 1..8)  */
 #define VMP_MAX_K 64          /* mixture components                                             */
+#define VMP_DIAG_MAX_D 64     /* data dimension of the diagonal-covariance mixture (compiled range 1..64) */
 
 /* mixture flavour */
 #define VMP_GMM 0             /* models/gmm.py  (Bishop 10.2)                */
@@ -392,6 +393,67 @@ int    vmp_mixture_wfit_iterate(const float* x, const float* w, const uint8_t* m
                                 float* x_fill, float* alpha, float* beta, float* m, float* C, float* v, float* xbar, float* S,
                                 float* pi, float* pack, double* stats, double* bound, void* ws, size_t ws_bytes, int iterations,
                                 void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Diagonal-covariance mixture fitting on wide rows (csrc/vmp_diagfit.hip): D up to VMP_DIAG_MAX_D = 64, any D; K up to VMP_MAX_K
+ * ------------------------------------------------------------------------------------------------
+ * Gaussian mixture with one precision per component and coordinate.  pi ~ Dir(alpha0); lambda_kd ~ Gamma(shape a0_k, rate b0_kd);
+ * mu_kd | lambda_kd ~ N(m0_kd, (beta0_k lambda_kd)^-1); given z_n = k, x_nd ~ N(mu_kd, 1 / lambda_kd).  The posterior has the same
+ * form: theta = (alpha (K), beta (K), m (K,D), a (K), b (K,D)), the prior (alpha0, beta0, m0, a0, b0) likewise; all fp32.
+ *   raw moments  Nk = sum_n r_nk,  sx_kd = sum_n r_nk x_nd,  sxx_kd = sum_n r_nk x_nd^2,  xbar = sx / Nk,  NS_kd = sxx_kd - sx_kd^2 / Nk
+ *   M-step   alpha_k = alpha0_k + Nk,  beta_k = beta0_k + Nk,  a_k = a0_k + Nk / 2,  m_kd = (beta0_k m0_kd + sx_kd) / beta_k,
+ *            b_kd = b0_kd + 1/2 [ NS_kd + (beta0_k Nk / beta_k) (xbar_kd - m0_kd)^2 ];  Nk = 0: the component's prior, no NaN
+ *   E-step   lbar_kd = a_k / b_kd,  c_k = psi(alpha_k) - psi(sum alpha) + 1/2 sum_d (psi(a_k) - log b_kd) - D / (2 beta_k),
+ *            log rho_nk = c_k - 1/2 sum_d lbar_kd (x_nd - m_kd)^2,   r_nk = softmax_k log rho_nk
+ *   bound    = data - kl_pi - sum_kd kl_ng_kd,   data = sum_n logsumexp_k log rho_nk - 1/2 N D log 2 pi,   kl_pi as in "Variational
+ *            lower bound",  kl_ng_kd = 1/2 log(beta / beta0) - 1/2 + 1/2 beta0 / beta + 1/2 beta0 lbar_kd (m_kd - m0_kd)^2
+ *            + (a - a0) psi(a) - lgamma(a) + lgamma(a0) + a0 (log b_kd - log b0_kd) + a (b0_kd - b_kd) / b_kd
+ * Both steps are exact coordinate ascent: the bound of the state after an iteration (theta from the M-step, r from the E-step at
+ * that theta) never falls from one iteration to the next.
+ * Layouts: pack (K, vmp_mixture_diag_pack_words(D) = 2 D + 1) fp32 = [ m (D) | lbar (D) | c ];  stats (K, 1 + 2 D) fp64 =
+ * [ Nk | sx (D) | sxx (D) ].
+ *
+ * vmp_mixture_diag_pack: the pack from theta, one block per component, fp64 inside, rounded once.  A component with a non-positive
+ *   (or NaN) b_kd, a_k or beta_k gets a NaN row.
+ * vmp_mixture_diag_pass: one streaming pass over x (N,D) fp32, any alignment, under a pack.  Outputs, all optional but at least
+ *   one: r_out (N,K); logr_out (N,K) = log r (needs r_out); stats_out (K, 1 + 2 D) fp64; bound_out (1) fp64 = data.  The moments are
+ *   those of the responsibilities the pass itself computes; r_out == NULL is legal and is the fast form of an iteration: the pass
+ *   then moves x alone.  r_in (N,K) != NULL replaces the E-part: stats_out are the moments of the caller's responsibilities (how a
+ *   loop is started from r_init); r_out, logr_out and bound_out must then be NULL and the pack's values are not read.
+ *   log rho is formed on x - m, never in the expanded form.  The moments are accumulated in fp32 on x - p with ONE pivot p near the
+ *   data (the mean of up to 64 evenly strided rows, a function of x, N and D alone) in 16-row MFMA groups, added to the wave's own fp64 words every 128
+ *   rows of a wave, and a second launch adds the waves in a fixed order and undoes the shift in fp64.  The rows' log-sum-exp (fp32
+ *   per row) are added in fp64 in a fixed order - the rows of a lane, the lanes of a wave, the waves of a block, the blocks by block
+ *   0 of the second launch.  No atomics, one geometry whichever outputs are requested: stats_out and bound_out are bit-identical
+ *   from run to run and with or without r_out / logr_out.  ws (vmp_mixture_diag_workspace_bytes: the fp64 moments of every wave, one
+ *   fp64 word per block and the pivot; 8-byte aligned) is always needed.
+ * vmp_mixture_diag_finalize: stats + prior -> theta and, each optional, xbar (K,D), S (K,D) = NS / Nk (0 where Nk = 0) and pi (K) =
+ *   exp E log pi.  One thread per (k, d), fp64 inside.
+ * vmp_mixture_diag_bound_terms: out (2 + K) fp64 = [ kl_pi | sum_kd kl_ng_kd | sum_d kl_ng_0d .. sum_d kl_ng_{K-1}d ]; one thread per
+ *   component adds its D terms in d order, one thread adds the components in k order; fp64.
+ * vmp_mixture_diag_iterate: `iterations` x (vmp_mixture_diag_finalize on stats -> vmp_mixture_diag_pack -> vmp_mixture_diag_pass with
+ *   stats_out = stats, bound_out = bound) enqueued back to back, no host work in between; stats holds the moments of the current r
+ *   on entry and of the last r on return.  r and logr, if not NULL, are written by the last pass only.  xbar, S, pi, bound may be NULL.
+ * Errors (decided before any launch): VMP_E_DIM (D outside 1..VMP_DIAG_MAX_D, K outside 1..VMP_MAX_K), VMP_E_BADARG (N < 1; x or pack
+ *   NULL; no output; logr_out without r_out; r_in together with r_out, logr_out or bound_out; ws not 8-byte aligned; a NULL prior,
+ *   posterior or stats of the iteration, the finalize, the pack or the terms; iterations < 0), VMP_E_WS (ws NULL or too small).
+ *   vmp_mixture_diag_workspace_bytes and vmp_mixture_diag_pack_words are 0 outside the compiled range.                          */
+int    vmp_mixture_diag_pack_words(int D);
+size_t vmp_mixture_diag_workspace_bytes(int64_t N, int D, int K);
+int    vmp_mixture_diag_pack(int D, int K, const float* alpha, const float* beta, const float* m, const float* a, const float* b,
+                             float* pack, void* stream);
+int    vmp_mixture_diag_pass(const float* x, int64_t N, int D, int K, const float* pack, const float* r_in, float* r_out,
+                             float* logr_out, double* stats_out, double* bound_out, void* ws, size_t ws_bytes, void* stream);
+int    vmp_mixture_diag_finalize(const double* stats, int D, int K, const float* alpha0, const float* beta0, const float* m0,
+                                 const float* a0, const float* b0, float* alpha, float* beta, float* m, float* a, float* b,
+                                 float* xbar, float* S, float* pi, void* stream);
+int    vmp_mixture_diag_bound_terms(int D, int K, const float* alpha0, const float* beta0, const float* m0, const float* a0,
+                                    const float* b0, const float* alpha, const float* beta, const float* m, const float* a,
+                                    const float* b, double* out, void* stream);
+int    vmp_mixture_diag_iterate(const float* x, int64_t N, int D, int K, const float* alpha0, const float* beta0, const float* m0,
+                                const float* a0, const float* b0, float* r, float* logr, float* alpha, float* beta, float* m,
+                                float* a, float* b, float* xbar, float* S, float* pi, float* pack, double* stats, double* bound,
+                                void* ws, size_t ws_bytes, int iterations, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Mixture initialisation (csrc/vmp_seed.hip): seeded k-means++ centres and the responsibilities of the nearest centre, on the device

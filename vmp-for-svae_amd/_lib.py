@@ -11,6 +11,7 @@ LIB_PATH = os.environ.get('VMP_LIB_PATH') or os.path.join(_HERE, 'lib', 'libvmp_
 
 VMP_GMM, VMP_SMM = 0, 1
 MAX_D, MAX_K = 8, 64
+DIAG_MAX_D = 64               # the diagonal-covariance mixture (csrc/vmp_diagfit.hip)
 
 _lib = None
 
@@ -58,6 +59,14 @@ _SIGNATURES = {
     'vmp_mixture_wfit_workspace_bytes': (_c.c_size_t, [_c.c_int64, _c.c_int, _c.c_int]),
     'vmp_mixture_wfit_pass': (_c.c_int, [_P, _P, _P, _c.c_int64, _c.c_int, _c.c_int, _P, _P, _P, _P, _P, _P, _P, _c.c_size_t, _P]),
     'vmp_mixture_wfit_iterate': (_c.c_int, [_P, _P, _P, _c.c_int64, _c.c_int, _c.c_int] + [_P] * 5 + [_P] * 3 + [_P] * 8
+                                 + [_P, _P, _P, _P, _c.c_size_t, _c.c_int, _P]),
+    'vmp_mixture_diag_pack_words': (_c.c_int, [_c.c_int]),
+    'vmp_mixture_diag_workspace_bytes': (_c.c_size_t, [_c.c_int64, _c.c_int, _c.c_int]),
+    'vmp_mixture_diag_pack': (_c.c_int, [_c.c_int, _c.c_int] + [_P] * 5 + [_P, _P]),
+    'vmp_mixture_diag_pass': (_c.c_int, [_P, _c.c_int64, _c.c_int, _c.c_int, _P, _P, _P, _P, _P, _P, _P, _c.c_size_t, _P]),
+    'vmp_mixture_diag_finalize': (_c.c_int, [_P, _c.c_int, _c.c_int] + [_P] * 5 + [_P] * 8 + [_P]),
+    'vmp_mixture_diag_bound_terms': (_c.c_int, [_c.c_int, _c.c_int] + [_P] * 10 + [_P, _P]),
+    'vmp_mixture_diag_iterate': (_c.c_int, [_P, _c.c_int64, _c.c_int, _c.c_int] + [_P] * 5 + [_P, _P] + [_P] * 8
                                  + [_P, _P, _P, _P, _c.c_size_t, _c.c_int, _P]),
     'vmp_mixture_seed_workspace_bytes': (_c.c_size_t, [_c.c_int64, _c.c_int, _c.c_int]),
     'vmp_mixture_seed_centers': (_c.c_int, [_P, _P, _P, _c.c_int64, _c.c_int, _c.c_int, _c.c_uint64, _P, _P, _P, _P, _c.c_size_t, _P]),

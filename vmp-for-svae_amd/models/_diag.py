@@ -1,0 +1,333 @@
+"""Host side of the diagonal-covariance Gaussian mixture on wide rows (csrc/vmp_diagfit.hip; include/vmp_hip.h "Diagonal-covariance
+mixture fitting on wide rows"): thin wrappers over the vmp_mixture_diag_* C ABI and the loop that drives them.  D up to
+_lib.DIAG_MAX_D = 64, K up to _lib.MAX_K.  theta = (alpha (K), beta (K), m (K,D), a (K), b (K,D)); a prior has the same five."""
+import torch
+
+from .. import _lib as L
+
+NAMES = ('alpha', 'beta', 'm', 'a', 'b')
+_POST = NAMES + ('xbar', 'S', 'pi')          # the outputs of the finalize, in the order of the C ABI
+
+
+def _check_dk(D, K):
+    if not (1 <= D <= L.DIAG_MAX_D):
+        raise L.VmpError('D=%d outside the compiled range 1..%d of the diagonal-covariance mixture' % (D, L.DIAG_MAX_D))
+    if not (1 <= K <= L.MAX_K):
+        raise L.VmpError('K=%d outside the compiled range 1..%d' % (K, L.MAX_K))
+
+
+def _x_dims(x, what):
+    if not torch.is_tensor(x) or x.dim() != 2 or x.shape[0] < 1:
+        raise L.VmpError('%s: x must be (N >= 1, D), got %s' % (what, tuple(x.shape) if torch.is_tensor(x) else type(x)))
+    return x.shape
+
+
+def _shapes(K, D):
+    return ((K,), (K,), (K, D), (K,), (K, D))
+
+
+def _five(ops, K, D, what, suffix=''):
+    """the five tensors of a posterior or a prior: shapes refused BEFORE the library or a device is touched"""
+    if len(ops) != 5:
+        raise L.VmpError('%s: expected (alpha, beta, m, a, b)' % what)
+    for t, n, shp in zip(ops, NAMES, _shapes(K, D)):
+        if not torch.is_tensor(t) or tuple(t.shape) != shp:
+            raise L.VmpError('%s: %s%s has shape %s, expected %s' % (what, n, suffix, tuple(t.shape) if torch.is_tensor(t) else type(t), shp))
+    return ops
+
+
+def _dev5(ops, dev, suffix=''):
+    return [L.dev_f32(t.detach().to(dev, torch.float32), n + suffix) for t, n in zip(ops, NAMES)]
+
+
+def default_diag_prior(x, K):
+    """alpha_0 = 0.05 / K, beta_0 = 0.5, m_0 = the column means of x, a_0 = 1, b_0 = 1 - on x's device"""
+    N, D = _x_dims(x, 'default_diag_prior')
+    f32 = dict(dtype=torch.float32, device=x.device)
+    mean = x.double().mean(0).to(torch.float32)
+    return (torch.full((K,), 0.05 / K, **f32), torch.full((K,), 0.5, **f32), mean[None, :].expand(K, D).contiguous(),
+            torch.ones(K, **f32), torch.ones(K, D, **f32))
+
+
+def diag_pack(alpha, beta, m, a, b):
+    """The E-step pack (K, 2 D + 1) fp32 = [ m | lbar = a / b | c ] of a posterior (vmp_mixture_diag_pack); fp64 inside, rounded
+    once.  A component with a non-positive b, a or beta gets a NaN row.  One K-block launch, no host synchronisation."""
+    if not torch.is_tensor(m) or m.dim() != 2:
+        raise L.VmpError('diag_pack: m must be (K,D)')
+    K, D = m.shape
+    _check_dk(D, K)
+    theta = _dev5(_five((alpha, beta, m, a, b), K, D, 'diag_pack'), m.device)
+    pack = torch.empty(K, L.lib().vmp_mixture_diag_pack_words(D), dtype=torch.float32, device=m.device)
+    L.check(L.lib().vmp_mixture_diag_pack(D, K, *[L.ptr(t) for t in theta], L.ptr(pack), L.stream()), 'vmp_mixture_diag_pack')
+    return pack
+
+
+def _pass_dims(x, pack, what):
+    N, D = _x_dims(x, what)
+    if not torch.is_tensor(pack) or pack.dim() != 2 or pack.shape[1] != 2 * D + 1:
+        raise L.VmpError('%s: no diagonal pack for D=%d (shape %s, expected (K,%d): diag_pack)'
+                         % (what, D, tuple(pack.shape) if torch.is_tensor(pack) else type(pack), 2 * D + 1))
+    K = pack.shape[0]
+    _check_dk(D, K)
+    return N, D, K
+
+
+def mixture_diag_pass(x, pack, r_in=None, want_r=True, want_logr=False, want_stats=True, want_bound=False):
+    """One streaming pass (vmp_mixture_diag_pass) over the rows of x (N,D) under a diagonal pack: (r (N,K), logr (N,K), stats
+    (K, 1 + 2 D) fp64 = [Nk | sx | sxx], bound 0-dim fp64 = the data term of the lower bound); outputs that are not wanted are None.
+    want_r=False is the fast form: the pass then moves x alone, and stats are still the moments of the responsibilities it computes.
+    r_in (N,K): the moments of the caller's responsibilities instead (stats only).  stats and bound are the same bits from run to
+    run and for every set of outputs.  No host synchronisation."""
+    what = 'mixture_diag_pass'
+    N, D, K = _pass_dims(x, pack, what)
+    if not (want_r or want_logr or want_stats or want_bound):
+        raise L.VmpError('%s: no output requested' % what)
+    if want_logr and not want_r:
+        raise L.VmpError('%s: want_logr needs want_r' % what)
+    if r_in is not None:
+        if not torch.is_tensor(r_in) or tuple(r_in.shape) != (N, K):
+            raise L.VmpError('%s: r_in has shape %s, expected %s' % (what, tuple(r_in.shape) if torch.is_tensor(r_in) else type(r_in), (N, K)))
+        if want_r or want_logr or want_bound:
+            raise L.VmpError('%s: r_in gives the moments only (want_r, want_logr and want_bound must be False)' % what)
+    x = L.dev_f32(x, 'x')
+    dev = x.device
+    pack = L.dev_f32(pack, 'pack', (K, 2 * D + 1))
+    if pack.device != dev:
+        raise L.VmpError('pack is on %s, x on %s' % (pack.device, dev))
+    if r_in is not None:
+        r_in = L.dev_f32(r_in, 'r_in', (N, K))
+    f32 = dict(dtype=torch.float32, device=dev)
+    r = torch.empty(N, K, **f32) if want_r else None
+    logr = torch.empty(N, K, **f32) if want_logr else None
+    stats = torch.empty(K, 1 + 2 * D, dtype=torch.float64, device=dev) if want_stats else None
+    bound = torch.empty((), dtype=torch.float64, device=dev) if want_bound else None
+    nb = L.lib().vmp_mixture_diag_workspace_bytes(N, D, K)
+    ws = L.workspace(dev, nb)
+    L.check(L.lib().vmp_mixture_diag_pass(L.ptr(x), N, D, K, L.ptr(pack), L.ptr(r_in), L.ptr(r), L.ptr(logr), L.ptr(stats), L.ptr(bound),
+                                          L.ptr(ws), nb, L.stream()), 'vmp_mixture_diag_pass')
+    return r, logr, stats, bound
+
+
+def _stats_dims(stats, what):
+    if not torch.is_tensor(stats) or stats.dim() != 2 or stats.shape[1] < 3 or stats.shape[1] % 2 != 1:
+        raise L.VmpError('%s: stats must be (K, 1 + 2 D) fp64' % what)
+    K, D = stats.shape[0], (stats.shape[1] - 1) // 2
+    _check_dk(D, K)
+    return K, D
+
+
+def _post_buffers(K, D, dev):
+    f32 = dict(dtype=torch.float32, device=dev)
+    return dict(alpha=torch.empty(K, **f32), beta=torch.empty(K, **f32), m=torch.empty(K, D, **f32), a=torch.empty(K, **f32),
+                b=torch.empty(K, D, **f32), xbar=torch.empty(K, D, **f32), S=torch.empty(K, D, **f32), pi=torch.empty(K, **f32))
+
+
+def diag_finalize(stats, prior):
+    """Posterior dict(alpha, beta, m, a, b, xbar, S, pi) from raw stats (K, 1 + 2 D) fp64 and a prior (vmp_mixture_diag_finalize)."""
+    K, D = _stats_dims(stats, 'diag_finalize')
+    _five(prior, K, D, 'diag_finalize', '_0')
+    if stats.dtype != torch.float64:
+        raise L.VmpError('diag_finalize: stats must be float64 (got %s)' % stats.dtype)
+    if not stats.is_cuda:
+        raise L.VmpError('stats is on %s: the diagonal mixture only runs in HIP kernels on a GPU (no CPU fallback)' % stats.device)
+    dev = stats.device
+    prior = _dev5(prior, dev, '_0')
+    out = _post_buffers(K, D, dev)
+    L.check(L.lib().vmp_mixture_diag_finalize(L.ptr(stats.contiguous()), D, K, *[L.ptr(t) for t in prior],
+                                              *[L.ptr(out[n]) for n in _POST], L.stream()), 'vmp_mixture_diag_finalize')
+    return out
+
+
+def diag_bound_terms(prior, theta):
+    """(2 + K,) fp64 device tensor [ KL(q(pi) || p(pi)) | sum_kd KL(q(mu, lambda)_kd || p) | the K per-component sums ]
+    (vmp_mixture_diag_bound_terms); fp64 inside, the sums in d and k order.  One launch, no host synchronisation."""
+    if len(theta) != 5 or not torch.is_tensor(theta[2]) or theta[2].dim() != 2:
+        raise L.VmpError('diag_bound_terms: theta is (alpha, beta, m (K,D), a, b)')
+    K, D = theta[2].shape
+    _five(theta, K, D, 'diag_bound_terms')
+    _five(prior, K, D, 'diag_bound_terms', '_0')
+    _check_dk(D, K)
+    dev = theta[2].device
+    theta, prior = _dev5(theta, dev), _dev5(prior, dev, '_0')
+    out = torch.empty(2 + K, dtype=torch.float64, device=dev)
+    L.check(L.lib().vmp_mixture_diag_bound_terms(D, K, *[L.ptr(t) for t in prior], *[L.ptr(t) for t in theta], L.ptr(out), L.stream()),
+            'vmp_mixture_diag_bound_terms')
+    return out
+
+
+def diag_lower_bound(x, theta, prior=None):
+    """The variational lower bound of the diagonal posterior theta on the rows of x: a 0-dim fp64 device tensor, data - kl_pi -
+    sum_kd kl_ng_kd, with q(z) at its optimum for theta.  Pack, the bound-only pass, the terms, one subtraction: no host
+    synchronisation."""
+    N, D = _x_dims(x, 'lower_bound_diag')
+    if len(theta) != 5 or not torch.is_tensor(theta[2]) or theta[2].dim() != 2:
+        raise L.VmpError('lower_bound_diag: theta is (alpha, beta, m (K,D), a, b)')
+    K = theta[2].shape[0]
+    _five(theta, K, D, 'lower_bound_diag')
+    _check_dk(D, K)
+    prior = default_diag_prior(x, K) if prior is None else _five(prior, K, D, 'lower_bound_diag', '_0')
+    x = L.dev_f32(x, 'x')
+    terms = diag_bound_terms(prior, theta)
+    data = mixture_diag_pass(x, diag_pack(*theta), want_r=False, want_stats=False, want_bound=True)[3]
+    return data - (terms[0] + terms[1])
+
+
+def nearest_center_r(x, centers, smooth=0.0):
+    """r (N,K) fp32 of the nearest of centers (K,D) by squared distance (torch.cdist + argmin, ties to the lowest k) with the
+    smoothing rule of _mix.seed_assign: r_nk = (1 - smooth) [k = z_n] + smooth / K.  Plumbing in torch, not a kernel."""
+    smooth = float(smooth)
+    if not 0.0 <= smooth < 1.0:
+        raise L.VmpError('smooth must be in [0, 1) (got %r)' % smooth)
+    N, D = _x_dims(x, 'from_centers')
+    if not torch.is_tensor(centers) or centers.dim() != 2 or centers.shape[1] != D:
+        raise L.VmpError('from_centers: centers has shape %s, expected (K,%d)' % (tuple(centers.shape) if torch.is_tensor(centers) else type(centers), D))
+    if centers.device != x.device:
+        raise L.VmpError('from_centers: centers is on %s, x on %s' % (centers.device, x.device))
+    K = centers.shape[0]
+    _check_dk(D, K)
+    d2 = torch.cdist(x.double(), centers.double())
+    # argmin does not promise the first of equal minima: the lowest k among them, explicitly
+    k_idx = torch.arange(K, device=x.device)[None, :].expand(N, K)
+    z = torch.where(d2 == d2.min(1, keepdim=True).values, k_idx, torch.full_like(k_idx, K)).min(1).values
+    r = torch.full((N, K), smooth / K, dtype=torch.float32, device=x.device)
+    r[torch.arange(N, device=x.device), z] = (1.0 - smooth) + smooth / K
+    return r
+
+
+class DiagLoop(object):
+    """The VMP iteration of the diagonal-covariance Gaussian mixture on x (N, D <= 64), started from responsibilities r_init (N,K):
+    M-step from the moments of the current r (vmp_mixture_diag_finalize), the E-step pack, and one streaming pass that computes the
+    new r, its moments and the data term of the lower bound.  run(n) enqueues n iterations in one call and leaves r in the kernel
+    (the pass then moves x alone); step() also writes r.  Both updates are exact coordinate ascent: lower_bound() never falls.
+    Out of scope, refused: masks, weights, the Student-t flavour, accurate=True, score / impute / sample."""
+
+    def __init__(self, x, r_init, prior=None, miss=None, weights=None, flavour=L.VMP_GMM, accurate=False):
+        if miss is not None:
+            raise L.VmpError('DiagLoop: no masks - the diagonal mixture fits complete rows only')
+        if weights is not None:
+            raise L.VmpError('DiagLoop: no weights - the diagonal mixture has no weighted pass')
+        if flavour != L.VMP_GMM:
+            raise L.VmpError('DiagLoop: Gaussian mixture only (no Student-t flavour)')
+        if accurate:
+            raise L.VmpError('DiagLoop: no accurate=True mode')
+        N, D = _x_dims(x, 'DiagLoop')
+        if not torch.is_tensor(r_init) or r_init.dim() != 2 or r_init.shape[0] != N:
+            raise L.VmpError('DiagLoop: r_init has shape %s, expected (%d,K)' % (tuple(r_init.shape) if torch.is_tensor(r_init) else type(r_init), N))
+        K = r_init.shape[1]
+        _check_dk(D, K)
+        if prior is not None:
+            _five(prior, K, D, 'DiagLoop', '_0')
+        self.x = L.dev_f32(x, 'x')
+        dev = self.x.device
+        r_init = L.dev_f32(r_init, 'r_init', (N, K))
+        self.N, self.D, self.K = N, D, K
+        self.prior = _dev5(default_diag_prior(self.x, K) if prior is None else prior, dev, '_0')
+        self.post = _post_buffers(K, D, dev)
+        self.pack = torch.zeros(K, 2 * D + 1, dtype=torch.float32, device=dev)
+        self._data = torch.zeros((), dtype=torch.float64, device=dev)
+        self._r = torch.empty(N, K, dtype=torch.float32, device=dev)
+        self._logr = None
+        self._r_ok = self._logr_ok = False
+        self.iterations = 0
+        # the moments of r_init: the r_in form of the pass (the pack's values are not read)
+        self._stats = mixture_diag_pass(self.x, self.pack, r_in=r_init, want_r=False)[2]
+
+    @classmethod
+    def from_centers(cls, x, centers, smooth=0.0, prior=None):
+        """start from the responsibilities of the nearest of `centers` (K,D) (nearest_center_r)"""
+        return cls(x, nearest_center_r(x, centers, smooth), prior=prior)
+
+    def _iterate(self, iterations, want_r, want_logr):
+        if want_logr and self._logr is None:
+            self._logr = torch.empty_like(self._r)
+        nb = L.lib().vmp_mixture_diag_workspace_bytes(self.N, self.D, self.K)
+        ws = L.workspace(self.x.device, nb)
+        p = self.post
+        L.check(L.lib().vmp_mixture_diag_iterate(
+            L.ptr(self.x), self.N, self.D, self.K, *[L.ptr(t) for t in self.prior], L.ptr(self._r if want_r else None),
+            L.ptr(self._logr if want_logr else None), *[L.ptr(p[n]) for n in _POST], L.ptr(self.pack), L.ptr(self._stats),
+            L.ptr(self._data), L.ptr(ws), nb, iterations, L.stream()), 'vmp_mixture_diag_iterate')
+        self.iterations += iterations
+        self._r_ok, self._logr_ok = want_r, want_logr
+
+    def step(self, want_logr=False):
+        """one iteration; returns the new r (N,K)"""
+        self._iterate(1, True, want_logr)
+        return self._r
+
+    def run(self, iterations):
+        """`iterations` iterations enqueued by one call, r left in the kernel; r / logr are produced by one pass on demand"""
+        iterations = int(iterations)
+        if iterations < 0:
+            raise L.VmpError('iterations must not be negative')
+        if iterations:
+            self._iterate(iterations, False, False)
+
+    def _need_iteration(self, what):
+        if self.iterations == 0:
+            raise L.VmpError('%s: no posterior yet - run at least one iteration' % what)
+
+    def _refresh(self):
+        """r and log r of the current posterior by one pass under the current pack (the moments it would give are self._stats)"""
+        self._need_iteration('r')
+        if self._logr is None:
+            self._logr = torch.empty_like(self._r)
+        nb = L.lib().vmp_mixture_diag_workspace_bytes(self.N, self.D, self.K)
+        ws = L.workspace(self.x.device, nb)
+        L.check(L.lib().vmp_mixture_diag_pass(L.ptr(self.x), self.N, self.D, self.K, L.ptr(self.pack), None, L.ptr(self._r), L.ptr(self._logr),
+                                              None, None, L.ptr(ws), nb, L.stream()), 'vmp_mixture_diag_pass')
+        self._r_ok = self._logr_ok = True
+
+    @property
+    def r(self):
+        if not self._r_ok:
+            self._refresh()
+        return self._r
+
+    @property
+    def logr(self):
+        if not self._logr_ok:
+            self._refresh()
+        return self._logr
+
+    @property
+    def stats(self):
+        """raw moments (K, 1 + 2 D) fp64 of the current r"""
+        return self._stats.clone()
+
+    def theta(self):
+        p = self.post
+        return p['alpha'], p['beta'], p['m'], p['a'], p['b']
+
+    def aux(self):
+        p = self.post
+        return p['xbar'], p['S'], p['pi']
+
+    def lower_bound(self):
+        """The variational lower bound (nats) of the state the last iteration left.  The pass wrote its data term: one K-sized launch
+        and one scalar read-back."""
+        self._need_iteration('lower_bound')
+        terms = diag_bound_terms(self.prior, self.theta())
+        return (self._data - (terms[0] + terms[1])).item()
+
+    def run_until_bound(self, tol, check_every=5, max_iterations=1000):
+        """run(check_every) and lower_bound() in turn until the bound improves by less than tol * max(1, |bound|) over the previous
+        check, or `max_iterations` iterations of this call are done (the rule of VMPLoop.run_until_bound).  Returns
+        [(iterations, bound), ...]."""
+        check_every = int(check_every)
+        if check_every < 1:
+            raise L.VmpError('check_every must be >= 1')
+        hist, done = [], 0
+        while done < max_iterations:
+            n = min(check_every, max_iterations - done)
+            self.run(n)
+            done += n
+            hist.append((self.iterations, self.lower_bound()))
+            if len(hist) > 1 and hist[-1][1] - hist[-2][1] < tol * max(1.0, abs(hist[-1][1])):
+                break
+        return hist
+
+    def _refuse(self, *args, **kw):
+        raise L.VmpError('DiagLoop: score, impute and sample are not built for the diagonal mixture')
+
+    score = impute = sample = impute_draws = run_until = _refuse

@@ -1043,3 +1043,8 @@ class VMPLoop(object):
     def aux(self):
         p = self.post
         return p['xbar'], p['S'], p['pi']
+
+
+# the diagonal-covariance mixture on wide rows (D up to 64) lives in models/_diag.py; its entry points are reachable from here as well
+from ._diag import (DiagLoop, default_diag_prior, diag_bound_terms, diag_finalize, diag_lower_bound, diag_pack,  # noqa: E402,F401
+                    mixture_diag_pass, nearest_center_r)

@@ -271,3 +271,37 @@ def inference(x, K, seed, name='inference', r_init=None, init='random'):
         return loop.step(want_logr=True)
 
     return (step, _Handle(lambda: loop.logr), _Handle(loop.theta), _Handle(loop.aux))
+
+
+def inference_diag(x, K, seed, iterations=1, r_init=None, prior=None, init='random'):
+    """inference() for the diagonal-covariance Gaussian mixture on wide rows: x (N, D <= 64), one precision per component and
+    coordinate (include/vmp_hip.h "Diagonal-covariance mixture fitting on wide rows"; csrc/vmp_diagfit.hip).  Returns (step, log_r_nk,
+    theta, (x_k, S_k, pi)) as inference() does: `step()` runs `iterations` VMP iterations enqueued by one call and returns the new
+    r_nk; theta() = (alpha_k, beta_k, m_k, a_k, b_k); S_k (K,D) holds the per-coordinate variances.  init='random': a host-side
+    Dirichlet(1) draw with `seed`; an explicit r_init wins.  prior = (alpha_0, beta_0, m_0, a_0, b_0), default
+    _mix.default_diag_prior.  init='kmeans++' is not available here (the seeding kernels stop at D = 8): seed with
+    _mix.DiagLoop.from_centers."""
+    if init != 'random':
+        raise L.VmpError("inference_diag: init=%r - only 'random' (or an explicit r_init; DiagLoop.from_centers for centres)" % (init,))
+    iterations = int(iterations)
+    if iterations < 1:
+        raise L.VmpError('inference_diag: iterations must be >= 1')
+    if not torch.is_tensor(x) or x.dim() != 2:
+        raise L.VmpError('inference_diag: x must be (N,D)')
+    if r_init is None:
+        r_init = _dirichlet_init(x.shape[0], K, seed, x.device)
+    loop = _mix.DiagLoop(x, r_init, prior=prior)
+
+    def step():
+        if iterations > 1:
+            loop.run(iterations - 1)
+        return loop.step(want_logr=True)
+
+    return (step, _Handle(lambda: loop.logr), _Handle(loop.theta), _Handle(loop.aux))
+
+
+def lower_bound_diag(x, alpha_k, beta_k, m_k, a_k, b_k, prior=None):
+    """The variational lower bound (nats) of the diagonal posterior that inference_diag()'s theta handle returns, on the rows of x:
+    two K-sized launches and the bound-only form of the streaming pass.  Returns a 0-dim fp64 DEVICE tensor (deterministic; no host
+    synchronisation)."""
+    return _mix.diag_lower_bound(x, (alpha_k, beta_k, m_k, a_k, b_k), prior=prior)

@@ -456,6 +456,50 @@ int    vmp_mixture_diag_iterate(const float* x, int64_t N, int D, int K, const f
                                 void* ws, size_t ws_bytes, int iterations, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Diagonal-covariance mixture: scoring and filling wide rows (csrc/vmp_diagscore.hip): D up to VMP_DIAG_MAX_D, K up to VMP_MAX_K
+ * ------------------------------------------------------------------------------------------------
+ * Log posterior predictive density, predictive responsibilities and conditional-mean fills of rows the posterior theta = (alpha,
+ * beta, m, a, b) of the section above was not fitted on, complete or partly observed.  q(lambda_kd) = Gamma(a_k, rate b_kd) and
+ * q(mu_kd | lambda_kd) = N(m_kd, (beta_k lambda_kd)^-1) are independent over d, so given z = k the predictive of a row is a product
+ * of one-dimensional Student-t densities with 2 a_k degrees of freedom and location m_kd; marginalising a missing coordinate leaves
+ * its factor out, and its conditional mean is the responsibility-weighted location.
+ *   g_kd  = beta_k / (2 b_kd (1 + beta_k)),   G_k = lgamma(a_k + 1/2) - lgamma(a_k) - 1/2 log pi
+ *   log St_kd(x) = G_k + 1/2 log g_kd - (a_k + 1/2) log1p(g_kd (x - m_kd)^2)
+ *   log w_k = log(alpha_k / sum_j alpha_j)            (the weights of vmp_mix_score_pack_niw)
+ *   l_nk  = log w_k + sum_{d in o(n)} log St_kd(x_nd)     o(n) = the observed coordinates of row n; without a mask all D
+ *   logp_n = logsumexp_k l_nk,   resp_nk = exp(l_nk - logp_n)
+ *   xhat_nd = sum_k resp_nk m_kd  for d missing       (the conditional mean when a_k > 1/2, the conditional location otherwise;
+ *                                                      returned either way, as vmp_mixture_impute does)
+ * a_k grows like N_k / 2 while g_kd (x - m)^2 shrinks like 1 / N_k: the kernel's log1p is accurate relative to its argument (four
+ * cells are merged as (1 + T)(1 + t) - 1 = T + t + T t, then log1p(T) = log u + (T - (u - 1)) / u with u = fl(1 + T)), and x - m is
+ * formed directly, never expanded.
+ * Layout: pack (K, vmp_mixture_diag_score_pack_words(D) = 3 D + 3) fp32 = [ m (D) | g (D) | h (D) | log w | a + 1/2 | c ] with
+ * h_kd = G_k + 1/2 log g_kd and c_k = log w_k + sum_d h_kd.
+ *
+ * vmp_mixture_diag_score_pack: the pack from theta, one block per component, fp64 inside, rounded once.  A component with a
+ *   non-positive (or NaN) alpha_k, beta_k, a_k or b_kd gets a NaN row.
+ * vmp_mixture_diag_score: one streaming pass over x (N,D) fp32, any alignment, with an optional mask (N,D) uint8, nonzero = missing;
+ *   mask == NULL is a kernel of its own that reads and selects nothing.  Outputs, all optional but at least one: logp_out (N);
+ *   resp_out (N,K); x_out (N,D) - needs a mask; observed entries copied bit for bit, missing ones filled with xhat; x_out == x fills
+ *   in place; sum_out (1) fp64 = sum_n logp_n, the rows added in fp64 in a fixed order - the rows of a lane, the lanes of a wave, the
+ *   waves of a block, then the blocks' partials (in ws) by a one-wave second launch.  No atomics; the geometry depends on N alone:
+ *   every output has the same bits from run to run and whichever other outputs are requested.
+ *   What a missing slot of x holds (NaN and +-Inf included) never enters arithmetic.  A row with nothing observed has l_nk = log w_k.
+ *   log w_k = -inf (a hand-made pack) gives resp_k = 0; if every log w is -inf: logp = -inf, resp = 0, fills 0, no NaN.  A NaN pack
+ *   row makes every row's logp NaN.
+ * vmp_mixture_diag_score_workspace_bytes = 8 * blocks,  blocks = min(2048, max(1, ceil(N / 1024))): one fp64 partial per block; a
+ *   multiple of 8, non-decreasing in N, 0 outside the compiled range.  ws is needed only with sum_out.
+ * Errors (decided before any launch): VMP_E_DIM (D outside 1..VMP_DIAG_MAX_D, K outside 1..VMP_MAX_K), VMP_E_BADARG (N < 1; x or pack
+ *   NULL; no output; x_out without mask; ws not 8-byte aligned when sum_out is given; a NULL operand of the pack builder), VMP_E_WS
+ *   (ws NULL or too small when sum_out is given).  vmp_mixture_diag_score_pack_words is 0 outside 1..VMP_DIAG_MAX_D.             */
+int    vmp_mixture_diag_score_pack_words(int D);
+int    vmp_mixture_diag_score_pack(int D, int K, const float* alpha, const float* beta, const float* m, const float* a,
+                                   const float* b, float* pack, void* stream);
+size_t vmp_mixture_diag_score_workspace_bytes(int64_t N, int D, int K);
+int    vmp_mixture_diag_score(const float* x, const uint8_t* mask, int64_t N, int D, int K, const float* pack, float* logp_out,
+                              float* resp_out, float* x_out, double* sum_out, void* ws, size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Mixture initialisation (csrc/vmp_seed.hip): seeded k-means++ centres and the responsibilities of the nearest centre, on the device
  * ------------------------------------------------------------------------------------------------
  * D^2-seeding (Arthur & Vassilvitskii 2007) of K centres from the rows of x (N,D) fp32, any alignment, as a pure function of (seed,

@@ -172,6 +172,119 @@ def diag_lower_bound(x, theta, prior=None):
     return data - (terms[0] + terms[1])
 
 
+def diag_score_pack(alpha, beta, m, a, b):
+    """The score pack (K, 3 D + 3) fp32 = [ m | g | h | log w | a + 1/2 | c ] of a posterior (vmp_mixture_diag_score_pack; include/vmp_hip.h
+    "Diagonal-covariance mixture: scoring and filling wide rows"); fp64 inside, rounded once.  A component with a non-positive alpha,
+    beta, a or b gets a NaN row.  One K-block launch, no host synchronisation."""
+    if not torch.is_tensor(m) or m.dim() != 2:
+        raise L.VmpError('diag_score_pack: m must be (K,D)')
+    K, D = m.shape
+    _check_dk(D, K)
+    theta = _dev5(_five((alpha, beta, m, a, b), K, D, 'diag_score_pack'), m.device)
+    pack = torch.empty(K, L.lib().vmp_mixture_diag_score_pack_words(D), dtype=torch.float32, device=m.device)
+    L.check(L.lib().vmp_mixture_diag_score_pack(D, K, *[L.ptr(t) for t in theta], L.ptr(pack), L.stream()), 'vmp_mixture_diag_score_pack')
+    return pack
+
+
+def _score_dims(x, pack, miss, what):
+    """(N, D, K) of a scoring pass, refused BEFORE the library or a device is touched"""
+    N, D = _x_dims(x, what)
+    if x.dtype != torch.float32:
+        raise L.VmpError('%s: x must be float32 (got %s)' % (what, x.dtype))
+    if not torch.is_tensor(pack) or pack.dim() != 2 or pack.shape[1] != 3 * D + 3:
+        raise L.VmpError('%s: no diagonal score pack for D=%d (shape %s, expected (K,%d): diag_score_pack)'
+                         % (what, D, tuple(pack.shape) if torch.is_tensor(pack) else type(pack), 3 * D + 3))
+    K = pack.shape[0]
+    _check_dk(D, K)
+    if miss is not None and (not torch.is_tensor(miss) or tuple(miss.shape) != (N, D)):
+        raise L.VmpError('%s: the missing-data mask must be (%d,%d), got %s' % (what, N, D, tuple(miss.shape) if torch.is_tensor(miss) else type(miss)))
+    return N, D, K
+
+
+def _mask_u8(miss):
+    """(N,D) uint8 view / copy of a missing-data mask of any dtype (nonzero = missing)"""
+    if miss.dtype == torch.bool:
+        return miss.contiguous().view(torch.uint8)
+    if miss.dtype == torch.uint8:
+        return miss.contiguous()
+    return (miss != 0).view(torch.uint8)
+
+
+def mixture_diag_score(x, pack, miss=None, want_logp=True, want_resp=False, want_fill=False, want_sum=False, inplace=False):
+    """One streaming pass (vmp_mixture_diag_score) over the rows of x (N,D) under a diagonal score pack, with an optional mask miss (N,D;
+    nonzero / True = missing): (logp (N,), resp (N,K), x_filled (N,D), total 0-dim fp64 = sum_n logp_n); outputs that are not wanted
+    are None.  logp is the log posterior predictive density of the observed entries; x_filled (needs miss) is x with its missing
+    entries replaced by sum_k resp_k m_k, observed entries copied bit for bit; inplace=True writes into x itself (a contiguous fp32
+    GPU tensor) and returns it.  What a missing slot of x holds is never read into arithmetic.  Every output has the same bits from
+    run to run and for every set of outputs.  No host synchronisation."""
+    what = 'mixture_diag_score'
+    N, D, K = _score_dims(x, pack, miss, what)
+    if not (want_logp or want_resp or want_fill or want_sum):
+        raise L.VmpError('%s: no output requested' % what)
+    if want_fill and miss is None:
+        raise L.VmpError('%s: want_fill needs miss (without a mask there is nothing to fill)' % what)
+    if inplace and not want_fill:
+        raise L.VmpError('%s: inplace=True needs want_fill' % what)
+    xin = x
+    x = L.dev_f32(x, 'x')
+    dev = x.device
+    pack = L.dev_f32(pack, 'pack', (K, 3 * D + 3))
+    if pack.device != dev:
+        raise L.VmpError('pack is on %s, x on %s' % (pack.device, dev))
+    mask = None
+    if miss is not None:
+        if miss.device != dev:
+            raise L.VmpError('the missing-data mask is on %s, x on %s' % (miss.device, dev))
+        mask = _mask_u8(miss)
+    x_out = None
+    if want_fill:
+        if inplace and x.data_ptr() != xin.data_ptr():
+            raise L.VmpError('inplace=True needs a contiguous x')
+        x_out = x if inplace else torch.empty_like(x)
+    logp = torch.empty(N, dtype=torch.float32, device=dev) if want_logp else None
+    resp = torch.empty(N, K, dtype=torch.float32, device=dev) if want_resp else None
+    total, ws, nb = None, None, 0
+    if want_sum:
+        total = torch.empty((), dtype=torch.float64, device=dev)
+        nb = L.lib().vmp_mixture_diag_score_workspace_bytes(N, D, K)
+        ws = L.workspace(dev, nb)
+    L.check(L.lib().vmp_mixture_diag_score(L.ptr(x), L.ptr(mask), N, D, K, L.ptr(pack), L.ptr(logp), L.ptr(resp), L.ptr(x_out), L.ptr(total),
+                                           L.ptr(ws), nb, L.stream()), 'vmp_mixture_diag_score')
+    return logp, resp, (xin if (want_fill and inplace) else x_out), total
+
+
+def _theta_dims(x, theta, what):
+    N, D = _x_dims(x, what)
+    if len(theta) != 5 or not torch.is_tensor(theta[2]) or theta[2].dim() != 2:
+        raise L.VmpError('%s: theta is (alpha, beta, m (K,D), a, b)' % what)
+    K = theta[2].shape[0]
+    if theta[2].shape[1] != D:
+        raise L.VmpError('%s: x has %d columns, m %d' % (what, D, theta[2].shape[1]))
+    _check_dk(D, K)
+    _five(theta, K, D, what)
+    return N, D, K
+
+
+def diag_predictive_logprob(x, theta, miss=None):
+    """logp (N,) of the rows of x under the posterior predictive of the diagonal posterior theta (gmm.predictive_logprob_diag)"""
+    N, D, K = _theta_dims(x, theta, 'predictive_logprob_diag')
+    if miss is not None and (not torch.is_tensor(miss) or tuple(miss.shape) != (N, D)):
+        raise L.VmpError('predictive_logprob_diag: the missing-data mask must be (%d,%d)' % (N, D))
+    L.dev_f32(x, 'x')
+    return mixture_diag_score(x, diag_score_pack(*theta), miss=miss)[0]
+
+
+def diag_predictive_impute(x, miss, theta):
+    """(x_filled (N,D), logp (N,)) of the partly observed rows of x under the diagonal posterior theta (gmm.predictive_impute_diag)"""
+    N, D, K = _theta_dims(x, theta, 'predictive_impute_diag')
+    if not torch.is_tensor(miss) or tuple(miss.shape) != (N, D):
+        raise L.VmpError('predictive_impute_diag: the missing-data mask must be (%d,%d), got %s'
+                         % (N, D, tuple(miss.shape) if torch.is_tensor(miss) else type(miss)))
+    L.dev_f32(x, 'x')
+    logp, _, x_out, _ = mixture_diag_score(x, diag_score_pack(*theta), miss=miss, want_fill=True)
+    return x_out, logp
+
+
 def nearest_center_r(x, centers, smooth=0.0):
     """r (N,K) fp32 of the nearest of centers (K,D) by squared distance (torch.cdist + argmin, ties to the lowest k) with the
     smoothing rule of _mix.seed_assign: r_nk = (1 - smooth) [k = z_n] + smooth / K.  Plumbing in torch, not a kernel."""
@@ -199,7 +312,11 @@ class DiagLoop(object):
     M-step from the moments of the current r (vmp_mixture_diag_finalize), the E-step pack, and one streaming pass that computes the
     new r, its moments and the data term of the lower bound.  run(n) enqueues n iterations in one call and leaves r in the kernel
     (the pass then moves x alone); step() also writes r.  Both updates are exact coordinate ascent: lower_bound() never falls.
-    Out of scope, refused: masks, weights, the Student-t flavour, accurate=True, score / impute / sample."""
+    Rows the loop was not fitted on: heldout() (mean log predictive density), heldout_logprob() (per row, with the predictive
+    responsibilities on request), fill() (conditional means of missing entries) and run_until() (stop on a validation set) - one
+    streaming pass each (csrc/vmp_diagscore.hip).  Out of scope, refused: fitting on masked or weighted rows, the Student-t flavour,
+    accurate=True; score / impute keep refusing and name heldout / heldout_logprob / fill, sampling (sample / impute_draws) is not
+    built."""
 
     def __init__(self, x, r_init, prior=None, miss=None, weights=None, flavour=L.VMP_GMM, accurate=False):
         if miss is not None:
@@ -327,7 +444,64 @@ class DiagLoop(object):
                 break
         return hist
 
-    def _refuse(self, *args, **kw):
-        raise L.VmpError('DiagLoop: score, impute and sample are not built for the diagonal mixture')
+    def predictive_pack(self):
+        """score pack of the CURRENT posterior (diag_score_pack on theta())"""
+        self._need_iteration('predictive_pack')
+        return diag_score_pack(*self.theta())
 
-    score = impute = sample = impute_draws = run_until = _refuse
+    def _new_rows(self, x_new, miss, what, need_miss=False):
+        self._need_iteration(what)
+        if not torch.is_tensor(x_new) or x_new.dim() != 2 or x_new.shape[1] != self.D or x_new.shape[0] < 1:
+            raise L.VmpError('%s: x has shape %s, expected (M >= 1, %d)' % (what, tuple(x_new.shape) if torch.is_tensor(x_new) else type(x_new), self.D))
+        if need_miss and miss is None:
+            raise L.VmpError('%s: needs the missing-data mask' % what)
+        if miss is not None and (not torch.is_tensor(miss) or tuple(miss.shape) != tuple(x_new.shape)):
+            raise L.VmpError('%s: the missing-data mask must be %s' % (what, tuple(x_new.shape)))
+
+    def heldout(self, x_val, miss=None):
+        """Mean log posterior predictive density (nats per row) of the rows of x_val (M,D) - of their observed entries with a mask miss
+        (M,D), nonzero = missing - under the current posterior.  One streaming launch with its one-wave sum, one scalar read-back."""
+        self._new_rows(x_val, miss, 'heldout')
+        total = mixture_diag_score(x_val, self.predictive_pack(), miss=miss, want_logp=False, want_sum=True)[3]
+        return total.item() / x_val.shape[0]
+
+    def heldout_logprob(self, x_new, miss=None, want_resp=False):
+        """logp (M,) of the rows of x_new under the current posterior, and the predictive responsibilities (M,K) with want_resp - what
+        gmm.predictive_logprob_diag gives on theta().  One streaming launch, no host synchronisation."""
+        self._new_rows(x_new, miss, 'heldout_logprob')
+        logp, resp, _, _ = mixture_diag_score(x_new, self.predictive_pack(), miss=miss, want_resp=want_resp)
+        return (logp, resp) if want_resp else logp
+
+    def fill(self, x_new, miss):
+        """(x_filled (M,D), logp (M,)) of the partly observed rows x_new with mask miss (M,D; nonzero = missing) under the current
+        posterior - gmm.predictive_impute_diag on theta().  One streaming launch, no host synchronisation."""
+        self._new_rows(x_new, miss, 'fill', need_miss=True)
+        logp, _, x_out, _ = mixture_diag_score(x_new, self.predictive_pack(), miss=miss, want_fill=True)
+        return x_out, logp
+
+    def run_until(self, x_val, tol, check_every=5, max_iterations=1000):
+        """run(check_every) and heldout(x_val) in turn until the score improves by less than `tol` (absolute, nats per row) over the
+        previous check, or `max_iterations` iterations of this call are done (the rule of VMPLoop.run_until).  Returns
+        [(iterations, score), ...] with `iterations` the loop's running count."""
+        check_every = int(check_every)
+        if check_every < 1:
+            raise L.VmpError('check_every must be >= 1')
+        hist, done = [], 0
+        while done < max_iterations:
+            n = min(check_every, max_iterations - done)
+            self.run(n)
+            done += n
+            hist.append((self.iterations, self.heldout(x_val)))
+            if len(hist) > 1 and hist[-1][1] - hist[-2][1] < tol:
+                break
+        return hist
+
+    def _refuse_score(self, *args, **kw):
+        raise L.VmpError('DiagLoop: score and impute are not built for the diagonal mixture under these names - use heldout / '
+                         'heldout_logprob / fill')
+
+    def _refuse_sample(self, *args, **kw):
+        raise L.VmpError('DiagLoop: sampling (sample, impute_draws) is not built for the diagonal mixture')
+
+    score = impute = _refuse_score
+    sample = impute_draws = _refuse_sample

@@ -305,3 +305,19 @@ def lower_bound_diag(x, alpha_k, beta_k, m_k, a_k, b_k, prior=None):
     two K-sized launches and the bound-only form of the streaming pass.  Returns a 0-dim fp64 DEVICE tensor (deterministic; no host
     synchronisation)."""
     return _mix.diag_lower_bound(x, (alpha_k, beta_k, m_k, a_k, b_k), prior=prior)
+
+
+def predictive_logprob_diag(x, alpha_k, beta_k, m_k, a_k, b_k, miss=None):
+    """Log posterior predictive density of the diagonal-covariance mixture at the rows of x (N, D <= 64), from the posterior
+    (alpha_k, beta_k, m_k, a_k, b_k) that inference_diag()'s theta handle returns: given the component a product of one-dimensional
+    Student-t densities with 2 a_k degrees of freedom (include/vmp_hip.h "Diagonal-covariance mixture: scoring and filling wide
+    rows").  miss (N,D), nonzero = missing: the density of the observed entries.  One K-sized launch and one streaming HIP pass
+    (csrc/vmp_diagscore.hip).  Returns logp (N,); no host synchronisation."""
+    return _mix.diag_predictive_logprob(x, (alpha_k, beta_k, m_k, a_k, b_k), miss=miss)
+
+
+def predictive_impute_diag(x, miss, alpha_k, beta_k, m_k, a_k, b_k):
+    """Fill the missing entries of the rows of x (N, D <= 64) - miss (N,D), nonzero = missing - from the posterior predictive of the
+    diagonal-covariance mixture: each gets sum_k r_nk m_kd with r_nk the responsibilities that follow from the density of the observed
+    entries.  Returns (x_filled (N,D), logp (N,)); what the missing slots of x hold is never read into arithmetic."""
+    return _mix.diag_predictive_impute(x, miss, (alpha_k, beta_k, m_k, a_k, b_k))

@@ -97,46 +97,14 @@ __device__ __forceinline__ v2f row16_sum2(v2f v) {
     return v2f{a, b};
 }
 
-// Four independent reductions interleaved (both halves of a 16-row sub-tile of pass_xdl_body): every butterfly step is four DPP
-// instructions back to back, so the DPP read of a register comes three instructions after the step that wrote it - more than the
-// two wait states "VALU writes a VGPR -> v_*_dpp reads that VGPR" asks for - and no step needs an s_nop.  Only the first step
-// reads registers written outside the statement, possibly by the VALU instruction just ahead of it: it keeps its two wait states
-// (s_nop 1).  Same rotations in the same order as the two-wide form: every maximum and sum is bit-identical.
-#define VMP_DPP4(OP, CTRL)                                                   \
-    "v_" OP "_f32_dpp %0, %0, %0 " CTRL " row_mask:0xf bank_mask:0xf\n\t"  \
-    "v_" OP "_f32_dpp %1, %1, %1 " CTRL " row_mask:0xf bank_mask:0xf\n\t"  \
-    "v_" OP "_f32_dpp %2, %2, %2 " CTRL " row_mask:0xf bank_mask:0xf\n\t"  \
-    "v_" OP "_f32_dpp %3, %3, %3 " CTRL " row_mask:0xf bank_mask:0xf\n\t"
-#define VMP_DPP4_FIRST(OP, CTRL)                                             \
-    "v_" OP "_f32_dpp %0, %4, %4 " CTRL " row_mask:0xf bank_mask:0xf\n\t"  \
-    "v_" OP "_f32_dpp %1, %5, %5 " CTRL " row_mask:0xf bank_mask:0xf\n\t"  \
-    "v_" OP "_f32_dpp %2, %6, %6 " CTRL " row_mask:0xf bank_mask:0xf\n\t"  \
-    "v_" OP "_f32_dpp %3, %7, %7 " CTRL " row_mask:0xf bank_mask:0xf\n\t"
-[[maybe_unused]] __device__ __forceinline__ void row16_max4(v2f v0, v2f v1, v2f& o0, v2f& o1) {
-    float a, b, c, d;
-    asm("s_nop 1\n\t" VMP_DPP4_FIRST("max", "row_ror:8") VMP_DPP4("max", "row_ror:4") VMP_DPP4("max", "row_ror:2")
-        VMP_DPP4("max", "row_ror:1")
-        : "=&v"(a), "=&v"(b), "=&v"(c), "=&v"(d) : "v"(v0.x), "v"(v0.y), "v"(v1.x), "v"(v1.y));
-    o0 = v2f{a, b};
-    o1 = v2f{c, d};
-}
-[[maybe_unused]] __device__ __forceinline__ void row16_sum4(v2f v0, v2f v1, v2f& o0, v2f& o1) {
-    float a, b, c, d;
-    asm("s_nop 1\n\t" VMP_DPP4_FIRST("add", "row_ror:8") VMP_DPP4("add", "row_ror:4") VMP_DPP4("add", "row_ror:2")
-        VMP_DPP4("add", "row_ror:1")
-        : "=&v"(a), "=&v"(b), "=&v"(c), "=&v"(d) : "v"(v0.x), "v"(v0.y), "v"(v1.x), "v"(v1.y));
-    o0 = v2f{a, b};
-    o1 = v2f{c, d};
-}
-
-// Reduce-scatter form of the four reductions (whole tiles only): registers v = 0..3 in, ONE register out, in which the four lanes
+// Reduce-scatter form of the four reductions of a 16-row sub-tile (whole tiles only): registers v = 0..3 in, ONE register out, in which the four lanes
 // of bank v (lanes 4 v .. 4 v + 3 of every DPP row) hold the reduction of register v over the row's 16 lanes.  A DPP lane i of
 // row_ror:n reads lane (i - n) mod 16 of its row; a bank-masked instruction writes the enabled banks and leaves the others.
 //   step 1 (pairs L, L + 8):   a0 = banks {0,1} <- v0, banks {2,3} <- v2;   a1 = banks {0,1} <- v1, banks {2,3} <- v3
 //   step 2 (pairs L, L + 4):   b  = banks 0, 2 <- a0 with its neighbour bank above (row_ror:12 = -4),
 //                                   banks 1, 3 <- a1 with its neighbour bank below (row_ror:4)          => bank v holds register v
 //   steps 3, 4 (pairs L ^ 2, L ^ 1 inside the bank): quad_perm [2,3,0,1], then [1,0,3,2]
-// 8 DPP instructions instead of 16.  Every addition pairs the two operands the butterfly of row16_sum4 pairs at that step
+// 8 DPP instructions instead of 16.  Every addition pairs the two operands the butterfly of row16_sum2 pairs at that step
 // ((v_L + v_L+8), + the same of L +- 4, + of L +- 2, + of L +- 1; fp32 addition commutes), so the sum has the butterfly's bits
 // (tests/mix_softmax_net_model.py holds the lane maps to that).  Wait states as above: a DPP read two instructions or less after
 // the VALU write of the same VGPR gets its s_nop; TAIL pads the end for a DPP consumer the compiler places right behind the
@@ -170,14 +138,6 @@ template <int V>
 __device__ __forceinline__ float row16_bcast_bank(float s) {
     return __uint_as_float(__builtin_amdgcn_update_dpp(0u, __float_as_uint(s), 0x150 + 4 * V, 0xf, 0xf, true));
 }
-
-// Exploration switch of the streaming loop of pass_xdl_body (tools/build_variant.sh ... -DVMP_PASS_PIPE=n), for the attribution in
-// profiles/NOTES_mix_pass_pipeline.md and NOTES_mix_softmax_net.md: 1 = straight-line full tiles, the staging still waits for the
-// tile's stores; 2 = + counted wait (the staging waits for the row loads only); 3 = + four-wide DPP reductions; 4 = the reductions as
-// a reduce-scatter (row16_rs4_*) and one reciprocal for the four rows of a lane.
-#ifndef VMP_PASS_PIPE
-#define VMP_PASS_PIPE 4
-#endif
 
 constexpr int MOM_TERMS = 3;
 #ifndef VMP_MOM_FLUSH
@@ -757,7 +717,10 @@ template <int D> constexpr int xdl_wave_floats() { return Geo<D>::XROWS * LS + T
 // products, 2^-17 relative per product, unbiased) from there on: every moment is then a sum over >= 1e4 rows per component whose
 // per-term rounding errors average out (relative error of a moment ~ 2^-17 / sqrt(rows of the component) < 1e-7), while the splits
 // and MFMAs they save are a fifth of the kernel's issue time (round 5).  The E-part (one value per row, nothing averages) keeps 3.
-template <int D, int FLAV, bool STATS, int MT = 3>
+// GEN: whole tiles of K == 16 as straight-line code, then the general form (any K <= 16, any row range).  !GEN: K == 16 and every
+// wave has no rows or at least 64 (launch_xdl decides) - whole tiles as straight-line code, and a wave's last rows as one more
+// whole tile (or half of one) that overlaps rows already done: no general form in the instance.
+template <int D, int FLAV, bool STATS, int MT = 3, bool GEN = true>
 __device__ __forceinline__ void pass_xdl_body(const PassArgs& a) {
     using G = Geo<D>;
     constexpr int FT = G::FT, KT = 1;
@@ -765,7 +728,7 @@ __device__ __forceinline__ void pass_xdl_body(const PassArgs& a) {
     constexpr int DP = (D + 1) / 2;                          // coordinate pairs
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
-    const int K = a.K;
+    const int K = GEN ? a.K : 16;
     PASS_TS(0);
     float* xl = smem + wave * xdl_wave_floats<D>();          // [XROWS][LS] fp32 (x - pivot), ones, zeros: moment features
     unsigned* ai = reinterpret_cast<unsigned*>(xl + G::XROWS * LS);   // [64][AIS] bf16 terms of x - pivot: E-part A operands
@@ -957,9 +920,10 @@ __device__ __forceinline__ void pass_xdl_body(const PassArgs& a) {
 #endif
     PASS_TS(1);
     // The streaming loop runs in two parts over the same per-tile pieces (stage / body / flush below): whole 64-row tiles with
-    // K == 16 as straight-line code (no trip counts, no validity tests, store addresses = one base + compile-time offsets), then
-    // today's general form for what is left: the ragged last tile, or every tile when K < 16.  The pieces run in the same order on
-    // the same values in both parts, so no result depends on which part a tile went through.
+    // K == 16 as straight-line code (no trip counts, no validity tests, store addresses = one base + compile-time offsets), the rows
+    // behind them as one more such tile that overlaps the last (!GEN), or through the general form (GEN: also every tile when K < 16
+    // and a wave of fewer than 64 rows).  The pieces run in the same order on the same values in both parts, and a row's r / u depend on
+    // nothing but the row, so they do not depend on which part, or which position of a tile, the row went through.
     long long row0 = lo, tbase = 0;                          // tbase: this lane's element of r/u for (row0 + kk, component i16)
     int trows = TR;                                          // rows of the tile: read by the not-FULL bodies only (general form)
     // ---- stage a tile: lane = tile row.  fp32 image for the moment features, bf16 term image for the y GEMM
@@ -985,7 +949,10 @@ __device__ __forceinline__ void pass_xdl_body(const PassArgs& a) {
             *reinterpret_cast<u32x4*>(ai + lane * AIS + 20) = u32x4{th[0], th[1], th[0], th[1]};
             *reinterpret_cast<u32x4*>(ai + lane * AIS + 24) = u32x4{tm[0], tm[1], th[0], th[1]};
             *reinterpret_cast<u32x4*>(ai + lane * AIS + 28) = u32x4{tl[0], tl[1], tm[0], tm[1]};
-            const long long n2 = row0 + TR + lane;
+            // rows of the next tile.  After a wave's last whole tile that is the overlap tile [hi - 64, hi) (below): never past hi
+            long long nb = row0 + TR;
+            if (!GEN && WHOLE && nb < hi && nb > hi - TR) nb = hi - TR;
+            const long long n2 = nb + lane;
 #pragma unroll
             for (int j = 0; j < D; ++j) xr[j] = 0.f;
             if (n2 < hi) load_row<D>(a.x + n2 * D, xr, vec);
@@ -996,10 +963,15 @@ __device__ __forceinline__ void pass_xdl_body(const PassArgs& a) {
     // One instance of the whole body (two sub-tiles + the moment MFMAs) per path: the operand registers of the MFMAs
     // are written and consumed inside the same instance, so no register tuple has to be re-assembled where the two
     // paths would merge (the first version paid 64 v_mov per body for that).  n0: first tile row of the body, an int or
-    // (straight-line tiles) an integral_constant.
-    auto body = [&](auto full_c, auto n0_v) __attribute__((always_inline)) {
+    // (straight-line tiles) an integral_constant.  OVL (straight-line tiles only): the tile overlaps rows this wave has already
+    // been through - register v of a sub-tile is such a row where n16 + 4 v < othr (othr: per lane, set ahead of the overlap
+    // tile).  Their E-part runs again (the same r / u bits go to the same addresses); their moment weight is 0.
+    int othr = 0;
+    auto body = [&](auto full_c, auto n0_v, auto ovl_c) __attribute__((always_inline)) {
         constexpr bool FULL = decltype(full_c)::value;
         constexpr bool LINE = !std::is_same<decltype(n0_v), int>::value;   // part of a straight-line tile
+        constexpr bool OVL = decltype(ovl_c)::value;
+        static_assert(!OVL || LINE, "only a straight-line tile overlaps");
         const int n0 = n0_v;
         unsigned As[3][4], Bs[FT][3][4];                 // [term h/m/l][k-slot pair: (sub-tile jj, v pair)]
         auto subtile = [&](auto jj_c) __attribute__((always_inline)) {
@@ -1049,7 +1021,7 @@ __device__ __forceinline__ void pass_xdl_body(const PassArgs& a) {
                 lg[h] = pk_const_minus_scaled(qh, pch);                 // log2 rho
                 if constexpr (SMM) uu[h] = v2f{pua * __builtin_amdgcn_rcpf(qh.x + pub), pua * __builtin_amdgcn_rcpf(qh.y + pub)};
             }
-            if constexpr (LINE && VMP_PASS_PIPE >= 4) {
+            if constexpr (LINE) {
                 // whole tile (FULL): maximum and sum as reduce-scatters, each row's value read back from its bank; one reciprocal
                 // serves the lane's four rows.  Same maxima, same addition tree, same rcp operand: the bits of the branch below.
                 static_assert(FULL, "straight-line tiles are whole tiles");
@@ -1063,18 +1035,11 @@ __device__ __forceinline__ void pass_xdl_body(const PassArgs& a) {
                 for (int h = 0; h < 2; ++h) w[h] = SMM ? rr[h] * uu[h] : rr[h];
             } else {
                 v2f mx[2], ssum[2];
-                if constexpr (LINE && VMP_PASS_PIPE >= 3) {
-                    row16_max4(lg[0], lg[1], mx[0], mx[1]);
 #pragma unroll
-                    for (int h = 0; h < 2; ++h) lg[h] = v2f{__builtin_amdgcn_exp2f(lg[h].x - mx[h].x), __builtin_amdgcn_exp2f(lg[h].y - mx[h].y)};
-                    row16_sum4(lg[0], lg[1], ssum[0], ssum[1]);
-                } else {
-#pragma unroll
-                    for (int h = 0; h < 2; ++h) {
-                        mx[h] = row16_max2(lg[h]);
-                        lg[h] = v2f{__builtin_amdgcn_exp2f(lg[h].x - mx[h].x), __builtin_amdgcn_exp2f(lg[h].y - mx[h].y)};
-                        ssum[h] = row16_sum2(lg[h]);
-                    }
+                for (int h = 0; h < 2; ++h) {
+                    mx[h] = row16_max2(lg[h]);
+                    lg[h] = v2f{__builtin_amdgcn_exp2f(lg[h].x - mx[h].x), __builtin_amdgcn_exp2f(lg[h].y - mx[h].y)};
+                    ssum[h] = row16_sum2(lg[h]);
                 }
 #pragma unroll
                 for (int h = 0; h < 2; ++h) {
@@ -1114,6 +1079,15 @@ __device__ __forceinline__ void pass_xdl_body(const PassArgs& a) {
                 }
             }
             if constexpr (STATS) {
+                if constexpr (OVL) {
+                    // rows already counted: one compare-and-select per register on the moment weight (and on the SMM's N_k term)
+#pragma unroll
+                    for (int h = 0; h < 2; ++h) {
+                        const bool ka = n16 + 8 * h >= othr, kb = n16 + 8 * h + 4 >= othr;
+                        w[h] = v2f{ka ? w[h].x : 0.f, kb ? w[h].y : 0.f};
+                        if constexpr (SMM) rr[h] = v2f{ka ? rr[h].x : 0.f, kb ? rr[h].y : 0.f};     // stored above: only nsum reads it from here on
+                    }
+                }
                 unsigned t3[3];
 #pragma unroll
                 for (int h = 0; h < 2; ++h) {
@@ -1188,28 +1162,51 @@ __device__ __forceinline__ void pass_xdl_body(const PassArgs& a) {
     // inner trip count, so the wait ahead of the next staging is a counted one: it covers the row loads and leaves the stores in
     // flight (gfx950 counts loads and stores in the one vmcnt).  The compiler emits that count itself (vmcnt(16), with u vmcnt(32)):
     // nothing is waited for by hand.  The logr_out stores sit in a wave-uniform branch, where its count stays the conservative one.
-    if (K == 16) {
+    using T_ = integral_constant<bool, true>;
+    using F_ = integral_constant<bool, false>;
+    if constexpr (!GEN) {
+        // every wave of this instance has no rows or at least 64 (launch_xdl)
         for (; row0 + TR <= hi; row0 += TR) {
-#if VMP_PASS_PIPE == 1
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // attribution build: the wait of the rolled loop
-#endif
-            stage(integral_constant<bool, true>{});
-            body(integral_constant<bool, true>{}, integral_constant<int, 0>{});
-            body(integral_constant<bool, true>{}, integral_constant<int, 32>{});
+            stage(T_{});
+            body(T_{}, integral_constant<int, 0>{}, F_{});
+            body(T_{}, integral_constant<int, 32>{}, F_{});
             flush();
         }
-    }
-    // ---- general form: the ragged last tile, every tile of K < 16
-    for (; row0 < hi; row0 += TR) {
-        trows = (hi - row0 < TR) ? (int)(hi - row0) : TR;
-        stage(integral_constant<bool, false>{});
-#pragma unroll 1
-        for (int n0 = 0; n0 < trows; n0 += 32) {
-            const bool full = (K == 16) && (n0 + 32 <= trows);
-            if (full) body(integral_constant<bool, true>{}, n0);
-            else body(integral_constant<bool, false>{}, n0);
+        PASS_TS(6);
+        // ---- the rows left (fewer than 64): the whole tile [hi - 64, hi), of which the first `done` rows have been through the
+        // loop above - no ragged tile.  More than 32 rows left: both halves; else the second half alone covers them.  The tile's
+        // rows were requested by the last staging above; flush() sees row0 + 64 == hi, the wave's last tile.
+        if (row0 < hi && hi - lo >= TR) {
+            const int done = TR - (int)(hi - row0);
+            row0 = hi - TR;
+            othr = done - kk;
+            stage(T_{});
+            if (done < 32) body(T_{}, integral_constant<int, 0>{}, T_{});
+            body(T_{}, integral_constant<int, 32>{}, T_{});
+            flush();
         }
-        flush();
+    } else {
+        if (K == 16) {
+            for (; row0 + TR <= hi; row0 += TR) {
+                stage(T_{});
+                body(T_{}, integral_constant<int, 0>{}, F_{});
+                body(T_{}, integral_constant<int, 32>{}, F_{});
+                flush();
+            }
+        }
+        PASS_TS(6);
+        // ---- general form: the ragged last tile, every tile of K < 16
+        for (; row0 < hi; row0 += TR) {
+            trows = (hi - row0 < TR) ? (int)(hi - row0) : TR;
+            stage(F_{});
+#pragma unroll 1
+            for (int n0 = 0; n0 < trows; n0 += 32) {
+                const bool full = (K == 16) && (n0 + 32 <= trows);
+                if (full) body(T_{}, n0, F_{});
+                else body(F_{}, n0, F_{});
+            }
+            flush();
+        }
     }
 
     PASS_TS(2);
@@ -1234,7 +1231,12 @@ __device__ __forceinline__ void pass_xdl_body(const PassArgs& a) {
 
 template <int D, int FLAV, bool STATS, int MT = 3>
 __global__ __launch_bounds__(MAX_NW1 * WAVE) void pass_xdl_kernel(PassArgs a) {
-    pass_xdl_body<D, FLAV, STATS, MT>(a);
+    pass_xdl_body<D, FLAV, STATS, MT, true>(a);
+}
+// K == 16, no wave of 1..63 rows: whole tiles and the overlap tail alone (a kernel of its own name: the two are told apart in profiles)
+template <int D, int FLAV, bool STATS, int MT = 3>
+__global__ __launch_bounds__(MAX_NW1 * WAVE) void pass_xdl_overlap_kernel(PassArgs a) {
+    pass_xdl_body<D, FLAV, STATS, MT, false>(a);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -1817,13 +1819,32 @@ int launch_tiled(const PassArgs& a, const PassPlan& p, hipStream_t s) {
     return check_launch("pass_kernel");
 }
 
+template <int D, int FL, bool S, int MT, bool GEN>
+int launch_xdl_form(const PassArgs& a, const PassPlan& p, hipStream_t s) {
+    void (*const kern)(PassArgs) = GEN ? pass_xdl_kernel<D, FL, S, MT> : pass_xdl_overlap_kernel<D, FL, S, MT>;
+    if (p.lds > 64 * 1024) {
+        if (const int rc = set_dyn_lds(reinterpret_cast<const void*>(kern), p.lds, "pass_xdl_kernel")) return rc;
+    }
+    hipLaunchKernelGGL(kern, dim3(p.blocks), dim3(p.nw * WAVE), p.lds, s, a);
+    return check_launch("pass_xdl_kernel");
+}
+
+// Rows of the last wave of the grid that has any: the one row range N cuts short (the ranges as pass_xdl_body derives them).
+long long last_wave_rows(const PassPlan& p, long long N) {
+    if (p.rpw_b == p.rpw) return N - (N - 1) / p.rpw * p.rpw;
+    const long long hw = p.nw / 2, per = hw * (p.rpw + p.rpw_b);
+    long long rem = N - (N - 1) / per * per;                   // rows of the last block, 1 .. per
+    if (rem <= hw * p.rpw) return rem - (rem - 1) / p.rpw * p.rpw;
+    rem -= hw * p.rpw;
+    return rem - (rem - 1) / p.rpw_b * p.rpw_b;
+}
+
+// K == 16 and no wave with fewer than 64 rows: the instance of whole tiles and the overlap tail.  Everything else - K < 16, or a
+// last wave of fewer than 64 rows, which has no tile to overlap - runs the general instance.
 template <int D, int FL, bool S, int MT>
 int launch_xdl(const PassArgs& a, const PassPlan& p, hipStream_t s) {
-    if (p.lds > 64 * 1024) {
-        if (const int rc = set_dyn_lds(reinterpret_cast<const void*>(pass_xdl_kernel<D, FL, S, MT>), p.lds, "pass_xdl_kernel")) return rc;
-    }
-    hipLaunchKernelGGL((pass_xdl_kernel<D, FL, S, MT>), dim3(p.blocks), dim3(p.nw * WAVE), p.lds, s, a);
-    return check_launch("pass_xdl_kernel");
+    const bool line = a.K == 16 && last_wave_rows(p, a.N) >= TR;
+    return line ? launch_xdl_form<D, FL, S, MT, false>(a, p, s) : launch_xdl_form<D, FL, S, MT, true>(a, p, s);
 }
 
 template <int D, int KT, int FL>

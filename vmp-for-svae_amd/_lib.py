@@ -228,6 +228,33 @@ def dev_f32(t, name, shape=None):
     return t.contiguous()
 
 
+def mask_u8(miss):
+    """(N,D) uint8 view / copy of a missing-data mask of any dtype (nonzero = missing), as every masked entry point normalises it"""
+    if miss.dtype == torch.bool:
+        return miss.contiguous().view(torch.uint8)
+    if miss.dtype == torch.uint8:
+        return miss.contiguous()
+    return (miss != 0).view(torch.uint8)
+
+
+def check_until(loop, measure, stalled, check_every, max_iterations):
+    """The stop loop of every run_until* method: loop.run(check_every) and measure() in turn until stalled(value, previous value)
+    holds at a check, or `max_iterations` iterations of this call are done (the last run is then a short one).  Returns
+    [(loop.iterations, value), ...], one entry per check."""
+    check_every = int(check_every)
+    if check_every < 1:
+        raise VmpError('check_every must be >= 1')
+    hist, done = [], 0
+    while done < max_iterations:
+        n = min(check_every, max_iterations - done)
+        loop.run(n)
+        done += n
+        hist.append((loop.iterations, measure()))
+        if len(hist) > 1 and stalled(hist[-1][1], hist[-2][1]):
+            break
+    return hist
+
+
 def ptr(t):
     return None if t is None else ctypes.c_void_p(t.data_ptr())
 

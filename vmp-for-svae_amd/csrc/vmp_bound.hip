@@ -295,13 +295,7 @@ int bound_pass_check(const char* who, const float* x, int64_t N, int D, int K, c
     if (rc) return rc;
     if (N <= 0) { set_error("%s: N must be positive (got %lld)", who, (long long)N); return VMP_E_BADARG; }
     if (!x || !pack || !data_out) { set_error("%s: null pointer (%s)", who, !x ? "x" : !pack ? "fit_pack" : "data_out"); return VMP_E_BADARG; }
-    const size_t need = vmp_mixture_bound_workspace_bytes(N, D, K);
-    if (!ws || ws_bytes < need) {
-        set_error("%s: workspace too small (%zu bytes, need %zu)", who, ws ? ws_bytes : (size_t)0, need);
-        return VMP_E_WS;
-    }
-    if (reinterpret_cast<uintptr_t>(ws) & 7) { set_error("%s: workspace not 8-byte aligned", who); return VMP_E_BADARG; }
-    return 0;
+    return workspace_check(who, ws, ws_bytes, vmp_mixture_bound_workspace_bytes(N, D, K));
 }
 
 }  // namespace

@@ -7,7 +7,8 @@
 // The pack is [ m (D) | lbar (D) | c ] per component, fp32.
 //
 // The pass kernel: 4 waves per block, wave g owns the rows [g rpw, (g+1) rpw) (rpw a multiple of 64) and walks them in tiles of 64
-// rows.  A tile of x is copied to the wave's own LDS with coalesced dword loads (any alignment of x).  Then two lane maps:
+// rows.  A tile of x is copied to the wave's own LDS with coalesced dword loads (any alignment of x).  What this kernel shares with
+// the scoring pass (vmp_diagscore.hip) - tile movement, launch and dispatch - is in vmp_diag_stream.h.  Then two lane maps:
 //   E-part   lane = row.  The row's D values sit in registers; component k's m, lbar and c are wave-uniform and come through scalar
 //            loads (the pack is read through the constant address space); log rho is formed on x - m, never in the expanded form.
 //            log rho, then r, go to the wave's LDS tile rs (64, K); r_out is written from there with coalesced stores.
@@ -21,32 +22,22 @@
 // fp64.  The rows' log-sum-exp are added in fp64 in a fixed order: a lane's rows, the lanes of a wave (a fixed butterfly), the waves
 // of a block, the blocks (by block 0 of the reducing launch).  No atomics; the geometry depends on (N, D, K) only: stats and data are
 // bit-identical from run to run and for every set of optional outputs.
-#include "vmp_mix_stream.h"
+#include "vmp_diag_stream.h"
 
 using namespace vmp;
 
 namespace {
 
-constexpr int DG_NW = 4;                      // waves per block
-constexpr int DG_TILE = 64;                   // rows of a tile: one per lane in the E-part
 constexpr int DG_FLUSH_TILES = 2;             // tiles between two fp32 -> fp64 flushes: 128 rows of a wave
 constexpr int DG_ROWS_PER_BLOCK = 2048;       // below that a block is not worth its launch slot
 constexpr int DG_RED_GROUPS = 16;             // wave groups of the reduction block
 constexpr int DG_PIVOT_ROWS = 64;
 
-typedef const __attribute__((address_space(4))) float cfloat;
-
 // the slab of a wave is K (1 + 2 D) fp64 words: at most 512 blocks while that stays within 16 KB, 256 beyond
 inline int diag_max_blocks(int D, int K) { return K * (1 + 2 * D) <= 2048 ? 512 : 256; }
 inline int diag_blocks(int64_t N, int D, int K) { return stream_blocks(N, DG_ROWS_PER_BLOCK, diag_max_blocks(D, K)); }
-inline size_t diag_slab_bytes(int64_t N, int D, int K) { return (size_t)diag_blocks(N, D, K) * DG_NW * K * (1 + 2 * D) * sizeof(double); }
-inline size_t diag_lds_bytes(int D, int K) { return (size_t)(64 + DG_NW * DG_TILE * ((D | 1) + (K | 1))) * sizeof(float); }
-
-inline int diag_dims(const char* who, int D, int K) {
-    if (D < 1 || D > VMP_DIAG_MAX_D) { set_error("%s: D=%d outside compiled range 1..%d", who, D, VMP_DIAG_MAX_D); return VMP_E_DIM; }
-    if (K < 1 || K > VMP_MAX_K) { set_error("%s: K=%d outside compiled range 1..%d", who, K, VMP_MAX_K); return VMP_E_DIM; }
-    return 0;
-}
+inline size_t diag_slab_bytes(int64_t N, int D, int K) { return (size_t)diag_blocks(N, D, K) * DIAG_NW * K * (1 + 2 * D) * sizeof(double); }
+inline size_t diag_lds_bytes(int D, int K) { return (size_t)(64 + DIAG_NW * DIAG_TILE * ((D | 1) + (K | 1))) * sizeof(float); }
 
 struct DiagArgs {
     const float* x;
@@ -61,29 +52,18 @@ struct DiagArgs {
     int K;
 };
 
-// rows [0, rows) x `width` contiguous words of src -> the LDS tile dst with row stride `stride`; the rows past `rows` become zeros
-__device__ __forceinline__ void diag_stage(const float* __restrict__ src, float* dst, int rows, int width, int stride, int lane) {
-    const int total = rows * width;
-    int row = lane / width, col = lane % width;
-    for (int i = lane; i < DG_TILE * width; i += WAVE) {
-        dst[row * stride + col] = i < total ? src[i] : 0.f;
-        col += WAVE;
-        while (col >= width) { col -= width; ++row; }
-    }
-}
-
 template <int D, int KTMAX>
-__global__ __launch_bounds__(DG_NW * WAVE) void diag_pass_kernel(DiagArgs a, const float* __restrict__ pack) {
+__global__ __launch_bounds__(DIAG_NW * WAVE) void diag_pass_kernel(DiagArgs a, const float* __restrict__ pack) {
     extern __shared__ float dg_lds[];
-    __shared__ double wsum[DG_NW];
+    __shared__ double wsum[DIAG_NW];
     constexpr int XS = D | 1, FT = (D + 15) / 16, PW = 2 * D + 1, SW = 1 + 2 * D;
     const int K = a.K, RS = K | 1, KT = (K + 15) / 16;
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int i16 = lane & 15, j4 = lane >> 4;
     float* pv = dg_lds;
-    float* xs = dg_lds + 64 + wave * DG_TILE * (XS + RS);
-    float* rs = xs + DG_TILE * XS;
+    float* xs = dg_lds + 64 + wave * DIAG_TILE * (XS + RS);
+    float* rs = xs + DIAG_TILE * XS;
 
     // the pivot: column means of up to 64 evenly strided rows, added in row order
     if (threadIdx.x < D) {
@@ -99,7 +79,7 @@ __global__ __launch_bounds__(DG_NW * WAVE) void diag_pass_kernel(DiagArgs a, con
 #pragma unroll
     for (int ft = 0; ft < FT; ++ft) pvr[ft] = 16 * ft + i16 < D ? pv[16 * ft + i16] : 0.f;
 
-    const long long g = (long long)blockIdx.x * DG_NW + wave;
+    const long long g = (long long)blockIdx.x * DIAG_NW + wave;
     const long long r0 = g * a.rpw;
     const long long r1 = r0 + a.rpw < a.N ? r0 + a.rpw : a.N;
     double* slab = a.slab + g * K * SW;
@@ -119,11 +99,11 @@ __global__ __launch_bounds__(DG_NW * WAVE) void diag_pass_kernel(DiagArgs a, con
         for (int i = lane; i < K * SW; i += WAVE) slab[i] = 0.0;
 
     int tile = 0;
-    for (long long t0 = r0; t0 < r1; t0 += DG_TILE, ++tile) {
-        const int rows = r1 - t0 < DG_TILE ? (int)(r1 - t0) : DG_TILE;
-        diag_stage(a.x + t0 * D, xs, rows, D, XS, lane);
+    for (long long t0 = r0; t0 < r1; t0 += DIAG_TILE, ++tile) {
+        const int rows = r1 - t0 < DIAG_TILE ? (int)(r1 - t0) : DIAG_TILE;
+        tile_stage(a.x + t0 * D, xs, rows * D, D, XS, lane);
         if (a.r_in) {
-            diag_stage(a.r_in + t0 * K, rs, rows, K, RS, lane);
+            tile_stage(a.r_in + t0 * K, rs, rows * K, K, RS, lane);
         } else {
             __builtin_amdgcn_wave_barrier();
             float x[D];
@@ -159,22 +139,13 @@ __global__ __launch_bounds__(DG_NW * WAVE) void diag_pass_kernel(DiagArgs a, con
             }
         }
         __builtin_amdgcn_wave_barrier();
-        if (a.r) {                                                           // the tile of r is contiguous in r_out
-            float* __restrict__ dst = a.r + t0 * K;
-            const int total = rows * K;
-            int row = lane / K, col = lane % K;
-            for (int i = lane; i < total; i += WAVE) {
-                dst[i] = rs[row * RS + col];
-                col += WAVE;
-                while (col >= K) { col -= K; ++row; }
-            }
-        }
+        if (a.r) tile_store(a.r + t0 * K, rs, rows * K, K, RS, lane);        // the tile of r is contiguous in r_out
         // M-part: four rows per step, lane = (i16, j4): A = r[row j4][component 16 kt + i16], B = y[row j4][column 16 ft + i16]
         // The MFMA chain of a (kt, ft) tile runs over the 4 steps of a 16-row group from zero; the group's sums are then added to the
         // accumulators on the VALU (round to nearest).  A chain over all 32 steps between two flushes rounds at the size of the running
         // sum at every step; this way only 8 additions per flush interval do.
 #pragma unroll 1
-        for (int sg = 0; sg < DG_TILE / 16; ++sg) {
+        for (int sg = 0; sg < DIAG_TILE / 16; ++sg) {
             float av[4][KTMAX];
 #pragma unroll
             for (int st = 0; st < 4; ++st) {
@@ -210,7 +181,7 @@ __global__ __launch_bounds__(DG_NW * WAVE) void diag_pass_kernel(DiagArgs a, con
             }
         }
         __builtin_amdgcn_wave_barrier();
-        if (tile % DG_FLUSH_TILES == DG_FLUSH_TILES - 1 || t0 + DG_TILE >= r1) {
+        if (tile % DG_FLUSH_TILES == DG_FLUSH_TILES - 1 || t0 + DIAG_TILE >= r1) {
             // accumulator word v of tile (kt, ft) in lane (i16, j4): component 16 kt + 4 j4 + v, column 16 ft + i16
             const bool first = tile < DG_FLUSH_TILES;
 #pragma unroll
@@ -246,7 +217,7 @@ __global__ __launch_bounds__(DG_NW * WAVE) void diag_pass_kernel(DiagArgs a, con
     if (threadIdx.x == 0) {
         double s = wsum[0];
 #pragma unroll
-        for (int j = 1; j < DG_NW; ++j) s += wsum[j];
+        for (int j = 1; j < DIAG_NW; ++j) s += wsum[j];
         a.partials[blockIdx.x] = s;
     }
 }
@@ -432,35 +403,18 @@ __global__ __launch_bounds__(WAVE) void diag_terms_kernel(DiagTermsArgs a) {
     }
 }
 
-template <int D>
-int launch_diag(const DiagArgs& a, const float* pack, int blocks, size_t lds, hipStream_t s) {
-    const dim3 grid(blocks), block(DG_NW * WAVE);
-    if (a.K <= 16) {
-        if (lds > 48 * 1024)
-            if (const int rc = set_dyn_lds(reinterpret_cast<const void*>(diag_pass_kernel<D, 1>), lds, "diag_pass_kernel")) return rc;
-        hipLaunchKernelGGL((diag_pass_kernel<D, 1>), grid, block, lds, s, a, pack);
-    } else {
-        if (lds > 48 * 1024)
-            if (const int rc = set_dyn_lds(reinterpret_cast<const void*>(diag_pass_kernel<D, 4>), lds, "diag_pass_kernel")) return rc;
-        hipLaunchKernelGGL((diag_pass_kernel<D, 4>), grid, block, lds, s, a, pack);
-    }
-    return check_launch("diag_pass_kernel");
-}
-
-#define DG_CASE(n) case n: return launch_diag<n>(a, pack, blocks, lds, s);
-#define DG_CASE8(b) DG_CASE(b + 1) DG_CASE(b + 2) DG_CASE(b + 3) DG_CASE(b + 4) DG_CASE(b + 5) DG_CASE(b + 6) DG_CASE(b + 7) DG_CASE(b + 8)
 int launch_diag_dim(int D, const DiagArgs& a, const float* pack, int blocks, size_t lds, hipStream_t s) {
-    switch (D) {
-        DG_CASE8(0) DG_CASE8(8) DG_CASE8(16) DG_CASE8(24) DG_CASE8(32) DG_CASE8(40) DG_CASE8(48) DG_CASE8(56)
-        default: break;
-    }
-    return -1;
+    return dispatch_dim<VMP_DIAG_MAX_D>(D, [&](auto d) {
+        constexpr int DD = decltype(d)::value;
+        return a.K <= 16 ? launch_dyn_lds(diag_pass_kernel<DD, 1>, "diag_pass_kernel", blocks, DIAG_NW * WAVE, lds, s, a, pack)
+                         : launch_dyn_lds(diag_pass_kernel<DD, 4>, "diag_pass_kernel", blocks, DIAG_NW * WAVE, lds, s, a, pack);
+    });
 }
 
 // every refusal of the pass, decided on the host
 int diag_pass_check(const char* who, const float* x, int64_t N, int D, int K, const float* pack, const float* r_in, const float* r_out,
                     const float* logr_out, const double* stats_out, const double* bound_out, const void* ws, size_t ws_bytes) {
-    int rc = diag_dims(who, D, K);
+    int rc = stream_dims(who, D, K, VMP_DIAG_MAX_D);
     if (rc) return rc;
     if (N <= 0) { set_error("%s: N must be positive (got %lld)", who, (long long)N); return VMP_E_BADARG; }
     if (!x || !pack) { set_error("%s: null pointer (%s)", who, !x ? "x" : "pack"); return VMP_E_BADARG; }
@@ -473,13 +427,7 @@ int diag_pass_check(const char* who, const float* x, int64_t N, int D, int K, co
         set_error("%s: r_in gives the moments of the caller's responsibilities only (r_out, logr_out and bound_out must be NULL)", who);
         return VMP_E_BADARG;
     }
-    const size_t need = vmp_mixture_diag_workspace_bytes(N, D, K);
-    if (!ws || ws_bytes < need) {
-        set_error("%s: workspace too small (%zu bytes, need %zu)", who, ws ? ws_bytes : (size_t)0, need);
-        return VMP_E_WS;
-    }
-    if (reinterpret_cast<uintptr_t>(ws) & 7) { set_error("%s: workspace not 8-byte aligned", who); return VMP_E_BADARG; }
-    return 0;
+    return workspace_check(who, ws, ws_bytes, vmp_mixture_diag_workspace_bytes(N, D, K));
 }
 
 }  // namespace
@@ -496,7 +444,7 @@ size_t vmp_mixture_diag_workspace_bytes(int64_t N, int D, int K) {
 
 int vmp_mixture_diag_pack(int D, int K, const float* alpha, const float* beta, const float* m, const float* a, const float* b, float* pack,
                           void* stream) {
-    int rc = diag_dims("vmp_mixture_diag_pack", D, K);
+    int rc = stream_dims("vmp_mixture_diag_pack", D, K, VMP_DIAG_MAX_D);
     if (rc) return rc;
     if (!alpha || !beta || !m || !a || !b || !pack) { set_error("vmp_mixture_diag_pack: null pointer (posterior or pack)"); return VMP_E_BADARG; }
     DiagPackArgs pa{alpha, beta, m, a, b, pack, D, K};
@@ -510,14 +458,14 @@ int vmp_mixture_diag_pass(const float* x, int64_t N, int D, int K, const float* 
     if (rc) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int blocks = diag_blocks(N, D, K);
-    const long long waves = (long long)blocks * DG_NW;
+    const long long waves = (long long)blocks * DIAG_NW;
     DiagArgs a{};
     a.x = x; a.r_in = r_in; a.r = r_out; a.logr = logr_out;
     a.slab = static_cast<double*>(ws);
     a.partials = reinterpret_cast<double*>(static_cast<char*>(ws) + diag_slab_bytes(N, D, K));
     a.pivot = reinterpret_cast<float*>(a.partials + blocks);
     a.N = N; a.K = K;
-    a.rpw = rows_per_wave(N, waves, DG_TILE);
+    a.rpw = rows_per_wave(N, waves, DIAG_TILE);
     if ((rc = launch_diag_dim(D, a, pack, blocks, diag_lds_bytes(D, K), s)) != 0) return rc;
     if (stats_out || bound_out) {
         DiagReduceArgs ra{a.slab, a.partials, a.pivot, stats_out, bound_out, N, (int)waves, blocks, K, D};
@@ -530,7 +478,7 @@ int vmp_mixture_diag_pass(const float* x, int64_t N, int D, int K, const float* 
 int vmp_mixture_diag_finalize(const double* stats, int D, int K, const float* alpha0, const float* beta0, const float* m0, const float* a0,
                               const float* b0, float* alpha, float* beta, float* m, float* a, float* b, float* xbar, float* S, float* pi,
                               void* stream) {
-    int rc = diag_dims("vmp_mixture_diag_finalize", D, K);
+    int rc = stream_dims("vmp_mixture_diag_finalize", D, K, VMP_DIAG_MAX_D);
     if (rc) return rc;
     if (!stats || !alpha0 || !beta0 || !m0 || !a0 || !b0 || !alpha || !beta || !m || !a || !b) {
         set_error("vmp_mixture_diag_finalize: null pointer (stats, prior or posterior)");
@@ -544,7 +492,7 @@ int vmp_mixture_diag_finalize(const double* stats, int D, int K, const float* al
 int vmp_mixture_diag_bound_terms(int D, int K, const float* alpha0, const float* beta0, const float* m0, const float* a0, const float* b0,
                                  const float* alpha, const float* beta, const float* m, const float* a, const float* b, double* out,
                                  void* stream) {
-    int rc = diag_dims("vmp_mixture_diag_bound_terms", D, K);
+    int rc = stream_dims("vmp_mixture_diag_bound_terms", D, K, VMP_DIAG_MAX_D);
     if (rc) return rc;
     if (!alpha0 || !beta0 || !m0 || !a0 || !b0 || !alpha || !beta || !m || !a || !b || !out) {
         set_error("vmp_mixture_diag_bound_terms: null pointer (prior, posterior or out)");
@@ -560,7 +508,7 @@ int vmp_mixture_diag_iterate(const float* x, int64_t N, int D, int K, const floa
                              float* b, float* xbar, float* S, float* pi, float* pack, double* stats, double* bound, void* ws,
                              size_t ws_bytes, int iterations, void* stream) {
     if (!stats) {
-        int rc = diag_dims("vmp_mixture_diag_iterate", D, K);
+        int rc = stream_dims("vmp_mixture_diag_iterate", D, K, VMP_DIAG_MAX_D);
         if (rc) return rc;
         set_error("vmp_mixture_diag_iterate: null pointer (stats)");
         return VMP_E_BADARG;

@@ -6,8 +6,8 @@
 //   l_nk = log w_k + sum_{d in o(n)} [ h_kd - (a_k + 1/2) log1p(g_kd (x_nd - m_kd)^2) ],   logp_n = logsumexp_k l_nk
 // The pack is [ m (D) | g (D) | h (D) | log w | a + 1/2 | c = log w + sum_d h_d ] per component, fp32.
 //
-// The pass kernel is the E-part of diag_pass_kernel (vmp_diagfit.hip): 4 waves per block, wave g owns the rows [g rpw, (g+1) rpw), walks
-// them in tiles of 64, lane = row.  A tile of x (and of the mask bytes) is copied to the wave's own LDS with coalesced loads, so the
+// The pass kernel is the E-part of diag_pass_kernel (vmp_diagfit.hip; what the two files share is in vmp_diag_stream.h): 4 waves per
+// block, wave g owns the rows [g rpw, (g+1) rpw), walks them in tiles of 64, lane = row.  A tile of x (and of the mask bytes) is copied to the wave's own LDS with coalesced loads, so the
 // alignment of x changes no bit; the row's D values sit in registers and the pack words are wave-uniform scalar operands.
 //
 // sum_d log1p(t_d), t_d = g_d (x_d - m_d)^2 >= 0.  a_k grows like N_k / 2 while t shrinks like 1 / N_k, so log1p has to be accurate
@@ -24,14 +24,12 @@
 // observed coordinates are added in d order.  mask == NULL is its own instantiation without any of this.
 // The rows' logp are added in fp64 in a fixed order: a lane's rows, the lanes of a wave (a fixed butterfly), the waves of a block,
 // the blocks (dscore_rowsum_kernel, one wave).  No atomics; the geometry depends on N only.
-#include "vmp_mix_stream.h"
+#include "vmp_diag_stream.h"
 
 using namespace vmp;
 
 namespace {
 
-constexpr int DS_NW = 4;                      // waves per block
-constexpr int DS_TILE = 64;                   // rows of a tile: one per lane
 constexpr int DS_GROUP = 4;                   // cells merged before one logarithm
 constexpr int DS_ROWS_PER_BLOCK = 1024;
 constexpr int DS_MAX_BLOCKS = 2048;
@@ -39,19 +37,11 @@ constexpr int DS_FENCE = 16;                  // cells between two scheduling fe
 constexpr float DS_TMAX = 3e38f;
 constexpr float DS_LN2 = 0.693147180559945309f;
 
-typedef const __attribute__((address_space(4))) float cfloat;
-
 inline int dscore_blocks(int64_t N) { return stream_blocks(N, DS_ROWS_PER_BLOCK, DS_MAX_BLOCKS); }
 // bytes of a row of the mask tile: a multiple of 4 with an odd word count, so the 64 lanes read 64 different banks
 constexpr int dscore_mask_stride(int D) { return 4 * (((D + 3) / 4) | 1); }
 inline size_t dscore_lds_bytes(int D, int K, bool masked) {
-    return (size_t)DS_NW * DS_TILE * (((D | 1) + (K | 1)) * sizeof(float) + (masked ? dscore_mask_stride(D) : 0));
-}
-
-inline int dscore_dims(const char* who, int D, int K) {
-    if (D < 1 || D > VMP_DIAG_MAX_D) { set_error("%s: D=%d outside compiled range 1..%d", who, D, VMP_DIAG_MAX_D); return VMP_E_DIM; }
-    if (K < 1 || K > VMP_MAX_K) { set_error("%s: K=%d outside compiled range 1..%d", who, K, VMP_MAX_K); return VMP_E_DIM; }
-    return 0;
+    return (size_t)DIAG_NW * DIAG_TILE * (((D | 1) + (K | 1)) * sizeof(float) + (masked ? dscore_mask_stride(D) : 0));
 }
 
 struct DScoreArgs {
@@ -66,40 +56,29 @@ struct DScoreArgs {
     int K;
 };
 
-// `total` contiguous elements of src -> the LDS tile dst of 64 rows x `width` with row stride `stride`; the rest becomes zeros
-template <typename T>
-__device__ __forceinline__ void dscore_stage(const T* src, T* dst, int total, int width, int stride, int lane) {
-    int row = lane / width, col = lane % width;
-    for (int i = lane; i < DS_TILE * width; i += WAVE) {
-        dst[row * stride + col] = i < total ? src[i] : T(0);
-        col += WAVE;
-        while (col >= width) { col -= width; ++row; }
-    }
-}
-
 template <int D, bool MASKED>
-__global__ __launch_bounds__(DS_NW * WAVE) void dscore_pass_kernel(DScoreArgs a, const float* __restrict__ pack) {
+__global__ __launch_bounds__(DIAG_NW * WAVE) void dscore_pass_kernel(DScoreArgs a, const float* __restrict__ pack) {
     extern __shared__ float ds_lds[];
-    __shared__ double wsum[DS_NW];
+    __shared__ double wsum[DIAG_NW];
     constexpr int XS = D | 1, PW = 3 * D + 3, MS = dscore_mask_stride(D);
     const int K = a.K, RS = K | 1;
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    float* xs = ds_lds + wave * DS_TILE * (XS + RS);
-    float* rs = xs + DS_TILE * XS;
-    uint8_t* mb = reinterpret_cast<uint8_t*>(ds_lds + DS_NW * DS_TILE * (XS + RS)) + wave * DS_TILE * MS;
+    float* xs = ds_lds + wave * DIAG_TILE * (XS + RS);
+    float* rs = xs + DIAG_TILE * XS;
+    uint8_t* mb = reinterpret_cast<uint8_t*>(ds_lds + DIAG_NW * DIAG_TILE * (XS + RS)) + wave * DIAG_TILE * MS;
 
-    const long long g = (long long)blockIdx.x * DS_NW + wave;
+    const long long g = (long long)blockIdx.x * DIAG_NW + wave;
     const long long r0 = g * a.rpw;
     const long long r1 = r0 + a.rpw < a.N ? r0 + a.rpw : a.N;
     cfloat* cpack = (cfloat*)pack;
     double dsum = 0.0;                                                       // the lane's rows' logp, in row order
 
-    for (long long t0 = r0; t0 < r1; t0 += DS_TILE) {
-        const int rows = r1 - t0 < DS_TILE ? (int)(r1 - t0) : DS_TILE;
+    for (long long t0 = r0; t0 < r1; t0 += DIAG_TILE) {
+        const int rows = r1 - t0 < DIAG_TILE ? (int)(r1 - t0) : DIAG_TILE;
         const bool valid = lane < rows;
-        dscore_stage(a.x + t0 * D, xs, rows * D, D, XS, lane);
-        if (MASKED) dscore_stage(a.mask + t0 * D, mb, rows * D, D, MS, lane);
+        tile_stage(a.x + t0 * D, xs, rows * D, D, XS, lane);
+        if (MASKED) tile_stage(a.mask + t0 * D, mb, rows * D, D, MS, lane);
         __builtin_amdgcn_wave_barrier();
         float x[D], o[MASKED ? D : 1];
         unsigned mlo = 0u, mhi = 0u;                                         // bit d of (mhi, mlo): coordinate d is missing
@@ -200,18 +179,9 @@ __global__ __launch_bounds__(DS_NW * WAVE) void dscore_pass_kernel(DScoreArgs a,
             }
         }
         __builtin_amdgcn_wave_barrier();
-        if (a.resp) {                                                        // the tile of resp is contiguous in resp_out
-            float* dst = a.resp + t0 * K;
-            const int total = rows * K;
-            int row = lane / K, col = lane % K;
-            for (int i = lane; i < total; i += WAVE) {
-                dst[i] = rs[row * RS + col];
-                col += WAVE;
-                while (col >= K) { col -= K; ++row; }
-            }
-        }
-        if (fill) {                                                          // and so is the tile of x_out
-            float* dst = a.x_out + t0 * D;
+        if (a.resp) tile_store(a.resp + t0 * K, rs, rows * K, K, RS, lane);  // the tile of resp is contiguous in resp_out
+        if (fill) {                                                          // and so is the tile of x_out (D is a constant here: in
+            float* dst = a.x_out + t0 * D;                                   // tile_store the column walk gets another closed form)
             const int total = rows * D;
             int row = lane / D, col = lane % D;
             for (int i = lane; i < total; i += WAVE) {
@@ -230,7 +200,7 @@ __global__ __launch_bounds__(DS_NW * WAVE) void dscore_pass_kernel(DScoreArgs a,
     if (threadIdx.x == 0 && a.partials) {
         double s = wsum[0];
 #pragma unroll
-        for (int j = 1; j < DS_NW; ++j) s += wsum[j];
+        for (int j = 1; j < DIAG_NW; ++j) s += wsum[j];
         a.partials[blockIdx.x] = s;
     }
 }
@@ -291,22 +261,12 @@ __global__ __launch_bounds__(WAVE) void dscore_pack_kernel(DScorePackArgs a) {
     }
 }
 
-template <int D, bool MASKED>
-int launch_dscore(const DScoreArgs& a, const float* pack, int blocks, size_t lds, hipStream_t s) {
-    if (lds > 48 * 1024)
-        if (const int rc = set_dyn_lds(reinterpret_cast<const void*>(dscore_pass_kernel<D, MASKED>), lds, "dscore_pass_kernel")) return rc;
-    hipLaunchKernelGGL((dscore_pass_kernel<D, MASKED>), dim3(blocks), dim3(DS_NW * WAVE), lds, s, a, pack);
-    return check_launch("dscore_pass_kernel");
-}
-
-#define DS_CASE(n) case n: return a.mask ? launch_dscore<n, true>(a, pack, blocks, lds, s) : launch_dscore<n, false>(a, pack, blocks, lds, s);
-#define DS_CASE8(b) DS_CASE(b + 1) DS_CASE(b + 2) DS_CASE(b + 3) DS_CASE(b + 4) DS_CASE(b + 5) DS_CASE(b + 6) DS_CASE(b + 7) DS_CASE(b + 8)
 int launch_dscore_dim(int D, const DScoreArgs& a, const float* pack, int blocks, size_t lds, hipStream_t s) {
-    switch (D) {
-        DS_CASE8(0) DS_CASE8(8) DS_CASE8(16) DS_CASE8(24) DS_CASE8(32) DS_CASE8(40) DS_CASE8(48) DS_CASE8(56)
-        default: break;
-    }
-    return -1;
+    return dispatch_dim<VMP_DIAG_MAX_D>(D, [&](auto d) {
+        constexpr int DD = decltype(d)::value;
+        return a.mask ? launch_dyn_lds(dscore_pass_kernel<DD, true>, "dscore_pass_kernel", blocks, DIAG_NW * WAVE, lds, s, a, pack)
+                      : launch_dyn_lds(dscore_pass_kernel<DD, false>, "dscore_pass_kernel", blocks, DIAG_NW * WAVE, lds, s, a, pack);
+    });
 }
 
 }  // namespace
@@ -322,7 +282,7 @@ size_t vmp_mixture_diag_score_workspace_bytes(int64_t N, int D, int K) {
 
 int vmp_mixture_diag_score_pack(int D, int K, const float* alpha, const float* beta, const float* m, const float* a, const float* b,
                                 float* pack, void* stream) {
-    int rc = dscore_dims("vmp_mixture_diag_score_pack", D, K);
+    int rc = stream_dims("vmp_mixture_diag_score_pack", D, K, VMP_DIAG_MAX_D);
     if (rc) return rc;
     if (!alpha || !beta || !m || !a || !b || !pack) {
         set_error("vmp_mixture_diag_score_pack: null pointer (posterior or pack)");
@@ -336,7 +296,7 @@ int vmp_mixture_diag_score_pack(int D, int K, const float* alpha, const float* b
 int vmp_mixture_diag_score(const float* x, const uint8_t* mask, int64_t N, int D, int K, const float* pack, float* logp_out,
                            float* resp_out, float* x_out, double* sum_out, void* ws, size_t ws_bytes, void* stream) {
     const char* who = "vmp_mixture_diag_score";
-    int rc = dscore_dims(who, D, K);
+    int rc = stream_dims(who, D, K, VMP_DIAG_MAX_D);
     if (rc) return rc;
     if (N <= 0) { set_error("%s: N must be positive (got %lld)", who, (long long)N); return VMP_E_BADARG; }
     if (!x || !pack) { set_error("%s: null pointer (%s)", who, !x ? "x" : "pack"); return VMP_E_BADARG; }
@@ -352,7 +312,7 @@ int vmp_mixture_diag_score(const float* x, const uint8_t* mask, int64_t N, int D
     a.x = x; a.mask = mask; a.logp = logp_out; a.resp = resp_out; a.x_out = x_out;
     a.partials = sum_out ? static_cast<double*>(ws) : nullptr;
     a.N = N; a.K = K;
-    a.rpw = rows_per_wave(N, (long long)blocks * DS_NW, DS_TILE);
+    a.rpw = rows_per_wave(N, (long long)blocks * DIAG_NW, DIAG_TILE);
     if ((rc = launch_dscore_dim(D, a, pack, blocks, dscore_lds_bytes(D, K, mask != nullptr), s)) != 0) return rc;
     if (sum_out) {
         hipLaunchKernelGGL(dscore_rowsum_kernel, dim3(1), dim3(WAVE), 0, s, a.partials, blocks, sum_out);

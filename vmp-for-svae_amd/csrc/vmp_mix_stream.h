@@ -47,8 +47,8 @@ __device__ __forceinline__ void block_sum(const double* partials, int nblk, doub
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------------
-inline int stream_dims(const char* who, int D, int K) {
-    if (D < 1 || D > VMP_MAX_D) { set_error("%s: D=%d outside compiled range 1..%d", who, D, VMP_MAX_D); return VMP_E_DIM; }
+inline int stream_dims(const char* who, int D, int K, int max_d = VMP_MAX_D) {
+    if (D < 1 || D > max_d) { set_error("%s: D=%d outside compiled range 1..%d", who, D, max_d); return VMP_E_DIM; }
     if (K < 1 || K > VMP_MAX_K) { set_error("%s: K=%d outside compiled range 1..%d", who, K, VMP_MAX_K); return VMP_E_DIM; }
     return 0;
 }
@@ -61,6 +61,16 @@ inline int stream_blocks(int64_t N, int64_t rows_per_block, int max_blocks) {
 
 // rows per wave, a multiple of the `step` rows a wave advances per iteration: wave g owns rows [g rpw, min(N, (g+1) rpw))
 inline long long rows_per_wave(int64_t N, long long waves, int step) { return ((N + waves - 1) / waves + step - 1) / step * step; }
+
+// the refusals of a workspace that holds fp64 words: `need` bytes, 8-byte aligned
+inline int workspace_check(const char* who, const void* ws, size_t ws_bytes, size_t need) {
+    if (!ws || ws_bytes < need) {
+        set_error("%s: workspace too small (%zu bytes, need %zu)", who, ws ? ws_bytes : (size_t)0, need);
+        return VMP_E_WS;
+    }
+    if (reinterpret_cast<uintptr_t>(ws) & 7) { set_error("%s: workspace not 8-byte aligned", who); return VMP_E_BADARG; }
+    return 0;
+}
 
 // the refusals of a requested row sum (sum_out != NULL): the workspace holds one fp64 partial per block
 inline int sum_workspace_check(const char* who, const double* sum_out, const void* ws, size_t ws_bytes, size_t need) {

@@ -239,15 +239,6 @@ __global__ __launch_bounds__(SEED_NW * WAVE) void seed_assign_kernel(AssignArgs 
     }
 }
 
-int seed_ws_check(const char* who, const void* ws, size_t ws_bytes, size_t need) {
-    if (!ws || ws_bytes < need) {
-        set_error("%s: workspace too small (%zu bytes, need %zu)", who, ws ? ws_bytes : (size_t)0, need);
-        return VMP_E_WS;
-    }
-    if (reinterpret_cast<uintptr_t>(ws) & 7) { set_error("%s: workspace not 8-byte aligned", who); return VMP_E_BADARG; }
-    return 0;
-}
-
 template <int D>
 int launch_rounds(SeedArgs a, float* mind2_out, int blocks, hipStream_t s) {
     for (int j = 0; j <= a.K; ++j) {
@@ -286,7 +277,7 @@ int vmp_mixture_seed_centers(const float* x, const uint8_t* mask, const float* f
         set_error("%s: mask and fill are given together or both NULL (%s is NULL)", who, !mask ? "mask" : "fill");
         return VMP_E_BADARG;
     }
-    if ((rc = seed_ws_check(who, ws, ws_bytes, seed_ws_bytes(N)))) return rc;
+    if ((rc = workspace_check(who, ws, ws_bytes, seed_ws_bytes(N)))) return rc;
     const int blocks = seed_blocks(N);
     SeedArgs a{};
     a.x = x; a.mask = mask; a.fill = fill;

@@ -441,13 +441,7 @@ int wfit_pass_check(const char* who, const float* x, const float* w, const uint8
     if (!r_out && stats_out) { set_error("%s: stats_out needs r_out (the moments are those of the r the pass writes)", who); return VMP_E_BADARG; }
     if (!r_out && logr_out) { set_error("%s: logr_out needs r_out", who); return VMP_E_BADARG; }
     if (x_fill_out && !mask) { set_error("%s: x_fill_out needs a mask (a complete row has nothing to fill)", who); return VMP_E_BADARG; }
-    const size_t need = vmp_mixture_wfit_workspace_bytes(N, D, K);
-    if (!ws || ws_bytes < need) {
-        set_error("%s: workspace too small (%zu bytes, need %zu)", who, ws ? ws_bytes : (size_t)0, need);
-        return VMP_E_WS;
-    }
-    if (reinterpret_cast<uintptr_t>(ws) & 7) { set_error("%s: workspace not 8-byte aligned", who); return VMP_E_BADARG; }
-    return 0;
+    return workspace_check(who, ws, ws_bytes, vmp_mixture_wfit_workspace_bytes(N, D, K));
 }
 
 }  // namespace

@@ -201,13 +201,7 @@ def _score_dims(x, pack, miss, what):
     return N, D, K
 
 
-def _mask_u8(miss):
-    """(N,D) uint8 view / copy of a missing-data mask of any dtype (nonzero = missing)"""
-    if miss.dtype == torch.bool:
-        return miss.contiguous().view(torch.uint8)
-    if miss.dtype == torch.uint8:
-        return miss.contiguous()
-    return (miss != 0).view(torch.uint8)
+_mask_u8 = L.mask_u8
 
 
 def mixture_diag_score(x, pack, miss=None, want_logp=True, want_resp=False, want_fill=False, want_sum=False, inplace=False):
@@ -431,18 +425,7 @@ class DiagLoop(object):
         """run(check_every) and lower_bound() in turn until the bound improves by less than tol * max(1, |bound|) over the previous
         check, or `max_iterations` iterations of this call are done (the rule of VMPLoop.run_until_bound).  Returns
         [(iterations, bound), ...]."""
-        check_every = int(check_every)
-        if check_every < 1:
-            raise L.VmpError('check_every must be >= 1')
-        hist, done = [], 0
-        while done < max_iterations:
-            n = min(check_every, max_iterations - done)
-            self.run(n)
-            done += n
-            hist.append((self.iterations, self.lower_bound()))
-            if len(hist) > 1 and hist[-1][1] - hist[-2][1] < tol * max(1.0, abs(hist[-1][1])):
-                break
-        return hist
+        return L.check_until(self, self.lower_bound, lambda v, prev: v - prev < tol * max(1.0, abs(v)), check_every, max_iterations)
 
     def predictive_pack(self):
         """score pack of the CURRENT posterior (diag_score_pack on theta())"""
@@ -483,18 +466,7 @@ class DiagLoop(object):
         """run(check_every) and heldout(x_val) in turn until the score improves by less than `tol` (absolute, nats per row) over the
         previous check, or `max_iterations` iterations of this call are done (the rule of VMPLoop.run_until).  Returns
         [(iterations, score), ...] with `iterations` the loop's running count."""
-        check_every = int(check_every)
-        if check_every < 1:
-            raise L.VmpError('check_every must be >= 1')
-        hist, done = [], 0
-        while done < max_iterations:
-            n = min(check_every, max_iterations - done)
-            self.run(n)
-            done += n
-            hist.append((self.iterations, self.heldout(x_val)))
-            if len(hist) > 1 and hist[-1][1] - hist[-2][1] < tol:
-                break
-        return hist
+        return L.check_until(self, lambda: self.heldout(x_val), lambda v, prev: v - prev < tol, check_every, max_iterations)
 
     def _refuse_score(self, *args, **kw):
         raise L.VmpError('DiagLoop: score and impute are not built for the diagonal mixture under these names - use heldout / '

@@ -332,13 +332,7 @@ def mixture_draw(n, pack, seed, row0=0, want_z=False):
     return x_out[0], (z[0] if want_z else None)
 
 
-def _mask_u8(miss):
-    """(N,D) uint8 view / copy of a missing-data mask of any dtype (nonzero = missing), as mixture_impute normalises it"""
-    if miss.dtype == torch.bool:
-        return miss.contiguous().view(torch.uint8)
-    if miss.dtype == torch.uint8:
-        return miss.contiguous()
-    return (miss != 0).view(torch.uint8)
+_mask_u8 = L.mask_u8
 
 
 def fit_pack(alpha_k, beta_k, m_k, C_k, v_k):
@@ -963,18 +957,7 @@ class VMPLoop(object):
         """run(check_every) and score(x_val) in turn until the score improves by less than `tol` (absolute, nats per row) over
         the previous check, or `max_iterations` iterations of this call are done.  Returns [(iterations, score), ...] with
         `iterations` the loop's running count.  A plain host loop: one scalar read-back per check."""
-        check_every = int(check_every)
-        if check_every < 1:
-            raise L.VmpError('check_every must be >= 1')
-        hist, done = [], 0
-        while done < max_iterations:
-            n = min(check_every, max_iterations - done)
-            self.run(n)
-            done += n
-            hist.append((self.iterations, self.score(x_val)))
-            if len(hist) > 1 and hist[-1][1] - hist[-2][1] < tol:
-                break
-        return hist
+        return L.check_until(self, lambda: self.score(x_val), lambda v, prev: v - prev < tol, check_every, max_iterations)
 
     def _check_bound(self, need_posterior):
         """the refusals of lower_bound() / run_until_bound(), on the host: nothing here looks at a device"""
@@ -1001,18 +984,7 @@ class VMPLoop(object):
         held-out rows.  Returns [(iterations, bound), ...] with `iterations` the loop's running count, as run_until does.  A plain
         host loop: one scalar read-back per check."""
         self._check_bound(False)
-        check_every = int(check_every)
-        if check_every < 1:
-            raise L.VmpError('check_every must be >= 1')
-        hist, done = [], 0
-        while done < max_iterations:
-            n = min(check_every, max_iterations - done)
-            self.run(n)
-            done += n
-            hist.append((self.iterations, self.lower_bound()))
-            if len(hist) > 1 and hist[-1][1] - hist[-2][1] < tol * max(1.0, abs(hist[-1][1])):
-                break
-        return hist
+        return L.check_until(self, self.lower_bound, lambda v, prev: v - prev < tol * max(1.0, abs(v)), check_every, max_iterations)
 
     @property
     def stats(self):

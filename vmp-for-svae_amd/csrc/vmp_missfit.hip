@@ -31,7 +31,7 @@ namespace {
 
 constexpr int FIT_NW = 4;                 // waves per block
 constexpr int FIT_MAX_BLOCKS = 512;
-constexpr int FIT_CHUNK = 128;            // rows of a wave between two fp32 -> fp64 flushes: VMP_MOM_FLUSH (2) tiles of 64 rows in vmp_mix.hip
+constexpr int FIT_CHUNK = 128;            // rows of a wave between two fp32 -> fp64 flushes: the cadence of vmp_mix.hip's pass_kernel (VMP_MOM_FLUSH = 2 tiles of 64 rows)
 constexpr int FIT_RED_GROUPS = 16;        // wave groups of the reduction block
 
 inline int fit_blocks(int64_t N) { return stream_blocks(N, (int64_t)FIT_NW * FIT_CHUNK, FIT_MAX_BLOCKS); }

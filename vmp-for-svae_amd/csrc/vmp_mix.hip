@@ -141,7 +141,13 @@ __device__ __forceinline__ float row16_bcast_bank(float s) {
 
 constexpr int MOM_TERMS = 3;
 #ifndef VMP_MOM_FLUSH
-#define VMP_MOM_FLUSH 2       // tiles of 64 rows between two fp32 -> fp64 flushes of the moment accumulators (both pass kernels)
+#define VMP_MOM_FLUSH 2       // tiles of 64 rows between two fp32 -> fp64 flushes of the moment accumulators (pass_kernel)
+#endif
+// The same cadence of the XDL pass (pass_xdl_body): a wave of up to 16 tiles flushes once, after its last tile; a longer one every
+// 16th tile as well.  Measured against 2, 4 and 8 (profiles/NOTES_mix_pass_uniform.md): the fp64 conversions and additions of a
+// flush issue at a fraction of the fp32 rate, and at the flagship shape a wave has 5.5 to 10 tiles.
+#ifndef VMP_XDL_MOM_FLUSH
+#define VMP_XDL_MOM_FLUSH 16
 #endif
 
 // Block reduction of the fp64 moment accumulators (waves summed in a fixed order) and the per-block partial: shared by
@@ -1141,9 +1147,9 @@ __device__ __forceinline__ void pass_xdl_body(const PassArgs& a) {
 
     auto flush = [&]() __attribute__((always_inline)) {
         if constexpr (STATS) {
-            // fp32 accumulators -> fp64 every VMP_MOM_FLUSH-th tile (default 2 = 128 rows; the fp64 conversions and additions run at a fraction of
-            // the fp32 rate: 48 of them per tile were ~5 % of the kernel) and after the wave's last tile
-            if (((row0 - lo) / TR) % VMP_MOM_FLUSH == VMP_MOM_FLUSH - 1 || row0 + TR >= hi) {
+            // fp32 accumulators -> fp64 every VMP_XDL_MOM_FLUSH-th tile (16 = 1 024 rows; the fp64 conversions and additions run at a fraction
+            // of the fp32 rate: 48 of them per tile were ~5 % of the kernel) and after the wave's last tile
+            if (((row0 - lo) / TR) % VMP_XDL_MOM_FLUSH == VMP_XDL_MOM_FLUSH - 1 || row0 + TR >= hi) {
 #pragma unroll
                 for (int c = 0; c < 4; ++c) {
 #pragma unroll

@@ -819,6 +819,18 @@ int    vmp_svae_step_inputs(void* dst16, uint64_t philox_key, float cvi_step, fl
                             float* y_dst, int64_t n_floats, void* stream);
 /* Number of partial rows the fused MLP backward kernel writes for `rows` input rows (N*K*S for the decoder). */
 int    vmp_decoder_bwd_blocks(int64_t rows);
+/* Host query, no launch and no device: the launch plan of the fused MLP kernels (csrc/vmp_decoder.hip) for `rows` input rows
+ * (N*K*S for the decoder).  kind: 0 forward (vmp_decoder_loglike_fwd, vmp_mlp_gauss_head_fwd), 1 evaluation forward
+ * (vmp_decoder_eval_fwd), 2 encoder forward + prep (vmp_mlp_gauss_head_fwd_prep*; K components add 2 K blocks, K is ignored by the
+ * other kinds), 3 backward of the decoder (vmp_decoder_loglike_bwd*, vmp_decoder_elbo*), 4 backward with the head outputs' gradients
+ * as inputs (vmp_mlp_gauss_bwd, vmp_mlp_gauss_head_bwd*).  out = [UT: 16-unit tiles of the instance | FS: U is no multiple of 16 |
+ * BT: bf16 terms of the backward data path's operands (2 or 3) | split: the older wave's % of a SIMD pair's tiles | red_one: the
+ * block epilogue sums all 8 waves' slabs in one round | blocks (backward: the partial rows, vmp_decoder_bwd_blocks) | threads per
+ * block | dynamic LDS bytes]; FS, BT, split and red_one are 0 for the forward kinds.  Returns 0, or with out zeroed: VMP_E_DIM for
+ * the sizes the entry points refuse (L, Dy outside 1..8, U outside 1..64, rows < 0 or >= 2^31; kind 2: rows < 1, K outside
+ * 1..VMP_MAX_K), VMP_E_BADARG (out NULL, no such kind).  rows = 0 is planned as a launch would be (one block), although the entry
+ * points launch nothing then and vmp_decoder_bwd_blocks(0) is 0.                                                              */
+int    vmp_decoder_launch_plan(int kind, int64_t rows, int L, int Dy, int U, int K, int64_t* out);
 /* vmp_decoder_elbo without its second launch: dx, ll as there; the (vmp_decoder_bwd_blocks(N*K*S), param_words) fp32
  * parameter partials are left in ws for vmp_svae_step_final.  The scalar tail runs inside vmp_svae_estep_bwd_tail.  */
 int    vmp_decoder_elbo_lazy(const float* x, const float* y, const float* log_z, float sigma, const float* W0,

@@ -1,12 +1,13 @@
 """fp64 yardsticks for the fused decoder / encoder backward (csrc/vmp_decoder.hip, dec_bwd_kernel<UT, FS, GIN, BT>) at row counts
 where one autograd graph is too big, and a pure-Python restatement of the kernel's tile-range arithmetic.  CPU only: nothing
-here touches a GPU (vmp_decoder_bwd_blocks / vmp_decoder_param_words are host-only ABI calls).
+here touches a GPU (vmp_decoder_launch_plan / vmp_decoder_bwd_blocks are host-only ABI calls).
 
   truth_chunked       oracle.nets.decoder / oracle.nets.mlp in fp64 with torch autograd, chunk by chunk; memory = one chunk
   two_term_emulation  the same mathematics written out by hand in fp64, with the operands the kernel's BT = 2 path splits into
                       bf16 terms replaced by their 2-term values and each product restricted to the partial products the kernel
                       issues - the "reference arithmetic's own error" yardstick of the 2-term bars (as the __f32 goldens and
                       bar() are in test_mix_gpu.py)
+  bwd_plan ...        what the library's launch layer decides (vmp_decoder_launch_plan): instance, split, epilogue form, grid
   bwd_tile_plan       ntiles, grid, tpb, tpp and every wave's (t0, t1) as the top of dec_bwd_kernel computes them
   CASES ...           the shapes tests/test_decoder_tiles_gpu.py runs; tests/test_decoder_truth.py proves the branch of each
 """
@@ -18,32 +19,41 @@ import torch
 NET_VARS = ('layer_0/kernel', 'layer_0/bias', 'layer_1/kernel', 'layer_1/bias', 'gaussian_output/kernel',
             'gaussian_output/bias', 'shortcut/W', 'shortcut/b1', 'shortcut/b2')
 
-# Sample rows from which dec_bwd_launch (csrc/vmp_decoder.hip, `#define VMP_DEC_BT2_ROWS (1u << 19)`) instantiates the backward
-# kernel with BT = 2 in decoder mode (gradient-input mode keeps BT = 3 at every size: `bt2 = !GIN && ...` there).  The ABI has
-# no getter for it: this is the one place the tests state it.
+# Sample rows from which dec_plan (csrc/vmp_decoder.hip, `#define VMP_DEC_BT2_ROWS (1u << 19)`) plans the backward kernel with BT = 2 in
+# decoder mode (gradient-input mode keeps BT = 3 at every size).  Stated here and proven against vmp_decoder_launch_plan by
+# tests/test_decoder_truth.py; every decision below is asked of the library.
 DEC_BT2_ROWS = 1 << 19
 BWD_WAVES = 8                         # BWD_THREADS / WAVE
 TANH_PRESCALE = float(np.float32(2.8853900817779268))    # fill_images folds 2 log2(e) into the hidden layers' FORWARD weight images
+KIND_BWD, KIND_BWD_GIN = 3, 4         # the backward `kind`s of vmp_decoder_launch_plan (include/vmp_hip.h)
+PLAN_FIELDS = ('UT', 'FS', 'BT', 'split', 'red_one', 'blocks', 'threads', 'lds_bytes')
+
+
+def bwd_plan(L, Dy, U, R, gin=False):
+    """vmp_decoder_launch_plan's answer for the backward over R sample rows as a dict (pure host: no launch, no device)."""
+    import ctypes
+    import vmp_for_svae_amd as V
+    out = (ctypes.c_int64 * 8)()
+    V._lib.check(V._lib.lib().vmp_decoder_launch_plan(KIND_BWD_GIN if gin else KIND_BWD, R, L, Dy, U, 0, out), 'vmp_decoder_launch_plan')
+    return dict(zip(PLAN_FIELDS, out))
 
 
 def bwd_split(U):
-    """dec_bwd_launch: a.split = (U & 15) ? 58 : 54 - the older wave's % of a SIMD pair's tiles."""
-    return 58 if U & 15 else 54
+    """DecArgs::split as the library plans it - the older wave's % of a SIMD pair's tiles (it depends on U alone)."""
+    return bwd_plan(8, 8, U, 16)['split']
 
 
 def bwd_variant(L, Dy, U, R, gin=False):
-    """Template arguments and epilogue form dec_bwd_launch picks: (UT, FS, BT, red_one)."""
-    import vmp_for_svae_amd as V
-    PW = V._lib.lib().vmp_decoder_param_words(L, U, Dy)
-    red_one = ((1 + BWD_WAVES) * PW + 64) * 4 <= 160 * 1024
-    return (U + 15) // 16, bool(U & 15), 2 if (R >= DEC_BT2_ROWS and not gin) else 3, red_one
+    """Template arguments and epilogue form the library plans: (UT, FS, BT, red_one)."""
+    p = bwd_plan(L, Dy, U, R, gin)
+    return p['UT'], bool(p['FS']), p['BT'], bool(p['red_one'])
 
 
 def bwd_tile_plan(R, split, grid=None):
-    """The tile ranges of dec_bwd_kernel for R sample rows; the grid is what the library launches (vmp_decoder_bwd_blocks)."""
+    """The tile ranges of dec_bwd_kernel for R sample rows; the grid is what the library launches (the plan's blocks)."""
+    lib_plan = bwd_plan(*SHIPPED_NET, R)                                # (grid and BT depend on the rows alone)
     if grid is None:
-        import vmp_for_svae_amd as V
-        grid = V._lib.lib().vmp_decoder_bwd_blocks(R)
+        grid = lib_plan['blocks']
     ntiles = (R + 15) // 16
     tpb = (ntiles + grid - 1) // grid
     tpp = (tpb + 3) // 4
@@ -69,7 +79,7 @@ def bwd_tile_plan(R, split, grid=None):
             'uneven': tpp >= 8 and older != (tpp + 1) // 2,             # ... and differs from the even share
             'ragged': R % 16 != 0,
             'last_short': 0 < ntiles - (grid - empty - 1) * tpb < tpb,
-            'bt': 2 if R >= DEC_BT2_ROWS else 3}                        # decoder mode; gradient-input mode: 3
+            'bt': lib_plan['BT']}                                       # decoder mode; gradient-input mode: 3
 
 
 # ---- the shapes of tests/test_decoder_tiles_gpu.py ----------------------------------------------------------------

@@ -1,7 +1,8 @@
 """CPU checks of tests/decoder_truth.py: the chunked fp64 truth equals the one-graph truth of test_decoder_gpu.py, the 2-term
 emulation with its truncation off equals the truth and with it on differs by what two bf16 terms allow, and the restated tile
 ranges of dec_bwd_kernel cover every tile once and put every case of tests/test_decoder_tiles_gpu.py on the branch it is named
-for (a later retuning of dec_bwd_blocks, a.split or VMP_DEC_BT2_ROWS fails here instead of silently moving a case)."""
+for (a later retuning of dec_plan's grid, split or VMP_DEC_BT2_ROWS fails here instead of silently moving a case: the launch
+decisions are read from the library through vmp_decoder_launch_plan, not restated)."""
 import numpy as np
 import pytest
 import torch
@@ -119,6 +120,24 @@ def test_plan_thresholds_come_from_the_library():
     assert T.case_rows('few_tile_last') == lo and T.case_rows('eight_wave_first') == lo + 16
     assert T.case_rows('bt3_last') < T.DEC_BT2_ROWS <= T.case_rows('bt2_first')
     assert T.case_rows('bt2_first') - T.case_rows('bt3_last') == 3 * 7                       # one data row apart
+
+
+def test_stated_constants_are_the_librarys():
+    """DEC_BT2_ROWS and BWD_WAVES are stated in decoder_truth.py; the library's launch plan must agree: BT flips exactly between
+    DEC_BT2_ROWS - 1 and DEC_BT2_ROWS rows in decoder mode and never in gradient-input mode, a backward block is BWD_WAVES waves, and
+    the grid the tile plan is built on is the number of partial rows vmp_decoder_bwd_blocks tells the callers to reduce."""
+    import vmp_for_svae_amd as V
+    lib = V._lib.lib()
+    rows = sorted(set(ALL_ROWS + [T.DEC_BT2_ROWS - 1, T.DEC_BT2_ROWS, T.DEC_BT2_ROWS + 1, 2 ** 31 - 1]))
+    for net in [T.SHIPPED_NET, (1, 1, 1)] + list(T.EXTRA_NETS):
+        for R in rows:
+            dec, gin = T.bwd_plan(*net, R), T.bwd_plan(*net, R, gin=True)
+            assert dec['BT'] == (2 if R >= T.DEC_BT2_ROWS else 3) and gin['BT'] == 3, (net, R)
+            assert dec['threads'] // 64 == gin['threads'] // 64 == T.BWD_WAVES and dec['threads'] % 64 == 0
+            assert dec['blocks'] == gin['blocks'] == lib.vmp_decoder_bwd_blocks(R), (net, R)
+    assert T.bwd_plan(*T.SHIPPED_NET, T.DEC_BT2_ROWS - 1)['BT'] == 3 and T.bwd_plan(*T.SHIPPED_NET, T.DEC_BT2_ROWS)['BT'] == 2
+    for R in rows:
+        assert T.bwd_tile_plan(R, 58)['grid'] == lib.vmp_decoder_bwd_blocks(R)
 
 
 def test_row_cases_sit_on_the_branch_they_are_named_for():

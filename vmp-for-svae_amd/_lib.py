@@ -125,6 +125,7 @@ _SIGNATURES = {
                                     + [_P] * 7 + [_P, _c.c_int, _P, _P, _P]),
     'vmp_svae_step_inputs': (_c.c_int, [_P, _c.c_uint64, _c.c_float, _c.c_float, _P, _P, _c.c_int64, _P]),
     'vmp_decoder_bwd_blocks': (_c.c_int, [_c.c_int64]),
+    'vmp_decoder_launch_plan': (_c.c_int, [_c.c_int, _c.c_int64] + [_c.c_int] * 4 + [_P]),
     'vmp_decoder_elbo_lazy': (_c.c_int, [_P] * 3 + [_c.c_float] + [_P] * 9 + [_c.c_int64] + [_c.c_int] * 5 + [_P, _P, _P, _c.c_size_t, _P]),
     'vmp_mlp_gauss_head_bwd_lazy': (_c.c_int, [_P] * 3 + [_c.c_float] + [_P] * 9 + [_c.c_int64] + [_c.c_int] * 3 + [_P, _P, _c.c_size_t, _P]),
     'vmp_svae_bwd_tail_applies': (_c.c_int, [_c.c_int64, _c.c_int, _c.c_int, _c.c_int]),

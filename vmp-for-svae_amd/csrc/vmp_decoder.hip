@@ -35,6 +35,7 @@
 #include "vmp_tail.h"
 #include "vmp_step_parts.h"
 #include "vmp_prep_parts.h"
+#include <type_traits>
 
 using namespace vmp;
 
@@ -43,6 +44,10 @@ namespace {
 constexpr int FWD_THREADS = 256;       // forward: 2+ blocks per CU
 constexpr int BWD_THREADS = 512;       // backward: 1 block per CU (8 waves share one set of operand images)
 constexpr int BWD_WAVES = BWD_THREADS / WAVE;
+#ifndef VMP_DEC_BT2_ROWS
+#define VMP_DEC_BT2_ROWS (1u << 19)   // sample rows from which the backward data path uses 2-term operands (0xffffffff: never)
+#endif
+constexpr unsigned DEC_BT2_ROWS = VMP_DEC_BT2_ROWS;
 
 struct DecArgs {
     const float* x;        // (R, L)  rows = N*K*S
@@ -130,6 +135,67 @@ struct Img {
     static constexpr int SCR = BWD_END;
     static constexpr int BWD_TOTAL = SCR + BWD_WAVES * (XSZ + PSZ + QSZ);
 };
+struct ImgWords { int fwd_end, bwd_total; };
+constexpr ImgWords IMG_WORDS[4] = {{Img<1>::FWD_END, Img<1>::BWD_TOTAL}, {Img<2>::FWD_END, Img<2>::BWD_TOTAL},
+                                   {Img<3>::FWD_END, Img<3>::BWD_TOTAL}, {Img<4>::FWD_END, Img<4>::BWD_TOTAL}};       // [UT - 1]
+
+// ---- the launch plan: every host decision about a launch of this file, made in one place ---------------------------
+// The launchers, the size queries (vmp_decoder_workspace_bytes, vmp_decoder_bwd_blocks), the workspace checks and
+// vmp_decoder_launch_plan all read it: a buffer sized from a query and the launch that fills it cannot disagree.
+enum DecKind { DEC_FWD = 0, DEC_EVAL = 1, DEC_PREP = 2, DEC_BWD = 3, DEC_BWD_GIN = 4 };     // (the `kind` of vmp_decoder_launch_plan)
+struct DecPlan {
+    int UT;                // the instance: unit tiles of 16 ...
+    bool FS;               // ... backward: U is no multiple of 16 ...
+    int BT;                // ... backward: bf16 terms of the data path's operands (2 or 3) ...
+    int LP;                // ... encoder forward + prep: the latent size of the K-sized maps (= Dy)
+    int split;             // DecArgs::split
+    int red_one;           // DecArgs::red_one
+    int blocks, threads;
+    int lds;               // dynamic LDS bytes
+    int PW;                // parameter words = words of a block's partial row (backward)
+    const char* kernel;    // what a failed launch is reported as
+};
+int dec_blocks(long long rows, int waves_per_block, int max_blocks) {
+    const long long tiles = (rows + 15) / 16;
+    long long b = (tiles + waves_per_block - 1) / waves_per_block;
+    if (b > max_blocks) b = max_blocks;
+    if (b < 1) b = 1;
+    return (int)b;
+}
+// K: the components of the prep kind, whose K-sized maps run in 2 K blocks behind the encoder's.  Sizes are NOT checked here
+// (dec_check): a U outside 1..64 plans the UT = 4 instance, as the size queries always answered.
+DecPlan dec_plan(DecKind kind, long long rows, int L, int Dy, int U, int K = 0) {
+    DecPlan p{};
+    const int ut = (U + 15) / 16;
+    p.UT = ut >= 1 && ut <= 3 ? ut : 4;
+    p.PW = dec_geo(L, U, Dy).PW;
+    if (kind == DEC_FWD || kind == DEC_EVAL || kind == DEC_PREP) {
+        constexpr int bpc = 16;   // blocks per CU: 4 are resident (82 VGPRs, 39 KB LDS), the rest back-fill as the older blocks - which the sequencer favours - finish (2 -> 4 -> 16: 4.5 -> 3.9 -> 3.5 ms per 4.2e7 rows)
+        p.blocks = dec_blocks(rows, FWD_THREADS / WAVE, 256 * bpc);
+        if (kind == DEC_PREP) { p.blocks += 2 * K; p.LP = Dy; }
+        p.threads = FWD_THREADS;
+        p.lds = IMG_WORDS[p.UT - 1].fwd_end * (int)sizeof(float);
+        p.kernel = kind == DEC_FWD ? "dec_fwd_kernel" : kind == DEC_EVAL ? "dec_eval_kernel" : "enc_prep_kernel";
+        return p;
+    }
+    p.FS = (U & 15) != 0;
+    p.BT = kind == DEC_BWD && rows >= (long long)DEC_BT2_ROWS ? 2 : 3;      // gradient-input mode: 3-term at every size (see dec_bwd_kernel)
+    // measured optimum at 4.2e7 rows: 58 % for U = 50 (10.0 -> 9.3 ms), 54 % for U = 64 (11.8 -> 11.3 ms)
+    p.split = (U & 15) ? 58 : 54;
+    p.red_one = ((size_t)(1 + BWD_WAVES) * p.PW + 64) * sizeof(float) <= 160u * 1024u;     // accumulator + 8 slabs inside the CU's LDS
+    const int red_floats = (1 + (p.red_one ? BWD_WAVES : BWD_WAVES / 2)) * p.PW + 64;   // epilogue: accumulator + slabs + dump word
+    // 1 block per CU.  Few tiles (<= 4 per CU): one tile per SIMD - waves 0-3 of a block take one each and waves 4-7 none, so
+    // that a block's epilogue (every wave with work stores a PW-word slab, then the slabs are summed) runs with one wave per
+    // SIMD and four slabs; with 8 one-tile waves per block it was 40 % of the launch at the reference's minibatch sizes.
+    const long long tiles = (rows + 15) / 16;
+    p.blocks = tiles <= 4 * 256 ? dec_blocks(rows, BWD_WAVES / 2, 256) : dec_blocks(rows, BWD_WAVES, 256);
+    p.threads = BWD_THREADS;
+    const int img = IMG_WORDS[p.UT - 1].bwd_total;
+    p.lds = (img > red_floats ? img : red_floats) * (int)sizeof(float);
+    p.kernel = "dec_bwd_kernel";
+    return p;
+}
+size_t dec_ws_bytes(const DecPlan& p) { return (size_t)p.blocks * (size_t)p.PW * sizeof(float); }     // the backward's partial rows
 
 // output slot m (0..15) of the last layer: lane group g = m>>2 owns slots 4g..4g+3 = (mean d0, mean d1, var d0, var d1)
 // with d0 = 2g, d1 = 2g+1 - so that a lane finds mean and variance of the same output dimension in its own registers.
@@ -833,7 +899,7 @@ __device__ __forceinline__ u32x4 trt_read(const unsigned char* __restrict__ img,
 // the 21-gradient bars of tests/test_fullsize_gpu.py at N = 65 536 and 1e5 gate the whole step.  It saves 34 of 195 MFMAs and
 // 64 of 840 VALU instructions per 16-row tile.  Small batches keep BT = 3, and so does gradient-input mode at every size: its
 // upstream gradients are free inputs, the row sums may cancel, and at 524 307 rows with independent upstream gradients the
-// 2-term form left db0, db1, dW0 and dW1 at 1.0e-5 .. 1.7e-5 (dec_bwd_launch; the GIN instances are built for BT = 3 only).
+// 2-term form left db0, db1, dW0 and dW1 at 1.0e-5 .. 1.7e-5 (dec_plan; the GIN instances are built for BT = 3 only).
 template <int UT, bool FS, bool GIN, int BT>
 __global__ __launch_bounds__(BWD_THREADS, 2) void dec_bwd_kernel(DecArgs a) {
     DEC_TS(0);
@@ -1242,27 +1308,9 @@ __global__ __launch_bounds__(64 * DEC_RED_GROUPS) void dec_reduce_tail_kernel(De
     else elbo_tail_body(t, blockIdx.x - red_blocks, gridDim.x - red_blocks);
 }
 
-int dec_blocks(long long rows, int waves_per_block, int max_blocks) {
-    const long long tiles = (rows + 15) / 16;
-    long long b = (tiles + waves_per_block - 1) / waves_per_block;
-    if (b > max_blocks) b = max_blocks;
-    if (b < 1) b = 1;
-    return (int)b;
-}
 #ifdef VMP_DEBUG_TS
 static long long* g_dbg_dec = nullptr;
 #endif
-int dec_fwd_blocks(long long rows) {
-    constexpr int bpc = 16;   // blocks per CU: 4 are resident (82 VGPRs, 39 KB LDS), the rest back-fill as the older blocks - which the sequencer favours - finish (2 -> 4 -> 16: 4.5 -> 3.9 -> 3.5 ms per 4.2e7 rows)
-    return dec_blocks(rows, FWD_THREADS / WAVE, 256 * bpc);
-}
-// 1 block per CU.  Few tiles (<= 4 per CU): one tile per SIMD - waves 0-3 of a block take one each and waves 4-7 none, so
-// that a block's epilogue (every wave with work stores a PW-word slab, then the slabs are summed) runs with one wave per
-// SIMD and four slabs; with 8 one-tile waves per block it was 40 % of the launch at the reference's minibatch sizes.
-int dec_bwd_blocks(long long rows) {
-    const long long tiles = (rows + 15) / 16;
-    return tiles <= 4 * 256 ? dec_blocks(rows, BWD_WAVES / 2, 256) : dec_blocks(rows, BWD_WAVES, 256);
-}
 
 int dec_check(const char* what, long long N, int K, int S, int L, int Dy, int U) {
     if (N < 0 || K < 1 || S < 1 || L < 1 || L > 8 || Dy < 1 || Dy > 8 || U < 1 || U > 64) {
@@ -1276,81 +1324,74 @@ int dec_check(const char* what, long long N, int K, int S, int L, int Dy, int U)
     return 0;
 }
 
-// dispatch on UT = unit tiles of 16
-#define DEC_DISPATCH(U, CALL)                          \
-    do {                                               \
-        switch (((U) + 15) / 16) {                     \
-            case 1: CALL(1); break;                    \
-            case 2: CALL(2); break;                    \
-            case 3: CALL(3); break;                    \
-            default: CALL(4); break;                   \
-        }                                              \
-    } while (0)
+// f(std::integral_constant<int, UT>) for the plan's UT = unit tiles of 16; returns what f returns
+template <class F>
+int with_ut(int UT, F&& f) {
+    switch (UT) {
+        case 1: return f(std::integral_constant<int, 1>{});
+        case 2: return f(std::integral_constant<int, 2>{});
+        case 3: return f(std::integral_constant<int, 3>{});
+        default: return f(std::integral_constant<int, 4>{});
+    }
+}
+// one launch as the plan shapes it: 0, or the HIP error code of the LDS attribute (the caller checks the launch itself)
+template <class... KA, class... A>
+int launch(void (*kernel)(KA...), const DecPlan& p, hipStream_t s, const A&... args) {
+    if (const int rc = set_dyn_lds(reinterpret_cast<const void*>(kernel), (size_t)p.lds, p.kernel)) return rc;
+    hipLaunchKernelGGL(kernel, dim3(p.blocks), dim3(p.threads), p.lds, s, args...);
+    return 0;
+}
+
+// the weights of one network and its sizes, as every entry point receives them
+struct DecNet {
+    const float *W0, *b0, *W1, *b1, *W2, *b2, *Ws, *bs1, *bs2;
+    int L, Dy, U;
+};
+bool net_set(const DecNet& n) { return n.W0 && n.b0 && n.W1 && n.b1 && n.W2 && n.b2 && n.Ws && n.bs1 && n.bs2; }
+// the part of DecArgs every launch shares: the weights and R = N*K*S rows of an L -> U -> U -> Dy network
+DecArgs dec_args(const DecNet& n, int64_t N, int K, int S) {
+    DecArgs a{};
+    a.W0 = n.W0; a.b0 = n.b0; a.W1 = n.W1; a.b1 = n.b1; a.W2 = n.W2; a.b2 = n.b2; a.Ws = n.Ws; a.bs1 = n.bs1; a.bs2 = n.bs2;
+    a.R = (unsigned)(N * K * S); a.K = (unsigned)K; a.S = (unsigned)S; a.L = n.L; a.Dy = n.Dy; a.U = n.U;
+    return a;
+}
 
 template <bool GIN>
-int dec_bwd_launch(const DecArgs& a0, int blocks, hipStream_t s) {
-    // measured optimum at 4.2e7 rows: 58 % for U = 50 (10.0 -> 9.3 ms), 54 % for U = 64 (11.8 -> 11.3 ms)
-    DecArgs a = a0;
+int dec_bwd_launch(DecArgs a, const DecPlan& p, hipStream_t s) {
 #ifdef VMP_DEBUG_TS
     a.dbg_t = g_dbg_dec;
 #endif
-    a.split = (a0.U & 15) ? 58 : 54;
-    const int U = a.U;
-    const int PWl = dec_geo(a.L, a.U, a.Dy).PW;
-    a.red_one = ((size_t)(1 + BWD_WAVES) * PWl + 64) * sizeof(float) <= 160u * 1024u;     // accumulator + 8 slabs inside the CU's LDS
-    const int red_floats = (1 + (a.red_one ? BWD_WAVES : BWD_WAVES / 2)) * PWl + 64;   // epilogue: accumulator + slabs + dump word
-#ifndef VMP_DEC_BT2_ROWS
-#define VMP_DEC_BT2_ROWS (1u << 19)   // sample rows from which the backward data path uses 2-term operands (0xffffffff: never)
-#endif
-    const bool bt2 = !GIN && a.R >= (unsigned)VMP_DEC_BT2_ROWS;      // gradient-input mode: 3-term at every size (see dec_bwd_kernel)
-#define DEC_BWD_L(UTV, FSV, BTV)                                                                                      \
-    do {                                                                                                              \
-        if (const int rc_ = set_dyn_lds(reinterpret_cast<const void*>(dec_bwd_kernel<UTV, FSV, GIN, (GIN ? 3 : BTV)>), (size_t)lds, "dec_bwd_kernel")) return rc_; \
-        hipLaunchKernelGGL((dec_bwd_kernel<UTV, FSV, GIN, (GIN ? 3 : BTV)>), dim3(blocks), dim3(BWD_THREADS), lds, s, a); \
-    } while (0)
-#define DEC_BWD(UTV)                                                                                                  \
-    do {                                                                                                              \
-        const int lds = (Img<UTV>::BWD_TOTAL > red_floats ? Img<UTV>::BWD_TOTAL : red_floats) * (int)sizeof(float);   \
-        if ((U & 15) == 0) { if (bt2) DEC_BWD_L(UTV, false, 2); else DEC_BWD_L(UTV, false, 3); }                      \
-        else { if (bt2) DEC_BWD_L(UTV, true, 2); else DEC_BWD_L(UTV, true, 3); }                                      \
-    } while (0)
-    DEC_DISPATCH(U, DEC_BWD);
-#undef DEC_BWD
-#undef DEC_BWD_L
-    return check_launch(GIN ? "vmp_mlp_gauss_bwd" : "vmp_decoder_loglike_bwd");
+    a.split = p.split;
+    a.red_one = p.red_one;
+    const int rc = with_ut(p.UT, [&](auto ut) {
+        constexpr int UT = decltype(ut)::value;
+        if (!p.FS) return p.BT == 2 ? launch(dec_bwd_kernel<UT, false, GIN, (GIN ? 3 : 2)>, p, s, a) : launch(dec_bwd_kernel<UT, false, GIN, 3>, p, s, a);
+        return p.BT == 2 ? launch(dec_bwd_kernel<UT, true, GIN, (GIN ? 3 : 2)>, p, s, a) : launch(dec_bwd_kernel<UT, true, GIN, 3>, p, s, a);
+    });
+    return rc ? rc : check_launch(GIN ? "vmp_mlp_gauss_bwd" : "vmp_decoder_loglike_bwd");
 }
 
+// What both backward modes do behind their argument checks: no rows - zero gradients; else the workspace check, the launch and,
+// unless lazy, the reduction of the per-block partials (with `tail`: in one launch with the ELBO's scalar tail).
 // lazy: the per-block parameter partials stay in `ws` ((vmp_decoder_bwd_blocks, PW) fp32) for a later launch to reduce - no reduce launch here
-int decoder_loglike_bwd_impl(const char* what, float logw, const TailArgs* tail, unsigned tail_blocks, bool lazy, const float* x, const float* y, const float* gA,
-                             const float* W0, const float* b0, const float* W1, const float* b1, const float* W2, const float* b2, const float* Ws,
-                            const float* bs1, const float* bs2, int64_t N, int K, int S, int L, int Dy, int U, float* dx,
-                            float* dparams, float* ll, void* ws, size_t ws_bytes, void* stream) {
-    if (int e = dec_check(what, N, K, S, L, Dy, U)) return e;
-    if (!x || !y || !gA || !W0 || !b0 || !W1 || !b1 || !W2 || !b2 || !Ws || !bs1 || !bs2 || !dx || (!dparams && !lazy) || !ws) {
-        set_error("%s: NULL argument", what);
-        return VMP_E_BADARG;
-    }
-    const DecGeo q = dec_geo(L, U, Dy);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (N == 0) {
-        if (lazy) { set_error("%s: N = 0", what); return VMP_E_DIM; }
-        (void)hipMemsetAsync(dparams, 0, (size_t)q.PW * sizeof(float), s);
+template <bool GIN>
+int dec_bwd_run(const char* what, DecArgs a, const DecNet& n, bool lazy, float* dparams, void* ws, size_t ws_bytes, const TailArgs* tail,
+                unsigned tail_blocks, hipStream_t s) {
+    const DecPlan p = dec_plan(GIN ? DEC_BWD_GIN : DEC_BWD, (long long)a.R, n.L, n.Dy, n.U);
+    if (a.R == 0) {
+        if (lazy) { set_error("%s: %s = 0", what, GIN ? "R" : "N"); return VMP_E_DIM; }
+        (void)hipMemsetAsync(dparams, 0, (size_t)p.PW * sizeof(float), s);
         return check_launch(what);
     }
-    const size_t need = (size_t)dec_bwd_blocks((long long)N * K * S) * (size_t)q.PW * sizeof(float);
-    if (ws_bytes < need) {
-        set_error("%s: workspace too small (%zu < %zu bytes)", what, ws_bytes, need);
+    if (ws_bytes < dec_ws_bytes(p)) {
+        set_error("%s: workspace too small (%zu < %zu bytes)", what, ws_bytes, dec_ws_bytes(p));
         return VMP_E_WS;
     }
-    DecArgs a{};
-    a.x = x; a.y = y; a.gA = gA; a.W0 = W0; a.b0 = b0; a.W1 = W1; a.b1 = b1; a.W2 = W2; a.b2 = b2; a.Ws = Ws; a.bs1 = bs1; a.bs2 = bs2;
-    a.dx = dx; a.part = static_cast<float*>(ws); a.ll = ll; a.logw = logw; a.vscale = 1.0f;
-    a.R = (unsigned)(N * K * S); a.K = (unsigned)K; a.S = (unsigned)S; a.L = L; a.Dy = Dy; a.U = U;
-    const int blocks = dec_bwd_blocks((long long)a.R);
-    if (int e = dec_bwd_launch<false>(a, blocks, s)) return e;
+    a.part = static_cast<float*>(ws);
+    if (int e = dec_bwd_launch<GIN>(a, p, s)) return e;
     if (lazy) return 0;
-    DecRedArgs r{a.part, bs2, dparams, blocks, q.PW, q.obs2, Dy};
-    const int red_blocks = (q.PW + 63) / 64;
+    DecRedArgs r{a.part, n.bs2, dparams, p.blocks, p.PW, dec_geo(n.L, n.U, n.Dy).obs2, n.Dy};
+    const int red_blocks = (p.PW + 63) / 64;
     if (tail) {
         hipLaunchKernelGGL(dec_reduce_tail_kernel, dim3(red_blocks + tail_blocks), dim3(64 * DEC_RED_GROUPS), 0, s, r, *tail, red_blocks);
         if (tail_blocks > 1) hipLaunchKernelGGL(dec_elbo_final_kernel, dim3(1), dim3(WAVE), 0, s, *tail, tail_blocks);      // the three scalars, behind a kernel boundary (one tail block: written by that block)
@@ -1359,39 +1400,38 @@ int decoder_loglike_bwd_impl(const char* what, float logw, const TailArgs* tail,
     return check_launch(what);
 }
 
-int decoder_fwd_impl(const char* what, float vscale, const float* x, const float* y, const float* W0, const float* b0, const float* W1,
-                            const float* b1, const float* W2, const float* b2, const float* Ws, const float* bs1,
-                            const float* bs2, int64_t N, int K, int S, int L, int Dy, int U, float* ll, float* mean,
-                            float* var, void* stream) {
-    if (int e = dec_check(what, N, K, S, L, Dy, U)) return e;
-    if (!x || (!y && ll) || !W0 || !b0 || !W1 || !b1 || !W2 || !b2 || !Ws || !bs1 || !bs2 || (!ll && !mean) || (!mean != !var)) {
+int decoder_loglike_bwd_impl(const char* what, float logw, const TailArgs* tail, unsigned tail_blocks, bool lazy, const float* x, const float* y, const float* gA,
+                             const DecNet& n, int64_t N, int K, int S, float* dx, float* dparams, float* ll, void* ws, size_t ws_bytes, void* stream) {
+    if (int e = dec_check(what, N, K, S, n.L, n.Dy, n.U)) return e;
+    if (!x || !y || !gA || !net_set(n) || !dx || (!dparams && !lazy) || !ws) {
+        set_error("%s: NULL argument", what);
+        return VMP_E_BADARG;
+    }
+    DecArgs a = dec_args(n, N, K, S);
+    a.x = x; a.y = y; a.gA = gA; a.dx = dx; a.ll = ll; a.logw = logw; a.vscale = 1.0f;
+    return dec_bwd_run<false>(what, a, n, lazy, dparams, ws, ws_bytes, tail, tail_blocks, static_cast<hipStream_t>(stream));
+}
+
+int decoder_fwd_impl(const char* what, float vscale, const float* x, const float* y, const DecNet& n, int64_t N, int K, int S, float* ll, float* mean,
+                     float* var, void* stream) {
+    if (int e = dec_check(what, N, K, S, n.L, n.Dy, n.U)) return e;
+    if (!x || (!y && ll) || !net_set(n) || (!ll && !mean) || (!mean != !var)) {
         set_error("%s: NULL argument", what);
         return VMP_E_BADARG;
     }
     if (N == 0) return 0;
-    DecArgs a{};
-    a.x = x; a.y = y; a.W0 = W0; a.b0 = b0; a.W1 = W1; a.b1 = b1; a.W2 = W2; a.b2 = b2; a.Ws = Ws; a.bs1 = bs1; a.bs2 = bs2;
-    a.ll = ll; a.mean = mean; a.var = var; a.vscale = vscale;
-    a.R = (unsigned)(N * K * S); a.K = (unsigned)K; a.S = (unsigned)S; a.L = L; a.Dy = Dy; a.U = U;
-    const int blocks = dec_fwd_blocks((long long)a.R);
+    DecArgs a = dec_args(n, N, K, S);
+    a.x = x; a.y = y; a.ll = ll; a.mean = mean; a.var = var; a.vscale = vscale;
+    const DecPlan p = dec_plan(DEC_FWD, (long long)a.R, n.L, n.Dy, n.U);
     hipStream_t s = static_cast<hipStream_t>(stream);
-#define DEC_FWD(UTV)                                                                                                  \
-    do {                                                                                                              \
-        const int lds = Img<UTV>::FWD_END * (int)sizeof(float);                                                       \
-        if (const int rc_ = set_dyn_lds(reinterpret_cast<const void*>(dec_fwd_kernel<UTV>), (size_t)lds, "dec_fwd_kernel")) return rc_; \
-        hipLaunchKernelGGL((dec_fwd_kernel<UTV>), dim3(blocks), dim3(FWD_THREADS), lds, s, a);                        \
-    } while (0)
-    DEC_DISPATCH(U, DEC_FWD);
-#undef DEC_FWD
+    if (const int rc = with_ut(p.UT, [&](auto ut) { return launch(dec_fwd_kernel<decltype(ut)::value>, p, s, a); })) return rc;
     return check_launch(what);
 }
 
-int decoder_eval_impl(const char* what, const float* x, const float* y, const float* W0, const float* b0, const float* W1, const float* b1,
-                      const float* W2, const float* b2, const float* Ws, const float* bs1, const float* bs2, const uint8_t* mask,
-                      int mask_mse, const float* logw, int64_t N, int K, int S, int L, int Dy, int U, float* mse, float* lse, void* ws,
-                      size_t ws_bytes, void* stream) {
-    if (int e = dec_check(what, N, K, S, L, Dy, U)) return e;
-    if (!x || !y || !W0 || !b0 || !W1 || !b1 || !W2 || !b2 || !Ws || !bs1 || !bs2 || !ws || (!mse && !lse)) {
+int decoder_eval_impl(const char* what, const float* x, const float* y, const DecNet& n, const uint8_t* mask, int mask_mse, const float* logw,
+                      int64_t N, int K, int S, float* mse, float* lse, void* ws, size_t ws_bytes, void* stream) {
+    if (int e = dec_check(what, N, K, S, n.L, n.Dy, n.U)) return e;
+    if (!x || !y || !net_set(n) || !ws || (!mse && !lse)) {
         set_error("%s: NULL argument", what);
         return VMP_E_BADARG;
     }
@@ -1401,21 +1441,12 @@ int decoder_eval_impl(const char* what, const float* x, const float* y, const fl
         set_error("%s: workspace of %zu bytes (8-byte aligned) needed for the per-row pairs, got %zu", what, rows * sizeof(v2f), ws_bytes);
         return VMP_E_WS;
     }
-    DecArgs a{};
-    a.x = x; a.y = y; a.W0 = W0; a.b0 = b0; a.W1 = W1; a.b1 = b1; a.W2 = W2; a.b2 = b2; a.Ws = Ws; a.bs1 = bs1; a.bs2 = bs2;
-    a.vscale = 1.0f;
-    a.R = (unsigned)rows; a.K = (unsigned)K; a.S = (unsigned)S; a.L = L; a.Dy = Dy; a.U = U;
+    DecArgs a = dec_args(n, N, K, S);
+    a.x = x; a.y = y; a.vscale = 1.0f;
     const EvalEpi e{mask, (mask && mask_mse) ? 1 : 0, static_cast<v2f*>(ws)};
-    const int blocks = dec_fwd_blocks((long long)a.R);
+    const DecPlan p = dec_plan(DEC_EVAL, (long long)a.R, n.L, n.Dy, n.U);
     hipStream_t s = static_cast<hipStream_t>(stream);
-#define DEC_EVAL(UTV)                                                                                                 \
-    do {                                                                                                              \
-        const int lds = Img<UTV>::FWD_END * (int)sizeof(float);                                                       \
-        if (const int rc_ = set_dyn_lds(reinterpret_cast<const void*>(dec_eval_kernel<UTV>), (size_t)lds, "dec_eval_kernel")) return rc_; \
-        hipLaunchKernelGGL((dec_eval_kernel<UTV>), dim3(blocks), dim3(FWD_THREADS), lds, s, a, e);                    \
-    } while (0)
-    DEC_DISPATCH(U, DEC_EVAL);
-#undef DEC_EVAL
+    if (const int rc = with_ut(p.UT, [&](auto ut) { return launch(dec_eval_kernel<decltype(ut)::value>, p, s, a, e); })) return rc;
     if (int rc = check_launch("dec_eval_kernel")) return rc;
     const EvalRedArgs r{static_cast<const v2f*>(ws), logw, mse, lse, (long long)N * K, S};
     const int SL = S < WAVE ? S : WAVE, CPT = WAVE / SL;
@@ -1425,61 +1456,30 @@ int decoder_eval_impl(const char* what, const float* x, const float* y, const fl
     return check_launch("dec_eval_reduce_kernel");
 }
 
-int mlp_gauss_bwd_impl(const char* what, float vscale, bool lazy, const float* x, const float* gmean, const float* gvar, const float* W0, const float* b0,
-                      const float* W1, const float* b1, const float* W2, const float* b2, const float* Ws, const float* bs1,
-                      const float* bs2, int64_t R, int L, int Dy, int U, float* dx, float* dparams, void* ws,
-                      size_t ws_bytes, void* stream) {
-    if (int e = dec_check(what, R, 1, 1, L, Dy, U)) return e;
-    if (!x || !gmean || !gvar || !W0 || !b0 || !W1 || !b1 || !W2 || !b2 || !Ws || !bs1 || !bs2 || (!dparams && !lazy) || !ws) {
+int mlp_gauss_bwd_impl(const char* what, float vscale, bool lazy, const float* x, const float* gmean, const float* gvar, const DecNet& n, int64_t R,
+                       float* dx, float* dparams, void* ws, size_t ws_bytes, void* stream) {
+    if (int e = dec_check(what, R, 1, 1, n.L, n.Dy, n.U)) return e;
+    if (!x || !gmean || !gvar || !net_set(n) || (!dparams && !lazy) || !ws) {
         set_error("%s: NULL argument", what);
         return VMP_E_BADARG;
     }
-    const DecGeo q = dec_geo(L, U, Dy);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (R == 0) {
-        if (lazy) { set_error("%s: R = 0", what); return VMP_E_DIM; }
-        (void)hipMemsetAsync(dparams, 0, (size_t)q.PW * sizeof(float), s);
-        return check_launch(what);
-    }
-    if (ws_bytes < (size_t)dec_bwd_blocks((long long)R) * (size_t)q.PW * sizeof(float)) {
-        set_error("%s: workspace too small", what);
-        return VMP_E_WS;
-    }
-    DecArgs a{};
-    a.x = x; a.gmean = gmean; a.gvar = gvar; a.W0 = W0; a.b0 = b0; a.W1 = W1; a.b1 = b1; a.W2 = W2; a.b2 = b2; a.Ws = Ws;
-    a.bs1 = bs1; a.bs2 = bs2; a.dx = dx; a.part = static_cast<float*>(ws); a.vscale = vscale;
-    a.R = (unsigned)R; a.K = 1; a.S = 1; a.L = L; a.Dy = Dy; a.U = U;
-    const int blocks = dec_bwd_blocks((long long)a.R);
-    if (int e = dec_bwd_launch<true>(a, blocks, s)) return e;
-    if (lazy) return 0;
-    DecRedArgs r{a.part, bs2, dparams, blocks, q.PW, q.obs2, Dy};
-    hipLaunchKernelGGL(dec_reduce_kernel, dim3((q.PW + 63) / 64), dim3(64 * DEC_RED_GROUPS), 0, s, r);
-    return check_launch(what);
+    DecArgs a = dec_args(n, R, 1, 1);
+    a.x = x; a.gmean = gmean; a.gvar = gvar; a.dx = dx; a.vscale = vscale;
+    return dec_bwd_run<true>(what, a, n, lazy, dparams, ws, ws_bytes, nullptr, 0, static_cast<hipStream_t>(stream));
 }
 
-template <int UT, int LP>
-void enc_prep_launch(unsigned grid, int lds, hipStream_t s, const DecArgs& a, const PhiArgs& p, const ThetaArgs& t, const StepTable& st,
-                     unsigned nb) {
-    hipLaunchKernelGGL((enc_prep_kernel<UT, LP>), dim3(grid), dim3(FWD_THREADS), lds, s, a, p, t, st, nb);
-}
-template <int UT, int LP>
-void enc_prep_launch(unsigned grid, int lds, hipStream_t s, const DecArgs& a, const PhiArgs& p, const SmmThetaArgs& t, const StepTable& st,
-                     unsigned nb) {
-    hipLaunchKernelGGL((enc_prep_smm_kernel<UT, LP>), dim3(grid), dim3(FWD_THREADS), lds, s, a, p, t, st, nb);
-}
-template <int UT, int LP> const void* enc_prep_fn(const ThetaArgs*) { return reinterpret_cast<const void*>(enc_prep_kernel<UT, LP>); }
-template <int UT, int LP> const void* enc_prep_fn(const SmmThetaArgs*) { return reinterpret_cast<const void*>(enc_prep_smm_kernel<UT, LP>); }
+// the encoder forward + prep kernel of a theta: Gaussian (ThetaArgs) or Student-t mixture (SmmThetaArgs)
+template <int UT, int LP> auto enc_prep_fn(const ThetaArgs&) { return enc_prep_kernel<UT, LP>; }
+template <int UT, int LP> auto enc_prep_fn(const SmmThetaArgs&) { return enc_prep_smm_kernel<UT, LP>; }
 
 template <class TA>
-int enc_prep_impl(const char* what, bool theta_ok, const float* x, const float* W0, const float* b0, const float* W1, const float* b1, const float* W2,
-                  const float* b2, const float* Ws, const float* bs1, const float* bs2, int64_t R, int L, int Dy, int U, float var_scale,
+int enc_prep_impl(const char* what, bool theta_ok, const float* x, const DecNet& n, int64_t R, float var_scale,
                   float* out1, float* out2, const float* mu_k, const float* L_raw, const float* pi_raw, int K, float* Lk, float* P,
                   float* bias, double* logpi, const TA& t, const void* scalar_table, int table_rows, void* counter, void* dst16,
                   void* stream) {
-    if (int e = dec_check(what, R, 1, 1, L, Dy, U)) return e;
+    if (int e = dec_check(what, R, 1, 1, n.L, n.Dy, n.U)) return e;
     if (R < 1 || K < 1 || K > VMP_MAX_K) { set_error("%s: R = %lld, K = %d", what, (long long)R, K); return VMP_E_DIM; }
-    if (!x || !W0 || !b0 || !W1 || !b1 || !W2 || !b2 || !Ws || !bs1 || !bs2 || !out1 || !out2 || !mu_k || !L_raw || !pi_raw || !Lk || !P ||
-        !bias || !theta_ok) {
+    if (!x || !net_set(n) || !out1 || !out2 || !mu_k || !L_raw || !pi_raw || !Lk || !P || !bias || !theta_ok) {
         set_error("%s: NULL argument", what);
         return VMP_E_BADARG;
     }
@@ -1487,34 +1487,20 @@ int enc_prep_impl(const char* what, bool theta_ok, const float* x, const float* 
         set_error("%s: scalar table without rows / counter / 8-byte aligned destination", what);
         return VMP_E_BADARG;
     }
-    DecArgs a{};
-    a.x = x; a.W0 = W0; a.b0 = b0; a.W1 = W1; a.b1 = b1; a.W2 = W2; a.b2 = b2; a.Ws = Ws; a.bs1 = bs1; a.bs2 = bs2;
-    a.mean = out1; a.var = out2; a.vscale = var_scale;
-    a.R = (unsigned)R; a.K = 1; a.S = 1; a.L = L; a.Dy = Dy; a.U = U;
-    PhiArgs p{};
-    p.mu = mu_k; p.Lraw = L_raw; p.piraw = pi_raw; p.Lk = Lk; p.P = P; p.bias = bias; p.K = K; p.L = Dy; p.logpi_out = logpi;
+    DecArgs a = dec_args(n, R, 1, 1);
+    a.x = x; a.mean = out1; a.var = out2; a.vscale = var_scale;
+    PhiArgs phi{};
+    phi.mu = mu_k; phi.Lraw = L_raw; phi.piraw = pi_raw; phi.Lk = Lk; phi.P = P; phi.bias = bias; phi.K = K; phi.L = n.Dy; phi.logpi_out = logpi;
     StepTable st{static_cast<const unsigned long long*>(scalar_table), static_cast<unsigned long long*>(counter),
                  static_cast<unsigned long long*>(dst16), (unsigned)(table_rows > 0 ? table_rows : 0)};
-    const unsigned nb = (unsigned)dec_fwd_blocks((long long)a.R);
+    const DecPlan p = dec_plan(DEC_PREP, (long long)a.R, n.L, n.Dy, n.U, K);
+    const unsigned nb = (unsigned)(p.blocks - 2 * K);                  // the encoder's blocks; the K-sized maps run in the 2 K behind them
     hipStream_t s = static_cast<hipStream_t>(stream);
-#define ENC_PREP_L(UTV, LP)                                                                                           \
-    do {                                                                                                              \
-        const int lds = Img<UTV>::FWD_END * (int)sizeof(float);                                                       \
-        if (const int rc_ = set_dyn_lds(enc_prep_fn<UTV, LP>(&t), (size_t)lds, "enc_prep_kernel")) return rc_;        \
-        enc_prep_launch<UTV, LP>(nb + 2 * K, lds, s, a, p, t, st, nb);                                                \
-    } while (0)
-#define ENC_PREP(UTV)                                                                                                 \
-    do {                                                                                                              \
-        switch (Dy) {                                                                                                 \
-            case 1: ENC_PREP_L(UTV, 1); break; case 2: ENC_PREP_L(UTV, 2); break; case 3: ENC_PREP_L(UTV, 3); break;  \
-            case 4: ENC_PREP_L(UTV, 4); break; case 5: ENC_PREP_L(UTV, 5); break; case 6: ENC_PREP_L(UTV, 6); break;  \
-            case 7: ENC_PREP_L(UTV, 7); break; default: ENC_PREP_L(UTV, 8); break;                                    \
-        }                                                                                                             \
-    } while (0)
-    DEC_DISPATCH(U, ENC_PREP);
-#undef ENC_PREP
-#undef ENC_PREP_L
-    return check_launch(what);
+    const int rc = with_ut(p.UT, [&](auto ut) {
+        VMP_SWITCH_DIM(p.LP, LP, return launch(enc_prep_fn<decltype(ut)::value, LP>(t), p, s, a, phi, t, st, nb));
+        return 0;
+    });
+    return rc ? rc : check_launch(what);
 }
 
 }  // namespace
@@ -1527,14 +1513,27 @@ void vmp_debug_set_decoder_timestamps(long long* p) { g_dbg_dec = p; }    // exp
 int vmp_decoder_param_words(int L, int U, int Dy) { return dec_geo(L, U, Dy).PW; }
 
 size_t vmp_decoder_workspace_bytes(int64_t N, int K, int S, int L, int U, int Dy) {
-    return (size_t)dec_bwd_blocks((long long)N * K * S) * (size_t)dec_geo(L, U, Dy).PW * sizeof(float);
+    return dec_ws_bytes(dec_plan(DEC_BWD, (long long)N * K * S, L, Dy, U));
+}
+
+int vmp_decoder_launch_plan(int kind, int64_t rows, int L, int Dy, int U, int K, int64_t out[8]) {
+    const char* what = "vmp_decoder_launch_plan";
+    if (!out) { set_error("%s: null pointer", what); return VMP_E_BADARG; }
+    for (int i = 0; i < 8; ++i) out[i] = 0;
+    if (kind < DEC_FWD || kind > DEC_BWD_GIN) { set_error("%s: kind %d", what, kind); return VMP_E_BADARG; }
+    if (int e = dec_check(what, rows, 1, 1, L, Dy, U)) return e;
+    if (kind == DEC_PREP && (rows < 1 || K < 1 || K > VMP_MAX_K)) { set_error("%s: R = %lld, K = %d", what, (long long)rows, K); return VMP_E_DIM; }
+    const DecPlan p = dec_plan((DecKind)kind, rows, L, Dy, U, K);
+    const int64_t v[8] = {p.UT, p.FS, p.BT, p.split, p.red_one, p.blocks, p.threads, p.lds};
+    for (int i = 0; i < 8; ++i) out[i] = v[i];
+    return 0;
 }
 
 int vmp_decoder_eval_fwd(const float* x, const float* y, const float* W0, const float* b0, const float* W1, const float* b1,
                          const float* W2, const float* b2, const float* Ws, const float* bs1, const float* bs2, const uint8_t* mask,
                          int mask_mse, const float* logw, int64_t N, int K, int S, int L, int Dy, int U, float* mse, float* lse,
                          void* ws, size_t ws_bytes, void* stream) {
-    return decoder_eval_impl("vmp_decoder_eval_fwd", x, y, W0, b0, W1, b1, W2, b2, Ws, bs1, bs2, mask, mask_mse, logw, N, K, S, L, Dy, U,
+    return decoder_eval_impl("vmp_decoder_eval_fwd", x, y, DecNet{W0, b0, W1, b1, W2, b2, Ws, bs1, bs2, L, Dy, U}, mask, mask_mse, logw, N, K, S,
                              mse, lse, ws, ws_bytes, stream);
 }
 
@@ -1542,14 +1541,14 @@ int vmp_decoder_loglike_fwd(const float* x, const float* y, const float* W0, con
                             const float* b1, const float* W2, const float* b2, const float* Ws, const float* bs1,
                             const float* bs2, int64_t N, int K, int S, int L, int Dy, int U, float* ll, float* mean,
                             float* var, void* stream) {
-    return decoder_fwd_impl("vmp_decoder_loglike_fwd", 1.0f, x, y, W0, b0, W1, b1, W2, b2, Ws, bs1, bs2, N, K, S, L, Dy, U, ll, mean, var,
+    return decoder_fwd_impl("vmp_decoder_loglike_fwd", 1.0f, x, y, DecNet{W0, b0, W1, b1, W2, b2, Ws, bs1, bs2, L, Dy, U}, N, K, S, ll, mean, var,
                             stream);
 }
 
 int vmp_mlp_gauss_head_fwd(const float* x, const float* W0, const float* b0, const float* W1, const float* b1, const float* W2,
                            const float* b2, const float* Ws, const float* bs1, const float* bs2, int64_t R, int L, int Dy, int U,
                            float var_scale, float* out1, float* out2, void* stream) {
-    return decoder_fwd_impl("vmp_mlp_gauss_head_fwd", var_scale, x, nullptr, W0, b0, W1, b1, W2, b2, Ws, bs1, bs2, R, 1, 1, L, Dy, U,
+    return decoder_fwd_impl("vmp_mlp_gauss_head_fwd", var_scale, x, nullptr, DecNet{W0, b0, W1, b1, W2, b2, Ws, bs1, bs2, L, Dy, U}, R, 1, 1,
                             nullptr, out1, out2, stream);
 }
 
@@ -1562,7 +1561,7 @@ int vmp_mlp_gauss_head_fwd_prep(const float* x, const float* W0, const float* b0
                                 const void* scalar_table, int table_rows, void* counter, void* dst16, void* stream) {
     const char* what = "vmp_mlp_gauss_head_fwd_prep";
     const bool theta_ok = alpha && A && b && beta && v_hat && m && W && kappa;
-    return enc_prep_impl(what, theta_ok, x, W0, b0, W1, b1, W2, b2, Ws, bs1, bs2, R, L, Dy, U, var_scale, out1, out2, mu_k, L_raw, pi_raw, K, Lk, P,
+    return enc_prep_impl(what, theta_ok, x, DecNet{W0, b0, W1, b1, W2, b2, Ws, bs1, bs2, L, Dy, U}, R, var_scale, out1, out2, mu_k, L_raw, pi_raw, K, Lk, P,
                          bias, logpi, ThetaArgs{alpha, A, b, beta, v_hat, m, W, kappa, K, Dy}, scalar_table, table_rows, counter, dst16, stream);
 }
 
@@ -1575,7 +1574,7 @@ int vmp_mlp_gauss_head_fwd_prep_smm(const float* x, const float* W0, const float
                                     void* dst16, void* stream) {
     const char* what = "vmp_mlp_gauss_head_fwd_prep_smm";
     const bool theta_ok = alpha && theta_L_raw && dof && W && kappa;
-    return enc_prep_impl(what, theta_ok, x, W0, b0, W1, b1, W2, b2, Ws, bs1, bs2, R, L, Dy, U, var_scale, out1, out2, mu_k, L_raw, pi_raw, K, Lk, P,
+    return enc_prep_impl(what, theta_ok, x, DecNet{W0, b0, W1, b1, W2, b2, Ws, bs1, bs2, L, Dy, U}, R, var_scale, out1, out2, mu_k, L_raw, pi_raw, K, Lk, P,
                          bias, logpi, SmmThetaArgs{alpha, theta_L_raw, dof, W, kappa, K, Dy}, scalar_table, table_rows, counter, dst16,
                          stream);
 }
@@ -1584,7 +1583,7 @@ int vmp_decoder_loglike_bwd(const float* x, const float* y, const float* gA, con
                             const float* W1, const float* b1, const float* W2, const float* b2, const float* Ws,
                             const float* bs1, const float* bs2, int64_t N, int K, int S, int L, int Dy, int U, float* dx,
                             float* dparams, float* ll, void* ws, size_t ws_bytes, void* stream) {
-    return decoder_loglike_bwd_impl("vmp_decoder_loglike_bwd", 0.f, nullptr, 0, false, x, y, gA, W0, b0, W1, b1, W2, b2, Ws, bs1, bs2, N, K, S, L, Dy, U,
+    return decoder_loglike_bwd_impl("vmp_decoder_loglike_bwd", 0.f, nullptr, 0, false, x, y, gA, DecNet{W0, b0, W1, b1, W2, b2, Ws, bs1, bs2, L, Dy, U}, N, K, S,
                                     dx, dparams, ll, ws, ws_bytes, stream);
 }
 
@@ -1596,8 +1595,8 @@ int vmp_decoder_loglike_bwd_logw(const float* x, const float* y, const float* lo
         set_error("vmp_decoder_loglike_bwd_logw: w_scale must not be 0");
         return VMP_E_BADARG;
     }
-    return decoder_loglike_bwd_impl("vmp_decoder_loglike_bwd_logw", w_scale, nullptr, 0, false, x, y, log_w, W0, b0, W1, b1, W2, b2, Ws, bs1, bs2, N, K,
-                                    S, L, Dy, U, dx, dparams, ll, ws, ws_bytes, stream);
+    return decoder_loglike_bwd_impl("vmp_decoder_loglike_bwd_logw", w_scale, nullptr, 0, false, x, y, log_w, DecNet{W0, b0, W1, b1, W2, b2, Ws, bs1, bs2, L, Dy, U},
+                                    N, K, S, dx, dparams, ll, ws, ws_bytes, stream);
 }
 
 int vmp_decoder_elbo(const float* x, const float* y, const float* log_z, const float* T_prime, float sigma, const float* W0,
@@ -1619,15 +1618,15 @@ int vmp_decoder_elbo(const float* x, const float* y, const float* log_z, const f
     }
     TailArgs t{};
     const unsigned tb = tail_setup(t, log_z, T_prime, ll, N, K, S, Dy, sigma, scalars, g_log_z, g_T_prime, r, tail_ws, 64 * DEC_RED_GROUPS);
-    return decoder_loglike_bwd_impl("vmp_decoder_elbo", -sigma * 0.5f / (float)S, &t, tb, false, x, y, log_z, W0, b0, W1, b1, W2, b2, Ws, bs1,
-                                    bs2, N, K, S, L, Dy, U, dx, dparams, ll, ws, ws_bytes, stream);
+    return decoder_loglike_bwd_impl("vmp_decoder_elbo", -sigma * 0.5f / (float)S, &t, tb, false, x, y, log_z, DecNet{W0, b0, W1, b1, W2, b2, Ws, bs1, bs2, L, Dy, U},
+                                    N, K, S, dx, dparams, ll, ws, ws_bytes, stream);
 }
 
 int vmp_mlp_gauss_bwd(const float* x, const float* gmean, const float* gvar, const float* W0, const float* b0,
                       const float* W1, const float* b1, const float* W2, const float* b2, const float* Ws, const float* bs1,
                       const float* bs2, int64_t R, int L, int Dy, int U, float* dx, float* dparams, void* ws,
                       size_t ws_bytes, void* stream) {
-    return mlp_gauss_bwd_impl("vmp_mlp_gauss_bwd", 1.0f, false, x, gmean, gvar, W0, b0, W1, b1, W2, b2, Ws, bs1, bs2, R, L, Dy, U, dx, dparams,
+    return mlp_gauss_bwd_impl("vmp_mlp_gauss_bwd", 1.0f, false, x, gmean, gvar, DecNet{W0, b0, W1, b1, W2, b2, Ws, bs1, bs2, L, Dy, U}, R, dx, dparams,
                               ws, ws_bytes, stream);
 }
 
@@ -1635,14 +1634,14 @@ int vmp_mlp_gauss_head_bwd(const float* x, const float* g_out1, const float* g_o
                            const float* b0, const float* W1, const float* b1, const float* W2, const float* b2, const float* Ws,
                            const float* bs1, const float* bs2, int64_t R, int L, int Dy, int U, float* dx, float* dparams,
                            void* ws, size_t ws_bytes, void* stream) {
-    return mlp_gauss_bwd_impl("vmp_mlp_gauss_head_bwd", var_scale, false, x, g_out1, g_out2, W0, b0, W1, b1, W2, b2, Ws, bs1, bs2, R, L, Dy, U,
+    return mlp_gauss_bwd_impl("vmp_mlp_gauss_head_bwd", var_scale, false, x, g_out1, g_out2, DecNet{W0, b0, W1, b1, W2, b2, Ws, bs1, bs2, L, Dy, U}, R,
                               dx, dparams, ws, ws_bytes, stream);
 }
 
 // ---- round 6: the minibatch training step reduces the parameter partials inside its ONE closing launch (vmp_svae_step_final,
 // vmp_step.hip); these entry points run the fused MLP backward kernel alone and leave (vmp_decoder_bwd_blocks(rows), PW) fp32
 // partials in `ws`.
-int vmp_decoder_bwd_blocks(int64_t rows) { return rows > 0 ? dec_bwd_blocks((long long)rows) : 0; }
+int vmp_decoder_bwd_blocks(int64_t rows) { return rows > 0 ? dec_plan(DEC_BWD, rows, 1, 1, 1).blocks : 0; }     // (the grid depends on the rows alone)
 
 int vmp_decoder_elbo_lazy(const float* x, const float* y, const float* log_z, float sigma, const float* W0, const float* b0,
                           const float* W1, const float* b1, const float* W2, const float* b2, const float* Ws, const float* bs1,
@@ -1656,16 +1655,16 @@ int vmp_decoder_elbo_lazy(const float* x, const float* y, const float* log_z, fl
         set_error("vmp_decoder_elbo_lazy: N = %lld, K = %d, S = %d", (long long)N, K, S);
         return VMP_E_DIM;
     }
-    return decoder_loglike_bwd_impl("vmp_decoder_elbo_lazy", -sigma * 0.5f / (float)S, nullptr, 0, true, x, y, log_z, W0, b0, W1, b1, W2, b2,
-                                    Ws, bs1, bs2, N, K, S, L, Dy, U, dx, nullptr, ll, ws, ws_bytes, stream);
+    return decoder_loglike_bwd_impl("vmp_decoder_elbo_lazy", -sigma * 0.5f / (float)S, nullptr, 0, true, x, y, log_z, DecNet{W0, b0, W1, b1, W2, b2, Ws, bs1, bs2, L, Dy, U},
+                                    N, K, S, dx, nullptr, ll, ws, ws_bytes, stream);
 }
 
 int vmp_mlp_gauss_head_bwd_lazy(const float* x, const float* g_out1, const float* g_out2, float var_scale, const float* W0,
                                 const float* b0, const float* W1, const float* b1, const float* W2, const float* b2,
                                 const float* Ws, const float* bs1, const float* bs2, int64_t R, int L, int Dy, int U, float* dx,
                                 void* ws, size_t ws_bytes, void* stream) {
-    return mlp_gauss_bwd_impl("vmp_mlp_gauss_head_bwd_lazy", var_scale, true, x, g_out1, g_out2, W0, b0, W1, b1, W2, b2, Ws, bs1, bs2, R, L,
-                              Dy, U, dx, nullptr, ws, ws_bytes, stream);
+    return mlp_gauss_bwd_impl("vmp_mlp_gauss_head_bwd_lazy", var_scale, true, x, g_out1, g_out2, DecNet{W0, b0, W1, b1, W2, b2, Ws, bs1, bs2, L, Dy, U}, R,
+                              dx, nullptr, ws, ws_bytes, stream);
 }
 
 }  // extern "C"

@@ -13,12 +13,8 @@ using namespace vmp;
 namespace {
 
 // L is a template parameter everywhere: with run-time loop bounds the per-thread matrices live in scratch memory and
-// every element access is a dependent round trip (measured: 50 us per launch instead of a few).
-#define PREP_DISPATCH_L(L, CALL)                                                     \
-    switch (L) {                                                                     \
-        case 1: CALL(1); break; case 2: CALL(2); break; case 3: CALL(3); break; case 4: CALL(4); break; \
-        case 5: CALL(5); break; case 6: CALL(6); break; case 7: CALL(7); break; default: CALL(8); break; \
-    }
+// every element access is a dependent round trip (measured: 50 us per launch instead of a few).  The entry points refuse an L
+// outside 1..8 (prep_check) before they dispatch on it with VMP_SWITCH_DIM.
 
 // Block per component, lane (i, j) per matrix element as in phi_prep_kernel: the two digammas run side by side in lanes 0
 // and 1, the Cholesky factor is built column by column in LDS (rows in parallel), the columns of its inverse in parallel.
@@ -173,9 +169,7 @@ int vmp_svae_phi_prep_fwd(const float* mu_k, const float* L_raw, const float* pi
     if (!mu_k || !L_raw || !pi_raw || !Lk || !P || !bias) { set_error("vmp_svae_phi_prep_fwd: NULL argument"); return VMP_E_BADARG; }
     PhiArgs a{};
     a.mu = mu_k; a.Lraw = L_raw; a.piraw = pi_raw; a.Lk = Lk; a.P = P; a.bias = bias; a.K = K; a.L = L;
-#define PREP_CALL(LL) hipLaunchKernelGGL((phi_prep_kernel<LL, false>), dim3(K), dim3(PREP_THREADS), 0, static_cast<hipStream_t>(stream), a)
-    PREP_DISPATCH_L(L, PREP_CALL)
-#undef PREP_CALL
+    VMP_SWITCH_DIM(L, LL, hipLaunchKernelGGL((phi_prep_kernel<LL, false>), dim3(K), dim3(PREP_THREADS), 0, static_cast<hipStream_t>(stream), a));
     return check_launch("vmp_svae_phi_prep_fwd");
 }
 
@@ -189,9 +183,7 @@ int vmp_svae_phi_prep_bwd(const float* mu_k, const float* L_raw, const float* pi
     PhiArgs a{};
     a.mu = mu_k; a.Lraw = L_raw; a.piraw = pi_raw; a.g_hk = g_hk; a.g_P = g_P; a.g_bias = g_bias;
     a.g_mu = g_mu; a.g_Lraw = g_Lraw; a.g_piraw = g_piraw; a.K = K; a.L = L;
-#define PREP_CALL(LL) hipLaunchKernelGGL((phi_prep_kernel<LL, true>), dim3(K), dim3(PREP_THREADS), 0, static_cast<hipStream_t>(stream), a)
-    PREP_DISPATCH_L(L, PREP_CALL)
-#undef PREP_CALL
+    VMP_SWITCH_DIM(L, LL, hipLaunchKernelGGL((phi_prep_kernel<LL, true>), dim3(K), dim3(PREP_THREADS), 0, static_cast<hipStream_t>(stream), a));
     return check_launch("vmp_svae_phi_prep_bwd");
 }
 
@@ -219,9 +211,7 @@ int vmp_svae_bwd_reduce_prep(const float* partials, int nblk, const float* mu_k,
     }
     PhiArgs a{};
     a.mu = mu_k; a.Lraw = L_raw; a.piraw = pi_raw; a.g_mu = g_mu; a.g_Lraw = g_Lraw; a.g_piraw = g_piraw; a.K = K; a.L = L; a.logpi = logpi;
-#define PREP_CALL(LL) hipLaunchKernelGGL((bwd_reduce_prep_kernel<LL>), dim3(K), dim3(64 * RED_GROUPS), 0, static_cast<hipStream_t>(stream), a, partials, nblk)
-    PREP_DISPATCH_L(L, PREP_CALL)
-#undef PREP_CALL
+    VMP_SWITCH_DIM(L, LL, hipLaunchKernelGGL((bwd_reduce_prep_kernel<LL>), dim3(K), dim3(64 * RED_GROUPS), 0, static_cast<hipStream_t>(stream), a, partials, nblk));
     return check_launch("vmp_svae_bwd_reduce_prep");
 }
 
@@ -230,9 +220,7 @@ int vmp_svae_theta_pack(const float* alpha, const float* A, const float* b, cons
     if (int e = prep_check("vmp_svae_theta_pack", K, L)) return e;
     if (!alpha || !A || !b || !beta || !v_hat || !m || !W || !kappa) { set_error("vmp_svae_theta_pack: NULL argument"); return VMP_E_BADARG; }
     ThetaArgs a{alpha, A, b, beta, v_hat, m, W, kappa, K, L};
-#define PREP_CALL(LL) hipLaunchKernelGGL((theta_pack_kernel<LL>), dim3(K), dim3(PREP_THREADS), 0, static_cast<hipStream_t>(stream), a)
-    PREP_DISPATCH_L(L, PREP_CALL)
-#undef PREP_CALL
+    VMP_SWITCH_DIM(L, LL, hipLaunchKernelGGL((theta_pack_kernel<LL>), dim3(K), dim3(PREP_THREADS), 0, static_cast<hipStream_t>(stream), a));
     return check_launch("vmp_svae_theta_pack");
 }
 
@@ -247,9 +235,7 @@ int vmp_svae_prep_fwd2(const float* mu_k, const float* L_raw, const float* pi_ra
     PhiArgs a{};
     a.mu = mu_k; a.Lraw = L_raw; a.piraw = pi_raw; a.Lk = Lk; a.P = P; a.bias = bias; a.K = K; a.L = L; a.logpi_out = logpi;
     ThetaArgs t{alpha, A, b, beta, v_hat, m, W, kappa, K, L};
-#define PREP_CALL(LL) hipLaunchKernelGGL((prep_both_kernel<LL>), dim3(2 * K), dim3(PREP_THREADS), 0, static_cast<hipStream_t>(stream), a, t)
-    PREP_DISPATCH_L(L, PREP_CALL)
-#undef PREP_CALL
+    VMP_SWITCH_DIM(L, LL, hipLaunchKernelGGL((prep_both_kernel<LL>), dim3(2 * K), dim3(PREP_THREADS), 0, static_cast<hipStream_t>(stream), a, t));
     return check_launch("vmp_svae_prep_fwd");
 }
 

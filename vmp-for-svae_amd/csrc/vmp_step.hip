@@ -399,9 +399,7 @@ XLayout exchange_layout(int K, int L, int enc_words, int dec_words, bool smm) {
 
 template <bool SMM>
 void step_final_dispatch(int L, unsigned blocks, void* stream, const FinArgs& a) {
-#define FIN_CALL(LL) case LL: hipLaunchKernelGGL((step_final_kernel<LL, SMM>), dim3(blocks), dim3(FIN_THREADS), 0, static_cast<hipStream_t>(stream), a); break
-    switch (L) { FIN_CALL(1); FIN_CALL(2); FIN_CALL(3); FIN_CALL(4); FIN_CALL(5); FIN_CALL(6); FIN_CALL(7); default: FIN_CALL(8); }
-#undef FIN_CALL
+    VMP_SWITCH_DIM(L, LL, hipLaunchKernelGGL((step_final_kernel<LL, SMM>), dim3(blocks), dim3(FIN_THREADS), 0, static_cast<hipStream_t>(stream), a));
 }
 
 template <class T>

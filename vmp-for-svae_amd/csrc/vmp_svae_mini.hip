@@ -355,12 +355,8 @@ namespace vmp {
 int svae_bwd1_launch(const EBwdArgs& a, int L, int ntiles, int P, bool tail, bool student, void* stream) {
     if (student && !tail) { set_error("svae_estep_bwd1_kernel: Student-t theta is compiled with the tail only"); return VMP_E_BADARG; }
     // student: the theta half of every partial row is written
-#define BWD1_CASE(LL) case LL: return student ? launch_bwd1<LL, true, true>(a, ntiles, P, stream) \
-                                   : tail ? launch_bwd1<LL, true>(a, ntiles, P, stream) : launch_bwd1<LL, false>(a, ntiles, P, stream)
-    switch (L) {
-        BWD1_CASE(1); BWD1_CASE(2); BWD1_CASE(3); BWD1_CASE(4); BWD1_CASE(5); BWD1_CASE(6); BWD1_CASE(7); BWD1_CASE(8);
-        default: return -1;
-    }
-#undef BWD1_CASE
+    VMP_SWITCH_DIM(L, LL, return student ? launch_bwd1<LL, true, true>(a, ntiles, P, stream)
+                                 : tail ? launch_bwd1<LL, true>(a, ntiles, P, stream) : launch_bwd1<LL, false>(a, ntiles, P, stream));
+    return -1;                                // an L outside 1..8
 }
 }  // namespace vmp

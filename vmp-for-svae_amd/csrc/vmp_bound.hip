@@ -14,48 +14,30 @@
 //
 // Streaming kernel: the lane map of vmp_mix_stream.h - lane l = (i16 = l & 15, kk = l >> 4) owns component i16 + 16 t of every tile
 // and the data row n4 + kk; a wave walks a contiguous range of rows - and the row sum of that header: no atomics, one geometry
-// whichever outputs are requested, bit-identical from run to run.  The cell is the part of fit_cell (vmp_missfit.hip) that log rho
+// whichever outputs are requested, bit-identical from run to run.  The cell is the part of fit_cell (vmp_fit_cell.h) that log rho
 // needs, in the same operations: the factor and the forward substitution, no back-substitution, no xhat, no inverse; without a mask
 // there is nothing to factor and log rho = c - 1/2 d^T Lbar d.  What a missing slot of x holds never enters arithmetic.
 // K-sized kernel: one thread per component, fp64 inside; the sums over k are taken by one thread in k order.
-#include "vmp_mix_stream.h"
+#include "vmp_fit_cell.h"
 
 using namespace vmp;
 
 namespace {
 
+// not the FIT_* geometry of the two fits: no moments to flush, so more and smaller blocks (that of vmp_impute.hip)
 constexpr int BND_NW = 4;                 // waves per block
 constexpr int BND_MAX_BLOCKS = 2048;      // 8 waves per SIMD on 256 CUs
 constexpr int BND_ROWS_PER_BLOCK = 64 * BND_NW;       // below that a block is not worth its launch slot
 
 inline int bound_blocks(int64_t N) { return stream_blocks(N, BND_ROWS_PER_BLOCK, BND_MAX_BLOCKS); }
 
-// the fit pack of vmp_missfit.hip: [ m_k (D) | Lbar_k lower, row-major packed (D(D+1)/2) | c_k ]
-template <int D>
-struct BGeo {
-    static constexpr int TRI  = D * (D + 1) / 2;
-    static constexpr int C    = D + TRI;
-    static constexpr int PACK = C + 1;
-    static constexpr int STRIDE = PACK | 1;        // LDS stride: odd, so that the 16 components of a tile fall into 16 banks
-};
-
-template <int D>
-struct BoundParams {
-    float mu[D], lam[BGeo<D>::TRI], c;
-    __device__ __forceinline__ void load(const float* src) {
-        using G = BGeo<D>;
-#pragma unroll
-        for (int d = 0; d < D; ++d) mu[d] = src[d];
-#pragma unroll
-        for (int i = 0; i < G::TRI; ++i) lam[i] = src[D + i];
-        c = src[G::C];
-    }
-    __device__ __forceinline__ float L(int i, int j) const { return lam[i >= j ? i * (i + 1) / 2 + j : j * (j + 1) / 2 + i]; }
-};
+// The two cells below are fit_cell_full and fit_cell (vmp_fit_cell.h) without the outputs that log rho does not need.  Calling those
+// with the outputs dropped computes the same bits, but the compiler orders the instructions of 26 of the 32 bound_kernel forms
+// differently (profiles/NOTES_mix_fit_shared.md), so the text stays here, as does the row load with its hoisted `vec`.
 
 // complete row: c - 1/2 d^T Lbar d, the quadratic form over the lower triangle (the diagonal halved, the rest counted once)
 template <int D>
-__device__ __forceinline__ float bound_cell_full(const BoundParams<D>& p, const float (&x)[D]) {
+__device__ __forceinline__ float bound_cell_full(const FitParams<D>& p, const float (&x)[D]) {
     float d[D];
 #pragma unroll
     for (int i = 0; i < D; ++i) d[i] = x[i] - p.mu[i];
@@ -71,11 +53,11 @@ __device__ __forceinline__ float bound_cell_full(const BoundParams<D>& p, const 
     return p.c - h;
 }
 
-// partly observed row: fit_cell of vmp_missfit.hip up to |y|^2 - the factor of A~ = M Lbar M + (I - M), sum log R_ii from its pivots,
+// partly observed row: fit_cell of vmp_fit_cell.h up to |y|^2 - the factor of A~ = M Lbar M + (I - M), sum log R_ii from its pivots,
 // the forward substitution y = R^-1 t - in the same operations
 template <int D>
-__device__ __forceinline__ float bound_cell_masked(const BoundParams<D>& p, const float (&x)[D], const bool (&miss)[D]) {
-    using G = BGeo<D>;
+__device__ __forceinline__ float bound_cell_masked(const FitParams<D>& p, const float (&x)[D], const bool (&miss)[D]) {
+    using G = FitGeo<D>;
     float dt[D], v[D], A[G::TRI], rd[D], piv[D];
 #pragma unroll
     for (int d = 0; d < D; ++d) dt[d] = miss[d] ? 0.f : x[d] - p.mu[d];
@@ -140,7 +122,7 @@ struct BoundArgs {
 
 template <int D, int KTMAX, bool MASKED>
 __global__ __launch_bounds__(BND_NW * WAVE) void bound_kernel(BoundArgs a) {
-    using G = BGeo<D>;
+    using G = FitGeo<D>;
     __shared__ float lds[KTMAX * 16 * G::STRIDE];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -149,7 +131,7 @@ __global__ __launch_bounds__(BND_NW * WAVE) void bound_kernel(BoundArgs a) {
 
     for (int i = threadIdx.x; i < a.K * G::PACK; i += BND_NW * WAVE) lds[(i / G::PACK) * G::STRIDE + i % G::PACK] = a.pack[i];
     __syncthreads();
-    BoundParams<D> p;
+    FitParams<D> p;
     if constexpr (KTMAX == 1) p.load(lds + (i16 < a.K ? i16 : 0) * G::STRIDE);   // lanes beyond K: a readable component, its term forced to -inf
 
     const long long g = (long long)blockIdx.x * BND_NW + wave;

@@ -20,7 +20,7 @@
 // (K = 64, D = 8: 14.6 KB).  K <= 16: the lane's component is resident in its VGPRs, loaded once per kernel; only G_k[D_o] is read
 // from LDS per cell.  K > 16: the lane reloads its component per tile and walks its tiles with a lane-local online log-sum-exp that rescales its running sum_k e_k xhat^(k); the 16 lanes are combined once per row
 // (row16_max, then D + 1 row16_sum).  The row sum is the deterministic one of vmp_mix_stream.h.
-#include "vmp_mix_stream.h"
+#include "vmp_impute_pack.h"
 
 using namespace vmp;
 
@@ -33,23 +33,8 @@ constexpr int IMP_ROWS_PER_BLOCK = 64 * IMP_NW;
 inline int impute_blocks(int64_t N) { return stream_blocks(N, IMP_ROWS_PER_BLOCK, IMP_MAX_BLOCKS); }
 
 // ---------------------------------------------------------------------------------------------------------
-// impute packs:  [ mu_k (D) | Lambda_k lower, row-major packed (D(D+1)/2) | log w | nu | log det Lambda | 1 / nu | G_k[0..D] ]
-//   G_k[j] = lgamma((nu + j) / 2) - lgamma(nu / 2) - (j / 2) log(pi nu)        (natural-log units)
+// impute packs (layout: vmp_impute_pack.h)
 // ---------------------------------------------------------------------------------------------------------
-template <int D>
-struct IGeo {
-    static constexpr int TRI  = D * (D + 1) / 2;
-    static constexpr int LW   = D + TRI;           // log w
-    static constexpr int NU   = LW + 1;
-    static constexpr int LDET = LW + 2;
-    static constexpr int INU  = LW + 3;
-    static constexpr int G    = LW + 4;
-    static constexpr int PACK = G + D + 1;
-    static constexpr int STRIDE = PACK | 1;        // LDS stride: odd, so that the 16 components of a tile fall into 16 banks
-};
-
-inline int impute_pack_words(int D) { return 2 * D + D * (D + 1) / 2 + 5; }
-
 struct ImputePackArgs {
     int K;
     const float *w, *beta, *m, *S, *nu;     // NIW: alpha, beta, m, C, v;  explicit: log_w, -, mu, sigma, nu
@@ -59,7 +44,7 @@ struct ImputePackArgs {
 // pack row of a component with scale matrix S / scale (precision scale S^-1), log weight lw and nu degrees of freedom
 template <int D>
 __device__ __forceinline__ void write_impute_pack(const ImputePackArgs& a, int k, double scale, double lw, double nu, bool ok) {
-    using G = IGeo<D>;
+    using G = ImputeGeo<D>;
     const double PI = 3.14159265358979323846;
     const float qnan = __builtin_nanf("");
     double W[D * D], sumlog;
@@ -115,20 +100,6 @@ struct ImputeArgs {
     int vec_in, vec_out;  // x / x_out 16-byte aligned
 };
 
-template <int D>
-struct ImputeParams {
-    float mu[D], lam[IGeo<D>::TRI], lw, nu, ldet, inu;          // G[] stays in LDS: it is indexed by the row's D_o
-    __device__ __forceinline__ void load(const float* src) {
-        using G = IGeo<D>;
-#pragma unroll
-        for (int d = 0; d < D; ++d) mu[d] = src[d];
-#pragma unroll
-        for (int i = 0; i < G::TRI; ++i) lam[i] = src[D + i];
-        lw = src[G::LW]; nu = src[G::NU]; ldet = src[G::LDET]; inu = src[G::INU];
-    }
-    __device__ __forceinline__ float L(int i, int j) const { return lam[i >= j ? i * (i + 1) / 2 + j : j * (j + 1) / 2 + i]; }
-};
-
 // One (row, component) cell: the term l_k and the conditional location xh[] (mu - z; meaningful in the missing slots only);
 // g = G_k[n_obs].  x[] holds whatever the caller's buffer holds in the missing slots: it is read through the select only.
 template <int D>
@@ -148,7 +119,7 @@ __device__ __forceinline__ float impute_cell(const ImputeParams<D>& p, const flo
         qo = fmaf(dt[i], s, qo);                 // dt[i] = 0 in the missing rows
     }
     // A~ = M Lambda M + (I - M), lower Cholesky in place (off-diagonal entries; the diagonal is kept as 1 / R_jj)
-    float A[IGeo<D>::TRI], rd[D], piv[D];
+    float A[ImputeGeo<D>::TRI], rd[D], piv[D];
 #pragma unroll
     for (int i = 0; i < D; ++i)
 #pragma unroll
@@ -205,7 +176,7 @@ __device__ __forceinline__ float impute_cell(const ImputeParams<D>& p, const flo
 // select chain over registers is turned into an indexed private-memory load by the compiler: scratch inside the row loop).
 template <int D, int KTMAX>
 __global__ __launch_bounds__(IMP_NW * WAVE) void impute_kernel(ImputeArgs a) {
-    using G = IGeo<D>;
+    using G = ImputeGeo<D>;
     __shared__ float lds[KTMAX * 16 * G::STRIDE];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);

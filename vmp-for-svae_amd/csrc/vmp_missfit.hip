@@ -23,32 +23,14 @@
 // data row n4 + kk (vmp_impute.hip).  K <= 16: the component is resident in VGPRs and a cell is evaluated once.  K > 16: a chunk of
 // rows is walked twice - first all tiles of a row for the softmax (r, log r and x_fill are written), then tile by tile with the cell
 // evaluated again and r read back (the lane's own store), so that one set of accumulators serves every tile.
-#include "vmp_mix_stream.h"
+//
+// The cell (fit_cell), the moments (fit_moments), the flush, the row load, the body of the reduction and the block geometry (FIT_*)
+// are in vmp_fit_cell.h, which vmp_wfit.hip shares (vmp_bound.hip: the pack's geometry and registers).
+#include "vmp_fit_cell.h"
 
 using namespace vmp;
 
 namespace {
-
-constexpr int FIT_NW = 4;                 // waves per block
-constexpr int FIT_MAX_BLOCKS = 512;
-constexpr int FIT_CHUNK = 128;            // rows of a wave between two fp32 -> fp64 flushes: the cadence of vmp_mix.hip's pass_kernel (VMP_MOM_FLUSH = 2 tiles of 64 rows)
-constexpr int FIT_RED_GROUPS = 16;        // wave groups of the reduction block
-
-inline int fit_blocks(int64_t N) { return stream_blocks(N, (int64_t)FIT_NW * FIT_CHUNK, FIT_MAX_BLOCKS); }
-
-// fit pack: [ m_k (D) | Lbar_k = v_k C_k^-1 lower, row-major packed (D(D+1)/2) | c_k ]
-template <int D>
-struct FGeo {
-    static constexpr int TRI  = D * (D + 1) / 2;
-    static constexpr int C    = D + TRI;
-    static constexpr int PACK = C + 1;
-    static constexpr int STRIDE = PACK | 1;        // LDS stride: odd, so that the 16 components of a tile fall into 16 banks
-    static constexpr int MW   = 1 + D + TRI;       // moment words per component: Nk | s1 (D) | s2 lower packed
-    static constexpr int SW   = 2 + D + D * D;     // public stats words
-};
-
-inline int fit_pack_words(int D) { return D + D * (D + 1) / 2 + 1; }
-inline int fit_moment_words(int D) { return 1 + D + D * (D + 1) / 2; }
 
 struct FitPackArgs {
     int K;
@@ -60,7 +42,7 @@ struct FitPackArgs {
 // log rho as compute_log_pi / compute_expct_log_det_prec give it (gmm.py:117-138, the det <= 1e-20 guard included).
 template <int D>
 __global__ __launch_bounds__(WAVE) void fit_pack_kernel(FitPackArgs a) {
-    using G = FGeo<D>;
+    using G = FitGeo<D>;
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= a.K) return;
     const float qnan = __builtin_nanf("");
@@ -96,137 +78,9 @@ struct FitArgs {
     int vec_in, vec_out;  // x / x_fill 16-byte aligned
 };
 
-template <int D>
-struct FitParams {
-    float mu[D], lam[FGeo<D>::TRI], c;
-    __device__ __forceinline__ void load(const float* src) {
-        using G = FGeo<D>;
-#pragma unroll
-        for (int d = 0; d < D; ++d) mu[d] = src[d];
-#pragma unroll
-        for (int i = 0; i < G::TRI; ++i) lam[i] = src[D + i];
-        c = src[G::C];
-    }
-    __device__ __forceinline__ float L(int i, int j) const { return lam[i >= j ? i * (i + 1) / 2 + j : j * (j + 1) / 2 + i]; }
-};
-
-// One (row, component) cell: log rho; dh[] = xhat - m_k (x_o - m_k,o in the observed slots, -R^-T y in the missing ones); A[] the
-// off-diagonal entries of the Cholesky factor of A~ and rd[] its reciprocal diagonal, for fit_moments.
-template <int D>
-__device__ __forceinline__ float fit_cell(const FitParams<D>& p, const float (&x)[D], const bool (&miss)[D], float (&dh)[D],
-                                          float (&A)[FGeo<D>::TRI], float (&rd)[D]) {
-    float dt[D], v[D];
-#pragma unroll
-    for (int d = 0; d < D; ++d) dt[d] = miss[d] ? 0.f : x[d] - p.mu[d];
-    float qo = 0.f;
-#pragma unroll
-    for (int i = 0; i < D; ++i) {
-        float s = p.L(i, 0) * dt[0];
-#pragma unroll
-        for (int j = 1; j < D; ++j) s = fmaf(p.L(i, j), dt[j], s);
-        v[i] = miss[i] ? s : 0.f;
-        qo = fmaf(dt[i], s, qo);                 // dt[i] = 0 in the missing rows
-    }
-    float piv[D];
-#pragma unroll
-    for (int i = 0; i < D; ++i)
-#pragma unroll
-        for (int j = 0; j <= i; ++j) A[i * (i + 1) / 2 + j] = (miss[i] && miss[j]) ? p.lam[i * (i + 1) / 2 + j] : (i == j ? 1.f : 0.f);
-#pragma unroll
-    for (int j = 0; j < D; ++j) {
-        float s = A[j * (j + 1) / 2 + j];
-#pragma unroll
-        for (int q = 0; q < j; ++q) s = fmaf(-A[j * (j + 1) / 2 + q], A[j * (j + 1) / 2 + q], s);
-        piv[j] = s;
-        rd[j] = __builtin_amdgcn_rsqf(s);
-#pragma unroll
-        for (int i = j + 1; i < D; ++i) {
-            float t = A[i * (i + 1) / 2 + j];
-#pragma unroll
-            for (int q = 0; q < j; ++q) t = fmaf(-A[i * (i + 1) / 2 + q], A[j * (j + 1) / 2 + q], t);
-            A[i * (i + 1) / 2 + j] = t * rd[j];
-        }
-    }
-    float slog = 0.f;                            // sum_i log R_ii = 1/2 sum log pivot, two pivots per logarithm
-#pragma unroll
-    for (int j = 0; j + 1 < D; j += 2) slog += logf(piv[j] * piv[j + 1]);
-    if constexpr (D % 2) slog += logf(piv[D - 1]);
-    slog *= 0.5f;
-    float yy = 0.f;                              // y = R^-1 t (in v), |y|^2, z = R^-T y (in v)
-#pragma unroll
-    for (int i = 0; i < D; ++i) {
-        float s = v[i];
-#pragma unroll
-        for (int q = 0; q < i; ++q) s = fmaf(-A[i * (i + 1) / 2 + q], v[q], s);
-        v[i] = s * rd[i];
-        yy = fmaf(v[i], v[i], yy);
-    }
-#pragma unroll
-    for (int i = D - 1; i >= 0; --i) {
-        float s = v[i];
-#pragma unroll
-        for (int q = i + 1; q < D; ++q) s = fmaf(-A[q * (q + 1) / 2 + i], v[q], s);
-        v[i] = s * rd[i];
-    }
-#pragma unroll
-    for (int d = 0; d < D; ++d) dh[d] = dt[d] - v[d];        // one of the two is an exact zero
-    float q = qo - yy;
-    q = q < 0.f ? 0.f : q;                       // rounding of the difference; a NaN stays a NaN
-    return (p.c - slog) - 0.5f * q;
-}
-
-// acc += r [ 1 | dh | dh dh^T + Cov ]:  W = R^-1 in place of the factor (column by column: an entry of R is last read when its own
-// slot is written), Cov = W^T W with the observed diagonal (exactly 1) dropped.
-template <int D>
-__device__ __forceinline__ void fit_moments(const float (&dh)[D], const bool (&miss)[D], float (&A)[FGeo<D>::TRI], const float (&rd)[D],
-                                            float r, float (&acc)[FGeo<D>::MW]) {
-#pragma unroll
-    for (int j = 0; j < D; ++j)
-#pragma unroll
-        for (int i = j + 1; i < D; ++i) {
-            float s = A[i * (i + 1) / 2 + j] * rd[j];
-#pragma unroll
-            for (int q = j + 1; q < i; ++q) s = fmaf(A[i * (i + 1) / 2 + q], A[q * (q + 1) / 2 + j], s);
-            A[i * (i + 1) / 2 + j] = -s * rd[i];
-        }
-    acc[0] += r;
-#pragma unroll
-    for (int d = 0; d < D; ++d) acc[1 + d] = fmaf(r, dh[d], acc[1 + d]);
-#pragma unroll
-    for (int i = 0; i < D; ++i)
-#pragma unroll
-        for (int j = 0; j <= i; ++j) {
-            float cv = (i == j ? rd[i] : A[i * (i + 1) / 2 + j]) * rd[i];                 // q = i: W_ii W_ij
-#pragma unroll
-            for (int q = i + 1; q < D; ++q) cv = fmaf(A[q * (q + 1) / 2 + i], A[q * (q + 1) / 2 + j], cv);
-            if (i == j) cv = miss[i] ? cv : 0.f;
-            acc[1 + D + i * (i + 1) / 2 + j] = fmaf(r, fmaf(dh[i], dh[j], cv), acc[1 + D + i * (i + 1) / 2 + j]);
-        }
-}
-
-// the four lanes that own component k add their sums; lane kk = 0 adds the result to the wave's fp64 words (first: replaces them)
-template <int D>
-__device__ __forceinline__ void fit_flush(float (&acc)[FGeo<D>::MW], double* __restrict__ dst, bool first, bool owner) {
-#pragma unroll
-    for (int i = 0; i < FGeo<D>::MW; ++i) {
-        const float s = rows4_sum(acc[i]);
-        if (owner) dst[i] = (first ? 0.0 : dst[i]) + (double)s;
-        acc[i] = 0.f;
-    }
-}
-
-template <int D>
-__device__ __forceinline__ int fit_load_row(const FitArgs& a, long long nr, float (&x)[D], bool (&miss)[D]) {
-    load_row<D>(a.x + nr * D, x, a.vec_in != 0);
-    int n_obs = 0;
-#pragma unroll
-    for (int d = 0; d < D; ++d) { miss[d] = a.mask[nr * D + d] != 0; n_obs += miss[d] ? 0 : 1; }
-    return n_obs;
-}
-
 template <int D, int KTMAX>
 __global__ __launch_bounds__(FIT_NW * WAVE) void fit_kernel(FitArgs a) {
-    using G = FGeo<D>;
+    using G = FitGeo<D>;
     __shared__ float lds[KTMAX * 16 * G::STRIDE];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -258,7 +112,7 @@ __global__ __launch_bounds__(FIT_NW * WAVE) void fit_kernel(FitArgs a) {
             const long long nr = valid ? n : c1 - 1;                         // rows past the range: a row of the range, discarded
             float x[D];
             bool miss[D];
-            fit_load_row<D>(a, nr, x, miss);
+            fit_load_row<D, true>(a, nr, x, miss);
 
             // lane-local online log-sum-exp over the lane's tiles: ml = running maximum, s = sum e, ax = sum e xhat
             float ml = -INFINITY, s = 0.f, ax[D], lt[KTMAX], dh[D], A[G::TRI], rd[D];
@@ -322,7 +176,7 @@ __global__ __launch_bounds__(FIT_NW * WAVE) void fit_kernel(FitArgs a) {
                     const long long nr = valid ? n : c1 - 1;
                     float x[D], dh[D], A[G::TRI], rd[D];
                     bool miss[D];
-                    fit_load_row<D>(a, nr, x, miss);
+                    fit_load_row<D, true>(a, nr, x, miss);
                     fit_cell<D>(p, x, miss, dh, A, rd);
                     const float rk = (valid && k < a.K) ? a.r[n * a.K + k] : 0.f;      // the lane's own store of the first walk
                     fit_moments<D>(dh, miss, A, rd, rk, acc);
@@ -340,41 +194,10 @@ struct FitReduceArgs {
     int nwaves, K;
 };
 
-// One block per component: wave group j adds waves j, j + 16, ... in that order, the 16 group sums are added in group order, then
-// the shift by m_k (the fp32 words of the pack, exact in fp64) is undone:
-//   sx = s1 + Nk m,   sxx = s2 + s1 m^T + m s1^T + Nk m m^T.
+// the waves of the slab added in a fixed order and un-shifted by m_k: fit_unshift_reduce (vmp_fit_cell.h)
 template <int D>
 __global__ __launch_bounds__(FIT_RED_GROUPS * WAVE) void fit_reduce_kernel(FitReduceArgs a) {
-    using G = FGeo<D>;
-    __shared__ double part[FIT_RED_GROUPS][WAVE];
-    __shared__ double red[WAVE];
-    const int k = blockIdx.x, grp = threadIdx.x >> 6, i = threadIdx.x & 63;
-    double s = 0.0;
-    if (i < G::MW)
-        for (int w = grp; w < a.nwaves; w += FIT_RED_GROUPS) s += a.slab[((long long)w * a.K + k) * G::MW + i];
-    part[grp][i] = s;
-    __syncthreads();
-    if (grp == 0) {
-        double t = part[0][i];
-#pragma unroll
-        for (int j = 1; j < FIT_RED_GROUPS; ++j) t += part[j][i];
-        red[i] = t;
-    }
-    __syncthreads();
-    const int j = threadIdx.x;
-    if (j >= G::SW) return;
-    const float* pk = a.pack + k * G::PACK;
-    const double Nk = red[0];
-    double out;
-    if (j < 2) out = Nk;
-    else if (j < 2 + D) { const int d = j - 2; out = red[1 + d] + Nk * (double)pk[d]; }
-    else {
-        const int d = (j - 2 - D) / D, e = (j - 2 - D) % D;
-        const int hi = d > e ? d : e, lo = d > e ? e : d;
-        const double md = pk[d], me = pk[e];
-        out = red[1 + D + hi * (hi + 1) / 2 + lo] + red[1 + d] * me + md * red[1 + e] + Nk * md * me;
-    }
-    a.stats[(long long)k * G::SW + j] = out;
+    fit_unshift_reduce<D>(a);
 }
 
 template <int D>
@@ -418,7 +241,7 @@ int vmp_mixture_fit_pack(int D, int K, const float* alpha, const float* beta, co
 
 size_t vmp_mixture_fit_workspace_bytes(int64_t N, int D, int K) {
     if (D < 1 || D > VMP_MAX_D || K < 1 || K > VMP_MAX_K) return 0;
-    return (size_t)fit_blocks(N) * FIT_NW * K * fit_moment_words(D) * sizeof(double);      // the fp64 moments of every wave
+    return fit_slab_bytes(N, D, K);
 }
 
 int vmp_mixture_fit_pass(const float* x, const uint8_t* mask, int64_t N, int D, int K, const float* pack, float* r_out,
@@ -452,18 +275,9 @@ int vmp_mixture_fit_iterate(const float* x, const uint8_t* mask, int64_t N, int 
                             void* ws, size_t ws_bytes, int iterations, void* stream) {
     int rc = fit_pass_check("vmp_mixture_fit_iterate", x, mask, N, D, K, pack, r, ws, ws_bytes);
     if (rc) return rc;
-    if (iterations < 0) { set_error("vmp_mixture_fit_iterate: iterations must not be negative (got %d)", iterations); return VMP_E_BADARG; }
-    if (!alpha0 || !beta0 || !m0 || !C0 || !v0 || !alpha || !beta || !m || !C || !v || !stats) {
-        set_error("vmp_mixture_fit_iterate: null pointer (prior, posterior or stats)");
-        return VMP_E_BADARG;
-    }
-    for (int it = 0; it < iterations; ++it) {
-        rc = vmp_mix_finalize(stats, D, K, VMP_GMM, alpha0, beta0, m0, C0, v0, nullptr, alpha, beta, m, C, v, xbar, S, pi, nullptr, stream);
-        if (rc) return rc;
-        if ((rc = vmp_mixture_fit_pack(D, K, alpha, beta, m, C, v, pack, stream)) != 0) return rc;
-        if ((rc = vmp_mixture_fit_pass(x, mask, N, D, K, pack, r, logr, x_fill, stats, ws, ws_bytes, stream)) != 0) return rc;
-    }
-    return 0;
+    return fit_iterate("vmp_mixture_fit_iterate", "prior, posterior or stats", D, K, alpha0, beta0, m0, C0, v0, alpha, beta, m, C, v, xbar,
+                       S, pi, pack, stats, iterations, stream,
+                       [&] { return vmp_mixture_fit_pass(x, mask, N, D, K, pack, r, logr, x_fill, stats, ws, ws_bytes, stream); });
 }
 
 }  // extern "C"

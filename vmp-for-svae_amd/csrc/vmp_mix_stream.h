@@ -1,5 +1,7 @@
-// What the streaming mixture kernels share (vmp_score.hip, vmp_impute.hip, vmp_missfit.hip): the deterministic row sum and the
-// host-side geometry and refusals.  Each of the three files states its own feature's mathematics.
+// What the streaming mixture kernels share: the deterministic row sum and the host-side geometry and refusals.  Users: vmp_score.hip
+// and vmp_seed.hip directly; vmp_impute.hip and vmp_sample.hip through vmp_impute_pack.h (the impute pack); vmp_missfit.hip,
+// vmp_wfit.hip and vmp_bound.hip through vmp_fit_cell.h (the fit pack and its cell); vmp_diagfit.hip and vmp_diagscore.hip through
+// vmp_diag_stream.h (the diagonal row tile).  Each of the nine files states its own feature's mathematics.
 //
 // Lane map: lane l = (i16 = l & 15, kk = l >> 4) owns component k = i16 + 16 t of every component tile t and, per loop iteration,
 // the data row n + kk (the score kernel: two rows, n + kk and n + 4 + kk): the 16 lanes of a DPP row cover one data row, max and sum

@@ -39,7 +39,7 @@
 // s = s0 + i16 of its row: z is found for the 16 draws in turn (the draw's u_z is broadcast, the first k with cdf_k > u_z is a
 // row16 reduction), then each lane evaluates the cell of ITS z again for R, y, q and xhat - only cdf_k is kept per component - and
 // does the gamma draw and the R^-T solve on its own.  x == NULL (plain draws): the K-loop evaluates no cell, l_k = log w_k.
-#include "vmp_mix_stream.h"
+#include "vmp_impute_pack.h"
 #include "vmp_philox.h"
 
 using namespace vmp;
@@ -54,19 +54,6 @@ constexpr unsigned SAMPLE_TAG = 0x6d78a500u;
 constexpr unsigned SMP_B_Z = 0u, SMP_B_EPS = 1u, SMP_B_GAMMA = 16u;
 
 inline int sample_blocks(int64_t N) { return stream_blocks(N, SMP_ROWS_PER_BLOCK, SMP_MAX_BLOCKS); }
-
-// the impute pack of vmp_impute.hip
-template <int D>
-struct SGeo {
-    static constexpr int TRI  = D * (D + 1) / 2;
-    static constexpr int LW   = D + TRI;           // log w
-    static constexpr int NU   = LW + 1;
-    static constexpr int LDET = LW + 2;
-    static constexpr int INU  = LW + 3;
-    static constexpr int G    = LW + 4;
-    static constexpr int PACK = G + D + 1;
-    static constexpr int STRIDE = PACK | 1;        // LDS stride: odd, so that the 16 components of a tile fall into 16 banks
-};
 
 __device__ __forceinline__ void sample_philox(unsigned (&c)[4], unsigned long long row, unsigned s, unsigned b, unsigned long long seed) {
     c[0] = (unsigned)row; c[1] = (unsigned)(row >> 32); c[2] = s; c[3] = SAMPLE_TAG + b;
@@ -93,26 +80,12 @@ struct SampleArgs {
     int vec_in, vec_out;      // x / x_out 16-byte aligned
 };
 
-template <int D>
-struct SampleParams {
-    float mu[D], lam[SGeo<D>::TRI], lw, nu, ldet, inu;          // G[] stays in LDS: it is indexed by the row's D_o
-    __device__ __forceinline__ void load(const float* src) {
-        using G = SGeo<D>;
-#pragma unroll
-        for (int d = 0; d < D; ++d) mu[d] = src[d];
-#pragma unroll
-        for (int i = 0; i < G::TRI; ++i) lam[i] = src[D + i];
-        lw = src[G::LW]; nu = src[G::NU]; ldet = src[G::LDET]; inu = src[G::INU];
-    }
-    __device__ __forceinline__ float L(int i, int j) const { return lam[i >= j ? i * (i + 1) / 2 + j : j * (j + 1) / 2 + i]; }
-};
-
 // One (row, component) cell, the operations of impute_cell (vmp_impute.hip) in its order: returns l_k; q, the conditional location
 // xh[] (meaningful in the missing slots), the off-diagonal entries A[] of the Cholesky factor of A~ and its reciprocal diagonal rd[]
 // are what a draw needs of the chosen component (the K-loop uses l_k alone; the rest is dead code there).
 template <int D>
-__device__ __forceinline__ float sample_cell(const SampleParams<D>& p, const float (&x)[D], const bool (&miss)[D], int n_obs, float g,
-                                             float& q_out, float (&xh)[D], float (&A)[SGeo<D>::TRI], float (&rd)[D]) {
+__device__ __forceinline__ float sample_cell(const ImputeParams<D>& p, const float (&x)[D], const bool (&miss)[D], int n_obs, float g,
+                                             float& q_out, float (&xh)[D], float (&A)[ImputeGeo<D>::TRI], float (&rd)[D]) {
     float dt[D], v[D];
 #pragma unroll
     for (int d = 0; d < D; ++d) dt[d] = miss[d] ? 0.f : x[d] - p.mu[d];
@@ -217,7 +190,7 @@ __device__ __forceinline__ float sample_gamma(float a, float u_b, unsigned long 
 // The packs are staged in LDS once per block.  KTMAX = 1: K <= 16;  KTMAX = 4: the lane walks ceil(K / 16) tiles.
 template <int D, int KTMAX>
 __global__ __launch_bounds__(SMP_NW * WAVE) void sample_kernel(SampleArgs a) {
-    using G = SGeo<D>;
+    using G = ImputeGeo<D>;
     __shared__ float lds[KTMAX * 16 * G::STRIDE];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -257,7 +230,7 @@ __global__ __launch_bounds__(SMP_NW * WAVE) void sample_kernel(SampleArgs a) {
             const float* row = lds + (k < a.K ? k : 0) * G::STRIDE;
             float l = row[G::LW];
             if (cond) {
-                SampleParams<D> p;
+                ImputeParams<D> p;
                 p.load(row);
                 float q, xh[D], A[G::TRI], rd[D];
                 l = sample_cell<D>(p, x, miss, n_obs, row[G::G + n_obs], q, xh, A, rd);
@@ -312,7 +285,7 @@ __global__ __launch_bounds__(SMP_NW * WAVE) void sample_kernel(SampleArgs a) {
                     for (int d = 0; d < D; ++d) o[d] = miss[d] ? (bad ? __builtin_nanf("") : 0.f) : x[d];
                 } else {
                     const float* row = lds + z * G::STRIDE;
-                    SampleParams<D> p;
+                    ImputeParams<D> p;
                     p.load(row);
                     float q, xh[D], A[G::TRI], rd[D], w[D];
                     sample_cell<D>(p, x, miss, n_obs, 0.f, q, xh, A, rd);

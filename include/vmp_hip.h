@@ -632,6 +632,20 @@ int    vmp_svae_estep_bwd_n(const float* eta1, const float* eta2d, const float* 
                             const float* mk, const float* Wk, const float* nu, const float* x, const float* lz,
                             const float* Gx, const float* Glz, const float* GT, int64_t N, int K, int L, int S,
                             float* g_eta1, float* g_eta2d, float* partials, size_t partial_bytes, int nblk, void* stream);
+/* Host query, no launch and no device: the launch plan of the E-step kernels (fwd_plan / bwd_plan, csrc/vmp_svae.hip) for N rows.
+ * dir 0, forward: f0 = rng (in-kernel noise; 0: a noise tensor), f1 = the noise tensor is 16-byte aligned, f2 = in-kernel moments
+ * wanted (vmp_svae_estep_fwd_rng_epi with mom != NULL), f3 = the minibatch form may be used (0: vmp_svae_estep_fwd_rng_at).
+ *   out = [form: 0 none (no in-kernel-noise form / no in-kernel moments for the shape), 1 fwd1 (minibatch: one block per tile),
+ *   2 tile, 3 pst (per-pair staging), 4 pst2 (two pairs per flush), 5 chunked, 6 fwd3 (register-staged) | waves per block | blocks |
+ *   dynamic LDS bytes | cs: the LDS tile's cell stride (chunked: samples per chunk) | 0 | 0 | 0].
+ * dir 1, backward: f0 = Student-t theta, f1 = x and dLoss/dx are 16-byte aligned, f2 = nblk, the rows of the caller's partial
+ * buffer (0: what vmp_svae_bwd_blocks_for answers), f3 = 0.
+ *   out = [form: 0 none (nblk is neither vmp_svae_bwd_blocks_for nor vmp_svae_bwd_blocks), 1 bwd1 (minibatch: one block per tile),
+ *   2 ring, 3 generic, one tile per wave, 4 generic, streaming | partial rows | 1 when the form with the ELBO tail inside
+ *   (vmp_svae_estep_bwd_tail, or _tail_t for f0 = 1) covers the shape | 0 ...].
+ * Returns 0, or with out zeroed: VMP_E_BADARG (out NULL, no such dir, N < 1, S < 1, a flag outside 0 / 1, nblk < 0, f3 != 0 for
+ * dir 1), VMP_E_DIM (K, L outside the compiled range, S > 65536) - the sizes the entry points refuse.                        */
+int    vmp_svae_launch_plan(int dir, int64_t N, int K, int L, int S, int f0, int f1, int f2, int f3, int64_t* out);
 
 /* subsample_x (models/svae.py:122-151): z_ns ~ Cat(exp lz_n) and x_samples[n,s,:] = x[n, z_ns, s, :] for s < S_out
  * (the reference draws all S and keeps s = 0, svae.py:514).  The draw is the inverse CDF of the supplied uniform

@@ -2390,6 +2390,28 @@ int vmp_svae_estep_bwd_n(const float* eta1, const float* eta2d, const float* hk,
     return rc;
 }
 
+// what fwd_plan / bwd_plan decide, on the host alone (no launch, no device): the forms are the enumerators' values
+int vmp_svae_launch_plan(int dir, int64_t N, int K, int L, int S, int f0, int f1, int f2, int f3, int64_t out[8]) {
+    const char* what = "vmp_svae_launch_plan";
+    if (!out) { set_error("%s: null pointer", what); return VMP_E_BADARG; }
+    for (int i = 0; i < 8; ++i) out[i] = 0;
+    if (dir != 0 && dir != 1) { set_error("%s: dir %d", what, dir); return VMP_E_BADARG; }
+    const bool flags_ok = dir == 0 ? ((f0 | f1 | f2 | f3) & ~1) == 0 : ((f0 | f1) & ~1) == 0 && f2 >= 0 && f3 == 0;
+    if (!flags_ok) { set_error("%s: dir %d with flags %d, %d, %d, %d", what, dir, f0, f1, f2, f3); return VMP_E_BADARG; }
+    if (const int rc = check_sv(N, K, L, S)) return rc;
+    if (dir == 0) {
+        const FwdPlan p = fwd_plan(N, K, L, S, f0 != 0, f1 != 0, f2 != 0, f3 != 0);
+        const int64_t v[8] = {(int64_t)p.form, p.nw, p.grid, (int64_t)p.lds, p.cs, 0, 0, 0};
+        for (int i = 0; i < 8; ++i) out[i] = v[i];
+    } else {
+        const BwdPlan p = bwd_plan(N, K, L, S, f0 != 0, f1 != 0, f2);
+        out[0] = (int64_t)p.form;
+        out[1] = p.blocks;
+        out[2] = bwd1_covers(N, K, L, S, f0 != 0, true) ? 1 : 0;
+    }
+    return 0;
+}
+
 int vmp_svae_estep_bwd(const float* eta1, const float* eta2d, const float* hk, const float* Pk, const float* bias,
                        const float* mk, const float* Wk, const float* nu, const float* x, const float* lz, const float* Gx,
                        const float* Glz, const float* GT, int64_t N, int K, int L, int S, float* g_eta1, float* g_eta2d,

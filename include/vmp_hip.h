@@ -31,6 +31,7 @@ extern "C" {
 #define VMP_E_BADARG   (-1)   /* null pointer / non-positive size            */
 #define VMP_E_DIM      (-2)   /* D or K outside the compiled range           */
 #define VMP_E_WS       (-3)   /* workspace too small                         */
+#define VMP_E_NOIMPL   (-4)   /* no kernel of this form for these sizes      */
 
 #define VMP_MAX_D 8           /* latent / data dimension of the mixture (compiled range 1..8)  */
 #define VMP_MAX_K 64          /* mixture components                                             */
@@ -156,6 +157,26 @@ int    vmp_mix_iterate(const float* x, int64_t N, int D, int K, int flavour,
  * half | parallel block reduction | dynamic LDS bytes].  Returns 0, or what the pass would return and out zeroed: VMP_E_DIM,
  * VMP_E_BADARG (N < 1, a flavour that is neither, a combination no kernel exists for: a mask with VMP_SMM or with stats).  */
 int    vmp_mix_pass_plan(int64_t N, int D, int K, int flavour, int estep, int stats, int mask, int64_t* out);
+
+/* The fused pass of an iteration that nobody reads r from: vmp_mix_estep_fused without r_out, u_out and logr_out.  Within an
+ * iteration nothing reads them - vmp_mix_finalize_ws takes the partials in `ws`, the next pass forms r again from x and the new
+ * pack - so the kernel issues no store of them: per iteration the launch reads x and writes the partials, where the storing pass
+ * also writes N K floats of r (and of u).  Same launch plan, same rows per wave, same order: the partials are the bits
+ * vmp_mix_estep_fused leaves.  r (u) of the current pack, when wanted: vmp_mix_estep with the same pack and pivot, which gives the
+ * bits the fused pass would have stored.  Instances exist where the fused pass runs the XDL form (vmp_mix_pass_plan(.., 1, 1, 0):
+ * form 2, K <= 16); otherwise VMP_E_NOIMPL and nothing is launched - call vmp_mix_estep_fused.
+ * (The two names carry the vmp_mixture_ prefix of the newer entry points although they live beside vmp_mix_estep_fused: the set of
+ * vmp_mix_* symbols is closed - tests/test_abi.py holds every one of them to a table of NULL-pointer codes.)
+ * vmp_mixture_iterate_nostore: vmp_mix_iterate over this pass (no r, no u); everything either launch refuses is refused before the
+ * first one.  Errors (decided before any launch): VMP_E_DIM, VMP_E_BADARG (N < 1, x, pack or ws NULL, a flavour that is neither,
+ * iterations < 0), VMP_E_WS, VMP_E_NOIMPL.                                                                                     */
+int    vmp_mixture_estep_fused_nostore(const float* x, int64_t N, int D, int K, int flavour, const float* pack, const float* pivot,
+                                       void* ws, size_t ws_bytes, void* stream);
+int    vmp_mixture_iterate_nostore(const float* x, int64_t N, int D, int K, int flavour,
+                                   const float* alpha0, const float* beta0, const float* m0, const float* C0, const float* v0,
+                                   const float* kappa, const float* pivot,
+                                   float* alpha, float* beta, float* m, float* C, float* v, float* xbar, float* S, float* pi,
+                                   float* pack, void* ws, size_t ws_bytes, int iterations, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Mixture scoring (csrc/vmp_score.hip): held-out log predictive density of the pure mixtures in one streaming pass

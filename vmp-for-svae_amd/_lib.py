@@ -36,6 +36,9 @@ _SIGNATURES = {
     'vmp_mix_estep_accurate': (_c.c_int, [_P, _c.c_int64, _c.c_int, _c.c_int, _c.c_int, _P, _P, _P, _P, _P]),
     'vmp_mix_stats_ws': (_c.c_int, [_P, _P, _P, _P, _c.c_int64, _c.c_int, _c.c_int, _P, _c.c_size_t, _P]),
     'vmp_mix_iterate': (_c.c_int, [_P, _c.c_int64, _c.c_int, _c.c_int, _c.c_int] + [_P] * 7 + [_P] * 11 + [_P, _c.c_size_t, _c.c_int, _P]),
+    'vmp_mixture_estep_fused_nostore': (_c.c_int, [_P, _c.c_int64, _c.c_int, _c.c_int, _c.c_int, _P, _P, _P, _c.c_size_t, _P]),
+    'vmp_mixture_iterate_nostore': (_c.c_int, [_P, _c.c_int64, _c.c_int, _c.c_int, _c.c_int] + [_P] * 7 + [_P] * 9
+                                    + [_P, _c.c_size_t, _c.c_int, _P]),
     'vmp_mix_pass_plan': (_c.c_int, [_c.c_int64] + [_c.c_int] * 6 + [_P]),
     'vmp_mix_score_pack_niw': (_c.c_int, [_c.c_int, _c.c_int] + [_P] * 7),
     'vmp_mix_score_pack_t': (_c.c_int, [_c.c_int, _c.c_int] + [_P] * 6),

@@ -666,6 +666,15 @@ class VMPLoop(object):
       vmp_mix_estep_fused  (streaming)  E-pass that also accumulates the raw moments of ITS OWN output,
     which are exactly the M-pass input of the next iteration; only the very first iteration needs a
     stand-alone M-pass (vmp_mix_stats_ws).
+    Nothing inside an iteration reads r or u: the finalize launch takes the partial moments, the next pass forms r again from x and
+    the new pack.  stream_phase() and all but the last iteration of a run() therefore go through vmp_mixture_estep_fused_nostore / vmp_mixture_iterate_nostore, whose
+    kernel writes the partials alone (where the fused pass has the XDL form, K <= 16; elsewhere, and for accurate=, miss=, weights=
+    and a log r request, the storing calls as before), and `r` / `u` are properties: read after such a pass, they first run ONE
+    E-only pass (vmp_mix_estep: the bits the fused pass would have stored) from the current pack into the loop's own two buffers -
+    the same tensors on every read, nothing launched on a second read.  That is the r of the last pass as long as no finalize has
+    moved the pack on since: read between finalize_phase() and stream_phase(), it is the r of the NEW pack, while `stats` and the
+    workspace still describe the last pass.  step() hands r back on every call, so it keeps the storing pass, and the LAST iteration of
+    a run() is the storing pass as well: r is current when either returns, and neither ever costs more launches than before.
     accurate=True (round 6, opt-in): the E-part runs entirely in fp64 from an fp64 copy of the pack (vmp_mix_finalize_ws64 +
     vmp_mix_estep_accurate) and the moments of its output come from a separate fp64 M-pass (vmp_mix_stats_ws_accurate): three launches
     per iteration instead of one.  It is what meets the stated 1e-5 on the SMM's responsibilities at C5 (whose log rho is linear in
@@ -700,16 +709,18 @@ class VMPLoop(object):
         self.kappa = None if kappa is None else L.dev_f32(kappa.to(dev, torch.float32), 'kappa', (K,))
         prior = prior if prior is not None else default_prior(K, self.D, dev)
         self.prior = _prior(prior, K, self.D, dev)
-        self.r = L.dev_f32(r_init, 'r_nk', (self.N, K)).clone()
-        self.u = None
+        self._r = L.dev_f32(r_init, 'r_nk', (self.N, K)).clone()
+        self._u = None
         if flavour == L.VMP_SMM:
-            self.u = (torch.ones_like(self.r) if u_init is None else L.dev_f32(u_init, 'u_nk', (self.N, K)).clone())
+            self._u = (torch.ones_like(self._r) if u_init is None else L.dev_f32(u_init, 'u_nk', (self.N, K)).clone())
         D = self.D
         self.post = _post_buffers(K, D, dev)
         self.logr = None
         self.accurate = bool(accurate)
         self.iterations = 0
         self.pack64 = None
+        self._stale = False              # self._r / self._u are behind the pack: a no-store pass ran since they were written
+        self._nostore = False            # stream_phase() / run() go through the pass that stores no r / u
         if weights is not None:
             self._init_weighted(weights, miss)
             return
@@ -720,9 +731,39 @@ class VMPLoop(object):
         self.ws = torch.empty(self.nb, dtype=torch.uint8, device=dev)      # private: partials live across calls
         self.pivot = pivot_of(self.x)                                     # once per dataset
         seed_fn = L.lib().vmp_mix_stats_ws_accurate if self.accurate else L.lib().vmp_mix_stats_ws
-        L.check(seed_fn(L.ptr(self.x), L.ptr(self.r), L.ptr(self.u), L.ptr(self.pivot), self.N, D, K,
+        L.check(seed_fn(L.ptr(self.x), L.ptr(self._r), L.ptr(self._u), L.ptr(self.pivot), self.N, D, K,
                         L.ptr(self.ws), self.nb, L.stream()), 'vmp_mix_stats_ws')
         self.pack64 = torch.empty(K, L.lib().vmp_mix_pack_words(D), dtype=torch.float64, device=dev) if self.accurate else None
+        self._nostore = not self.accurate and self._has_nostore()
+
+    def _has_nostore(self):
+        """the fused pass of this loop has an instance without r / u stores: the XDL form (a host query, vmp_mix_pass_plan), in a
+        library that has the entry point (an older build selected with VMP_LIB_PATH for an A/B measurement may not)"""
+        import ctypes
+        if not hasattr(L.lib(), 'vmp_mixture_estep_fused_nostore'):
+            return False
+        plan = (ctypes.c_int64 * 8)()
+        L.check(L.lib().vmp_mix_pass_plan(self.N, self.D, self.K, self.flavour, 1, 1, 0, plan), 'vmp_mix_pass_plan')
+        return plan[0] == 2
+
+    def _fresh(self):
+        """self._r / self._u hold the r / u of the current pack: after a pass that stored none, one E-only pass (with the loop's
+        pivot: the pivot enters the rounding of the E-part) into the same buffers"""
+        if self._stale:
+            L.check(L.lib().vmp_mix_estep(L.ptr(self.x), self.N, self.D, self.K, self.flavour, L.ptr(self.post['pack']), None,
+                                          L.ptr(self._r), L.ptr(self._u), None, L.ptr(self.pivot), None, None, 0, L.stream()),
+                    'vmp_mix_estep')
+            self._stale = False
+
+    @property
+    def r(self):
+        self._fresh()
+        return self._r
+
+    @property
+    def u(self):
+        self._fresh()
+        return self._u
 
     @classmethod
     def from_seed(cls, x, K, flavour, seed, kappa=None, prior=None, accurate=False, miss=None, smooth=0.0):
@@ -785,7 +826,7 @@ class VMPLoop(object):
         self.w = L.dev_f32(weights, 'weights', (N,))
         self.miss = None if miss is None else _mask_u8(miss)
         keep = (self.w != 0)[:, None]
-        rw = torch.where(keep, self.r * self.w[:, None], torch.zeros((), dtype=torch.float32, device=dev))
+        rw = torch.where(keep, self._r * self.w[:, None], torch.zeros((), dtype=torch.float32, device=dev))
         self._stats = raw_stats(weighted_mean_filled(self.x, self.miss, self.w), rw)
         self.fpack = torch.empty(K, L.lib().vmp_mixture_fit_pack_words(D), dtype=torch.float32, device=dev)
         self.x_fill = None if miss is None else torch.empty_like(self.x)
@@ -800,7 +841,7 @@ class VMPLoop(object):
         vmp_mix_finalize -> vmp_mixture_fit_pack -> vmp_mixture_fit_pass (csrc/vmp_missfit.hip)."""
         dev, N, D, K = self.x.device, self.N, self.D, self.K
         self.miss = _mask_u8(miss)
-        self._stats = raw_stats(mean_filled(self.x, self.miss), self.r)
+        self._stats = raw_stats(mean_filled(self.x, self.miss), self._r)
         self.fpack = torch.empty(K, L.lib().vmp_mixture_fit_pack_words(D), dtype=torch.float32, device=dev)
         self.x_fill = torch.empty_like(self.x)
         self.nb = L.lib().vmp_mixture_fit_workspace_bytes(N, D, K)
@@ -833,65 +874,85 @@ class VMPLoop(object):
     def estep(self, want_logr=False):
         """E-pass with fused moments on the current pack (the second launch of an iteration)"""
         if want_logr and self.logr is None:
-            self.logr = torch.empty_like(self.r)
+            self.logr = torch.empty_like(self._r)
         if self.w is not None:
             L.check(L.lib().vmp_mixture_wfit_pass(L.ptr(self.x), L.ptr(self.w), L.ptr(self.miss), self.N, self.D, self.K, L.ptr(self.fpack),
-                                                  L.ptr(self.r), L.ptr(self.logr if want_logr else None), L.ptr(self.x_fill),
+                                                  L.ptr(self._r), L.ptr(self.logr if want_logr else None), L.ptr(self.x_fill),
                                                   L.ptr(self._stats), L.ptr(self._data), L.ptr(self.ws), self.nb, L.stream()),
                     'vmp_mixture_wfit_pass')
             return
         if self.miss is not None:
-            L.check(L.lib().vmp_mixture_fit_pass(L.ptr(self.x), L.ptr(self.miss), self.N, self.D, self.K, L.ptr(self.fpack), L.ptr(self.r),
+            L.check(L.lib().vmp_mixture_fit_pass(L.ptr(self.x), L.ptr(self.miss), self.N, self.D, self.K, L.ptr(self.fpack), L.ptr(self._r),
                                                  L.ptr(self.logr if want_logr else None), L.ptr(self.x_fill), L.ptr(self._stats),
                                                  L.ptr(self.ws), self.nb, L.stream()), 'vmp_mixture_fit_pass')
             return
         if self.accurate:
-            L.check(L.lib().vmp_mix_estep_accurate(L.ptr(self.x), self.N, self.D, self.K, self.flavour, L.ptr(self.pack64), L.ptr(self.r),
-                                                   L.ptr(self.u), L.ptr(self.logr if want_logr else None), L.stream()), 'vmp_mix_estep_accurate')
-            L.check(L.lib().vmp_mix_stats_ws_accurate(L.ptr(self.x), L.ptr(self.r), L.ptr(self.u), L.ptr(self.pivot), self.N, self.D,
+            L.check(L.lib().vmp_mix_estep_accurate(L.ptr(self.x), self.N, self.D, self.K, self.flavour, L.ptr(self.pack64), L.ptr(self._r),
+                                                   L.ptr(self._u), L.ptr(self.logr if want_logr else None), L.stream()), 'vmp_mix_estep_accurate')
+            L.check(L.lib().vmp_mix_stats_ws_accurate(L.ptr(self.x), L.ptr(self._r), L.ptr(self._u), L.ptr(self.pivot), self.N, self.D,
                                                       self.K, L.ptr(self.ws), self.nb, L.stream()), 'vmp_mix_stats_ws_accurate')
             return
         L.check(L.lib().vmp_mix_estep_fused(L.ptr(self.x), self.N, self.D, self.K, self.flavour, L.ptr(self.post['pack']),
-                                            L.ptr(self.r), L.ptr(self.u), L.ptr(self.logr if want_logr else None),
+                                            L.ptr(self._r), L.ptr(self._u), L.ptr(self.logr if want_logr else None),
                                             L.ptr(self.pivot), L.ptr(self.ws), self.nb, L.stream()), 'vmp_mix_estep_fused')
+        self._stale = False
 
     def stream_phase(self, want_logr=False):
-        """the streaming launch of an iteration: the E-pass with the moments of its own output"""
-        self.estep(want_logr)
+        """the streaming launch of an iteration: the E-pass with the moments of its own output - which it does not write out where a
+        kernel without the r / u stores exists and no log r is asked for (`r` / `u` catch up when they are read)"""
+        if want_logr or not self._nostore:
+            self.estep(want_logr)
+            return
+        L.check(L.lib().vmp_mixture_estep_fused_nostore(L.ptr(self.x), self.N, self.D, self.K, self.flavour, L.ptr(self.post['pack']),
+                                                        L.ptr(self.pivot), L.ptr(self.ws), self.nb, L.stream()),
+                'vmp_mixture_estep_fused_nostore')
+        self._stale = True
 
     def step(self, want_logr=False):
+        """one iteration; returns its r - which is why the pass here is the storing one"""
         self.finalize_phase()
-        self.stream_phase(want_logr)
+        self.estep(want_logr)
         self.iterations += 1
-        return self.r
+        return self._r
 
     def run(self, iterations):
-        """`iterations` VMP iterations enqueued by one C call (vmp_mix_iterate): no host work between launches."""
+        """`iterations` VMP iterations enqueued without host work between the launches (vmp_mix_iterate; where the pass has an instance
+        without r / u stores, vmp_mixture_iterate_nostore for all but the last of them).  Returns r."""
         if self.accurate:
             for _ in range(int(iterations)):
                 self.step()
-            return self.r
+            return self._r
         if self.w is not None:
             p = self.post
             L.check(L.lib().vmp_mixture_wfit_iterate(L.ptr(self.x), L.ptr(self.w), L.ptr(self.miss), self.N, self.D, self.K,
-                                                     *[L.ptr(t) for t in self.prior], L.ptr(self.r), None, L.ptr(self.x_fill),
+                                                     *[L.ptr(t) for t in self.prior], L.ptr(self._r), None, L.ptr(self.x_fill),
                                                      *[L.ptr(p[k]) for k in _POST[:8]], L.ptr(self.fpack), L.ptr(self._stats),
                                                      L.ptr(self._data), L.ptr(self.ws), self.nb, int(iterations), L.stream()),
                     'vmp_mixture_wfit_iterate')
             self.iterations += int(iterations)
-            return self.r
+            return self._r
         if self.miss is not None:
             p = self.post
             L.check(L.lib().vmp_mixture_fit_iterate(L.ptr(self.x), L.ptr(self.miss), self.N, self.D, self.K, *[L.ptr(t) for t in self.prior],
-                                                    L.ptr(self.r), None, L.ptr(self.x_fill), *[L.ptr(p[k]) for k in _POST[:8]],
+                                                    L.ptr(self._r), None, L.ptr(self.x_fill), *[L.ptr(p[k]) for k in _POST[:8]],
                                                     L.ptr(self.fpack), L.ptr(self._stats), L.ptr(self.ws), self.nb, int(iterations),
                                                     L.stream()), 'vmp_mixture_fit_iterate')
             self.iterations += int(iterations)
-            return self.r
+            return self._r
         ws, pivot, *f = self._fin_ptrs()                       # f = N, D, K, flavour, prior x 5, kappa | posterior x 9
-        L.check(L.lib().vmp_mix_iterate(L.ptr(self.x), *f[:10], pivot, L.ptr(self.r), L.ptr(self.u), *f[10:], ws, self.nb,
-                                        int(iterations), L.stream()), 'vmp_mix_iterate')
-        self.iterations += int(iterations)
+        n = int(iterations)
+        if self._nostore and n > 1:
+            # all but the last iteration without the r / u stores; the last one stores them, so that r is current when the call
+            # returns and no E-only pass is ever launched for it (run_until* call run() every few iterations)
+            L.check(L.lib().vmp_mixture_iterate_nostore(L.ptr(self.x), *f[:10], pivot, *f[10:], ws, self.nb, n - 1, L.stream()),
+                    'vmp_mixture_iterate_nostore')
+            self.iterations += n - 1
+            n = 1
+        L.check(L.lib().vmp_mix_iterate(L.ptr(self.x), *f[:10], pivot, L.ptr(self._r), L.ptr(self._u), *f[10:], ws, self.nb, n, L.stream()),
+                'vmp_mix_iterate')
+        self.iterations += n
+        if n > 0:
+            self._stale = False
         return self.r
 
     def score_pack(self):

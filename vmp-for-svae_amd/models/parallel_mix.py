@@ -278,7 +278,13 @@ class DistributedVMPLoop(_mix.VMPLoop):
     def run(self, iterations):
         """`iterations` data-parallel VMP iterations (the base class enqueues the SINGLE-process iteration through one C call;
         here every iteration has its exchange)."""
-        for _ in range(int(iterations)):
-            self.step()
+        n = int(iterations)
+        for i in range(n):
+            self.finalize_phase()
+            if i + 1 < n:
+                self.stream_phase()                       # no r / u stores where the pass has that instance
+            else:
+                self.estep()                              # the last iteration stores them: r is current, no extra launch when it is read
+            self.iterations += 1
         self.check()
         return self.r

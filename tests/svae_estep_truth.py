@@ -38,7 +38,8 @@ TENSOR_CASES = [('tile', 'bwd1', (37, 10, 6, 10), 'for'), ('chunked', 'generic_o
                 ('tile', 'generic_stream', (40000, 10, 2, 10), 'blocks')]
 # the direct-step sweep (tests/test_smm_direct_step_gpu.py): (N, K, L, U, Dy, S)
 DIRECT_SHAPES = [(64, 16, 8, 50, 8, 10), (64, 10, 8, 50, 6, 16), (512, 8, 6, 50, 6, 10), (40, 20, 4, 32, 4, 6), (30, 33, 2, 16, 2, 4),
-                 (37, 7, 4, 33, 3, 8), (5, 3, 2, 16, 1, 4)]
+                 (37, 7, 4, 33, 3, 8), (5, 3, 2, 16, 1, 4),
+                 (24, 3, 1, 16, 2, 4), (40, 4, 3, 24, 3, 8), (48, 5, 5, 40, 5, 4), (33, 33, 7, 48, 7, 8)]     # the odd latent sizes
 NET_VARS = ('layer_0/kernel', 'layer_0/bias', 'layer_1/kernel', 'layer_1/bias', 'gaussian_output/kernel', 'gaussian_output/bias',
             'shortcut/W', 'shortcut/b1', 'shortcut/b2')
 

@@ -161,7 +161,7 @@ def test_fused_elbo_fn_matches_unfused_composition(dims):
             assert rel(a, b * f) < 2e-5
 
 
-@pytest.mark.parametrize('N,K,Ld', [(64, 10, 8), (100, 16, 6), (1, 3, 2), (512, 5, 8)])
+@pytest.mark.parametrize('N,K,Ld', [(64, 10, 8), (100, 16, 6), (1, 3, 2), (512, 5, 8), (37, 7, 1), (37, 7, 3), (5, 3, 4), (64, 33, 5), (64, 16, 7)])
 def test_stats_cvi_one_launch_equals_the_two(N, K, Ld):
     """vmp_svae_stats_cvi (M-step moments + CVI update in one launch) == vmp_mix_stats followed by vmp_svae_cvi_update,
     bit for bit, with the step size by value and through the device word."""
@@ -184,7 +184,7 @@ def test_stats_cvi_one_launch_equals_the_two(N, K, Ld):
         _svae_ops.stats_cvi(torch.randn(513, Ld, device='cuda'), torch.rand(513, K, device='cuda'), prior, [t.clone() for t in theta0], 0.1)
 
 
-@pytest.mark.parametrize('K,Ld', [(10, 8), (16, 6), (3, 1), (64, 8)])
+@pytest.mark.parametrize('K,Ld', [(10, 8), (16, 6), (3, 1), (64, 8), (5, 2), (33, 3), (16, 4), (7, 5), (33, 7)])
 def test_prep_one_launch_equals_the_two(K, Ld):
     """PhiPrepFn with theta (vmp_svae_prep_fwd: recognition unpacking + theta packing in one launch) == PhiPrepFn without
     + theta_pack_gmm, bit for bit; gradients w.r.t. the recognition parameters unchanged."""
@@ -279,7 +279,8 @@ def test_bwd_tail_equals_tail_plus_backward(N, K, Ld, S):
     assert ((got - want).abs().max() / max(abs(want[1].item()), abs(want[2].item()))).item() < 2e-7
 
 
-@pytest.mark.parametrize('K,Ld,nblk', [(10, 8, 11), (16, 8, 1), (7, 4, 70), (3, 2, 300), (5, 5, 17)])
+@pytest.mark.parametrize('K,Ld,nblk', [(10, 8, 11), (16, 8, 1), (7, 4, 70), (3, 2, 300), (5, 5, 17), (64, 1, 16), (33, 3, 65), (16, 6, 63),
+                                        (33, 7, 15), (1, 8, 64)])
 def test_bwd_reduce_prep_equals_reduce_then_prep_backward(K, Ld, nblk):
     """Round 6: vmp_svae_bwd_reduce_prep (block k sums component k's partial rows and differentiates the recognition unpacking on them;
     log softmax(pi) from the forward's vmp_svae_prep_fwd2) against vmp_svae_bwd_reduce + vmp_svae_phi_prep_bwd: bit-identical."""
@@ -333,7 +334,8 @@ def test_step_inputs_and_the_first_launch_with_a_scalar_table():
     assert torch.equal(y, src)
     assert dst[:8].view(torch.int64).item() == 0xDEADBEEF12345678 - (1 << 64)
     assert dst[8:12].view(torch.float32).item() == 0.125 and dst[12:].view(torch.float32).item() == np.float32(3e-4)
-    for N, Dy, Ld, U, K in ((64, 6, 8, 50, 10), (5, 3, 2, 16, 3), (300, 8, 4, 64, 16)):
+    for N, Dy, Ld, U, K in ((64, 6, 8, 50, 10), (5, 3, 2, 16, 3), (300, 8, 4, 64, 16), (5, 3, 1, 16, 3), (37, 4, 3, 33, 7), (64, 5, 5, 48, 16),
+                            (40, 6, 6, 50, 33), (33, 7, 7, 32, 64)):
         enc = [rn(Dy, U) * 0.3, rn(U) * 0.1, rn(U, U) * 0.2, rn(U) * 0.1, rn(U, 2 * Ld) * 0.2, rn(2 * Ld) * 0.1, rn(Dy, Ld) * 0.3, rn(Ld) * 0.1, rn(Ld) * 0.1]
         yy = rn(N, Dy)
         mu, Lraw, pi = rn(K, Ld), rn(K, Ld, Ld), rn(K)

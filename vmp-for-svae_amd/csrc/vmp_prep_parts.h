@@ -163,7 +163,9 @@ __device__ __forceinline__ void phi_prep_body(const PhiArgs& a, const int k, con
         const double pr = lane < K ? (double)a.piraw[lane] : -1e300;
         const double mx = wave_max_d(pr);
         const double se = wave_sum_d(lane < K ? exp(pr - mx) : 0.0);
-        logpi = (double)a.piraw[k] - (mx + log(se));
+        // (pi_k - max) first: a difference of two fp32 values - exact in fp64 for |pi| of comparable size (exponents within ~29
+        // binades) - so that log pi_k is rounded ONCE; pi_k - (mx + log(se)) rounds at the size of mx and again at that of the result
+        logpi = ((double)a.piraw[k] - mx) - log(se);
     }
     const double ld = wave_sum_d((in && i == j) ? log(lij) : 0.0);           // log det L
     prep_sync<WS>();

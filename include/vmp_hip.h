@@ -560,6 +560,40 @@ int    vmp_mixture_seed_assign(const float* x, const uint8_t* mask, int64_t N, i
                                float* r_out, int32_t* z_out, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Diagonal-covariance mixture: seeded start on wide rows (csrc/vmp_diagseed.hip): the k-means++ centres and the nearest-centre
+ * responsibilities of "Mixture initialisation" for complete rows of D in 1..VMP_DIAG_MAX_D columns, K in 1..VMP_MAX_K
+ * ------------------------------------------------------------------------------------------------
+ * The mathematics of "Mixture initialisation" without a mask and without `fill`: dist2(n, c) = sum_d (x_nd - c_d)^2 in fp32 on the
+ * difference x - c, in d order (never the expanded form); the same uniform (Philox4x32-7, key = seed, counter (n low, n high, j,
+ * 0x6b6d2b00), word 0, the same u -> fp32 rule), the same exponential race, the same lexicographic (s, n) pick, round 0 uniform
+ * over all rows, N < K legal (the centres then repeat).  For D <= VMP_MAX_D the arithmetic is that of vmp_mixture_seed_centers with
+ * mask == NULL: both pick the same rows.
+ * x (N,D) fp32, any alignment: a 64-row tile goes to the wave's LDS with coalesced dword loads, lane = row afterwards; the centre of
+ * a round is read from x itself as a wave-uniform scalar operand.
+ *
+ * vmp_mixture_diag_seed_centers: centers_out (K,D) = the bits of x at the chosen rows; index_out (K) int64 = i_j or NULL; mind2_out
+ *   (N) = w after the last round, or NULL.  ONE call enqueues K + 1 launches back to back, no host work and no host synchronisation
+ *   in between: launch j = 0 .. K first reduces the per-block minima of launch j - 1 to i_{j-1} (every block the same reduction: no
+ *   atomics), reads c_{j-1} from x and then streams the rows once - w <- min(w, dist2(., c_{j-1})) and, for j < K, the block's
+ *   minimum of round j is left in ws; launch 0 reads no x, launch K without mind2_out is one block.  w lives in ws: per row a round
+ *   reads x and w and writes w.  The geometry depends on (N, D) only: every output is bit-identical from run to run and whichever
+ *   optional outputs are requested.
+ * vmp_mixture_diag_seed_assign: one launch; z_out (N) int32 = the k with the smallest dist2(n, c_k), ties to the lowest k, or NULL;
+ *   r_out (N,K) = (1 - smooth) [k = z_n] + smooth / K in fp32 (the one-hot entry is (1 - smooth) + smooth / K), or NULL; at least one
+ *   of the two.  No workspace.
+ * vmp_mixture_diag_seed_workspace_bytes = w (N) fp32 padded to 16 bytes + the double-buffered candidates (2, blocks) x (int64, fp32)
+ *   padded to 16 bytes, blocks = min(D > 32 ? 512 : 1024, ceil(N / 1024)): a multiple of 8, non-decreasing in N, 0 outside the
+ *   compiled range (and for N < 1).
+ * Errors (decided before any launch): VMP_E_DIM (D outside 1..VMP_DIAG_MAX_D, K outside 1..VMP_MAX_K), VMP_E_BADARG (N < 1; x,
+ *   centers_out or centers NULL; r_out and z_out both NULL; smooth outside [0, 1) or NaN; ws not 8-byte aligned), VMP_E_WS (ws NULL
+ *   or too small).                                                                                                          */
+size_t vmp_mixture_diag_seed_workspace_bytes(int64_t N, int D, int K);
+int    vmp_mixture_diag_seed_centers(const float* x, int64_t N, int D, int K, uint64_t seed, float* centers_out, int64_t* index_out,
+                                     float* mind2_out, void* ws, size_t ws_bytes, void* stream);
+int    vmp_mixture_diag_seed_assign(const float* x, int64_t N, int D, int K, const float* centers, float smooth, float* r_out,
+                                    int32_t* z_out, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * T2: SVAE E-step fused with the ELBO regulariser (models/svae.py:14-119 and :229-252)
  * ------------------------------------------------------------------------------------------------
  * Per (n,k) cell:  Pt = diag(-2 eta2d_n) + P_k,  ht = eta1_n + h_k,  Lt = chol(Pt),

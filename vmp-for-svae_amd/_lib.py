@@ -78,6 +78,9 @@ _SIGNATURES = {
     'vmp_mixture_seed_workspace_bytes': (_c.c_size_t, [_c.c_int64, _c.c_int, _c.c_int]),
     'vmp_mixture_seed_centers': (_c.c_int, [_P, _P, _P, _c.c_int64, _c.c_int, _c.c_int, _c.c_uint64, _P, _P, _P, _P, _c.c_size_t, _P]),
     'vmp_mixture_seed_assign': (_c.c_int, [_P, _P, _c.c_int64, _c.c_int, _c.c_int, _P, _c.c_float, _P, _P, _P]),
+    'vmp_mixture_diag_seed_workspace_bytes': (_c.c_size_t, [_c.c_int64, _c.c_int, _c.c_int]),
+    'vmp_mixture_diag_seed_centers': (_c.c_int, [_P, _c.c_int64, _c.c_int, _c.c_int, _c.c_uint64, _P, _P, _P, _P, _c.c_size_t, _P]),
+    'vmp_mixture_diag_seed_assign': (_c.c_int, [_P, _c.c_int64, _c.c_int, _c.c_int, _P, _c.c_float, _P, _P, _P]),
     'vmp_svae_estep_fwd': (_c.c_int, [_P] * 10 + [_c.c_int64, _c.c_int, _c.c_int, _c.c_int, _P, _P, _P, _P]),
     'vmp_svae_rng_in_kernel': (_c.c_int, [_c.c_int, _c.c_int, _c.c_int]),
     'vmp_svae_philox_noise': (_c.c_int, [_c.c_uint64, _c.c_int64, _c.c_int, _c.c_int, _c.c_int, _P, _P]),

@@ -301,11 +301,60 @@ def nearest_center_r(x, centers, smooth=0.0):
     return r
 
 
+def diag_seed_centers(x, K, seed, want_index=False, want_mind2=False):
+    """K seeded k-means++ centres (D^2-seeding) from the complete rows of x (N, D <= 64) on the device (vmp_mixture_diag_seed_centers;
+    include/vmp_hip.h "Diagonal-covariance mixture: seeded start on wide rows"): (centers (K,D), index (K,) int64 or None, mind2 (N,)
+    or None) - the chosen rows and every row's squared distance to its nearest centre.  A pure function of (seed, row index, round),
+    the stream and the rules of _mix.seed_centers: for D <= 8 the same rows.  K + 1 launches enqueued by one call, no host
+    synchronisation."""
+    K, seed = int(K), int(seed)
+    if not 0 <= seed < 1 << 64:
+        raise L.VmpError('seed must be in 0 .. 2^64 - 1 (got %d)' % seed)
+    N, D = _x_dims(x, 'diag_seed_centers')
+    _check_dk(D, K)
+    x = L.dev_f32(x, 'x')
+    dev = x.device
+    centers = torch.empty(K, D, dtype=torch.float32, device=dev)
+    index = torch.empty(K, dtype=torch.int64, device=dev) if want_index else None
+    mind2 = torch.empty(N, dtype=torch.float32, device=dev) if want_mind2 else None
+    nb = L.lib().vmp_mixture_diag_seed_workspace_bytes(N, D, K)
+    ws = L.workspace(dev, nb)
+    L.check(L.lib().vmp_mixture_diag_seed_centers(L.ptr(x), N, D, K, seed, L.ptr(centers), L.ptr(index), L.ptr(mind2), L.ptr(ws), nb,
+                                                  L.stream()), 'vmp_mixture_diag_seed_centers')
+    return centers, index, mind2
+
+
+def diag_seed_assign(x, centers, smooth=0.0, want_z=False):
+    """Responsibilities of the nearest centre on wide rows (vmp_mixture_diag_seed_assign): (r (N,K), z (N,) int32 or None) with z_n the
+    nearest of centers (K,D) by the fp32 squared distance of diag_seed_centers (ties to the lowest k) and r_nk = (1 - smooth)
+    [k = z_n] + smooth / K, 0 <= smooth < 1.  One streaming launch, no host synchronisation."""
+    smooth = float(smooth)
+    if not 0.0 <= smooth < 1.0:
+        raise L.VmpError('smooth must be in [0, 1) (got %r)' % smooth)
+    N, D = _x_dims(x, 'diag_seed_assign')
+    if not torch.is_tensor(centers) or centers.dim() != 2 or centers.shape[1] != D:
+        raise L.VmpError('diag_seed_assign: centers has shape %s, expected (K,%d)'
+                         % (tuple(centers.shape) if torch.is_tensor(centers) else type(centers), D))
+    if centers.device != x.device:
+        raise L.VmpError('diag_seed_assign: centers is on %s, x on %s' % (centers.device, x.device))
+    K = centers.shape[0]
+    _check_dk(D, K)
+    x = L.dev_f32(x, 'x')
+    centers = L.dev_f32(centers, 'centers', (K, D))
+    r = torch.empty(N, K, dtype=torch.float32, device=x.device)
+    z = torch.empty(N, dtype=torch.int32, device=x.device) if want_z else None
+    L.check(L.lib().vmp_mixture_diag_seed_assign(L.ptr(x), N, D, K, L.ptr(centers), smooth, L.ptr(r), L.ptr(z), L.stream()),
+            'vmp_mixture_diag_seed_assign')
+    return r, z
+
+
 class DiagLoop(object):
     """The VMP iteration of the diagonal-covariance Gaussian mixture on x (N, D <= 64), started from responsibilities r_init (N,K):
     M-step from the moments of the current r (vmp_mixture_diag_finalize), the E-step pack, and one streaming pass that computes the
     new r, its moments and the data term of the lower bound.  run(n) enqueues n iterations in one call and leaves r in the kernel
     (the pass then moves x alone); step() also writes r.  Both updates are exact coordinate ascent: lower_bound() never falls.
+    from_seed(x, K, seed) starts the loop from the data alone: k-means++ centres and their nearest-centre responsibilities, both in
+    kernels (csrc/vmp_diagseed.hip); from_centers() takes the caller's centres (torch plumbing).
     Rows the loop was not fitted on: heldout() (mean log predictive density), heldout_logprob() (per row, with the predictive
     responsibilities on request), fill() (conditional means of missing entries) and run_until() (stop on a validation set) - one
     streaming pass each (csrc/vmp_diagscore.hip).  Out of scope, refused: fitting on masked or weighted rows, the Student-t flavour,
@@ -347,6 +396,15 @@ class DiagLoop(object):
     def from_centers(cls, x, centers, smooth=0.0, prior=None):
         """start from the responsibilities of the nearest of `centers` (K,D) (nearest_center_r)"""
         return cls(x, nearest_center_r(x, centers, smooth), prior=prior)
+
+    @classmethod
+    def from_seed(cls, x, K, seed, smooth=0.0, prior=None):
+        """The loop started from the data: r_init = diag_seed_assign on the K centres of diag_seed_centers(x, K, seed) - k-means++ on
+        the device, a pure function of (x, K, seed) - then the constructor's r_in pass.  K + 3 launches, no host synchronisation, and
+        no buffer of the seeding larger than r_init (N,K) fp32; with prior=None the constructor takes default_diag_prior(x, K), whose
+        column means go through an fp64 copy of x as for every DiagLoop - pass a prior to avoid it."""
+        centers, _, _ = diag_seed_centers(x, K, seed)
+        return cls(x, diag_seed_assign(x, centers, smooth)[0], prior=prior)
 
     def _iterate(self, iterations, want_r, want_logr):
         if want_logr and self._logr is None:

@@ -1080,5 +1080,5 @@ class VMPLoop(object):
 
 # the diagonal-covariance mixture on wide rows (D up to 64) lives in models/_diag.py; its entry points are reachable from here as well
 from ._diag import (DiagLoop, default_diag_prior, diag_bound_terms, diag_finalize, diag_lower_bound, diag_pack,  # noqa: E402,F401
-                    diag_predictive_impute, diag_predictive_logprob, diag_score_pack, mixture_diag_pass, mixture_diag_score,
-                    nearest_center_r)
+                    diag_predictive_impute, diag_predictive_logprob, diag_score_pack, diag_seed_assign, diag_seed_centers,
+                    mixture_diag_pass, mixture_diag_score, nearest_center_r)

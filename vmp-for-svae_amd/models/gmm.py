@@ -279,18 +279,22 @@ def inference_diag(x, K, seed, iterations=1, r_init=None, prior=None, init='rand
     theta, (x_k, S_k, pi)) as inference() does: `step()` runs `iterations` VMP iterations enqueued by one call and returns the new
     r_nk; theta() = (alpha_k, beta_k, m_k, a_k, b_k); S_k (K,D) holds the per-coordinate variances.  init='random': a host-side
     Dirichlet(1) draw with `seed`; an explicit r_init wins.  prior = (alpha_0, beta_0, m_0, a_0, b_0), default
-    _mix.default_diag_prior.  init='kmeans++' is not available here (the seeding kernels stop at D = 8): seed with
-    _mix.DiagLoop.from_centers."""
-    if init != 'random':
-        raise L.VmpError("inference_diag: init=%r - only 'random' (or an explicit r_init; DiagLoop.from_centers for centres)" % (init,))
+    _mix.default_diag_prior.  init='kmeans++' (when no r_init is given): the start of _mix.DiagLoop.from_seed(x, K, seed) - k-means++
+    centres and their nearest-centre responsibilities, built on the device by the kernels of csrc/vmp_diagseed.hip, so x must be on a
+    GPU for it; 'random' is the only start that is drawn on the host."""
+    _mix.check_init(init)
     iterations = int(iterations)
     if iterations < 1:
         raise L.VmpError('inference_diag: iterations must be >= 1')
     if not torch.is_tensor(x) or x.dim() != 2:
         raise L.VmpError('inference_diag: x must be (N,D)')
-    if r_init is None:
-        r_init = _dirichlet_init(x.shape[0], K, seed, x.device)
-    loop = _mix.DiagLoop(x, r_init, prior=prior)
+    if r_init is None and init == 'kmeans++':
+        if not x.is_cuda:
+            raise L.VmpError("inference_diag: init='kmeans++' seeds in HIP kernels on x's device and x is on %s (no CPU fallback) - "
+                             "only 'random' is drawn on the host" % (x.device,))
+        loop = _mix.DiagLoop.from_seed(x, K, seed, prior=prior)
+    else:
+        loop = _mix.DiagLoop(x, _dirichlet_init(x.shape[0], K, seed, x.device) if r_init is None else r_init, prior=prior)
 
     def step():
         if iterations > 1:

@@ -477,6 +477,67 @@ int    vmp_mixture_diag_iterate(const float* x, int64_t N, int D, int K, const f
                                 void* ws, size_t ws_bytes, int iterations, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Diagonal-covariance mixture: fitting partly observed and weighted rows (csrc/vmp_diagmfit.hip): D up to VMP_DIAG_MAX_D, K up to VMP_MAX_K
+ * ------------------------------------------------------------------------------------------------
+ * The fit of the section above on rows with missing entries (missing at random) and with row weights.  Notation and model are those
+ * of that section; o(n) / m(n) are the observed / missing coordinates of row n, D_o(n) = |o(n)|, w_n >= 0 the weight of row n (1
+ * without weights), lbar_kd = a_k / b_kd.  The missing entries are latent variables; for the diagonal model the optimum q(x_m | z) is
+ * a product of one-dimensional Gaussians, so the posterior keeps its form theta = (alpha, beta, m, a, b) and both updates stay exact
+ * coordinate ascent (the bound never falls):
+ *   hl_kd      = -1/2 log lbar_kd
+ *   log rho_nk = c_k - 1/2 sum_{d in o(n)} lbar_kd (x_nd - m_kd)^2 + sum_{d in m(n)} hl_kd      (c_k as above, over all D)
+ *   r_nk       = softmax_k log rho_nk                  a weight does not enter a row's own responsibilities
+ *   q(x_nd | z_n = k), d missing:  N(m_kd, 1 / lbar_kd)
+ *   Nk     = sum_n w_n r_nk,    M_kd = sum_n w_n r_nk [d in m(n)]
+ *   sx_kd  = sum_n w_n r_nk [d in o(n)] x_nd   + M_kd m_kd
+ *   sxx_kd = sum_n w_n r_nk [d in o(n)] x_nd^2 + M_kd (m_kd^2 + 1 / lbar_kd)
+ *   data   = sum_n w_n ( logsumexp_k log rho_nk - 1/2 D_o(n) log 2 pi )
+ *   bound  = data - kl_pi - sum_kd kl_ng_kd            (vmp_mixture_diag_bound_terms, unchanged)
+ * The M-step is vmp_mixture_diag_finalize, unchanged, on stats (K, 1 + 2 D) = [ Nk | sx | sxx ] of the completed rows.  A row that
+ * observes nothing has log rho_nk = c_k + sum_d hl_kd; a column nobody observes stays finite.  A row with w = 0 is removed by a
+ * select, not a product: whatever its slots hold (NaN and +-Inf included) reaches neither moments nor data; its r / log r / fill are
+ * still written.  What a missing slot of x holds never enters arithmetic.
+ * Layout: pack (K, vmp_mixture_diag_mfit_pack_words(D) = 3 D + 1) fp32 = [ m (D) | lbar (D) | hl (D) | c ].
+ *
+ * vmp_mixture_diag_mfit_pack: the pack from theta, one block per component, fp64 inside, rounded once.  A component with a
+ *   non-positive (or NaN) b_kd, a_k or beta_k gets a NaN row.
+ * vmp_mixture_diag_mfit_pass: one streaming pass over x (N,D) fp32, any alignment, with an optional mask (N,D) uint8, nonzero =
+ *   missing, and optional weights w (N) fp32 (finite, >= 0; the caller's business), under a pack.  mask == NULL is a kernel of its own
+ *   that reads and selects nothing of a mask; w == NULL is a wave-uniform test.  Outputs, all optional but at least one: r_out (N,K)
+ *   and logr_out (N,K) (needs r_out), both of the unweighted r; x_fill_out (N,D) (needs mask): observed entries copied bit for bit,
+ *   missing ones filled with sum_k r_nk m_kd; stats_out (K, 1 + 2 D) fp64; bound_out (1) fp64 = data.  r_out == NULL is the fast form
+ *   of an iteration: the pass then moves x, mask and w alone.  The geometry is that of vmp_mixture_diag_pass: the moments of w r are
+ *   accumulated in fp32 on x - p by 16-row MFMA groups with ONE pivot p (the mean of the observed entries of up to 64 evenly strided
+ *   rows of positive weight: a function of x, mask, w, N and D alone), M_kd by a third MFMA chain on the 0/1 indicator of a missing
+ *   entry; added to the wave's own fp64 words every 128 rows; a second launch adds the waves in a fixed order, undoes the shift on
+ *   the observed part and completes the missing part in fp64 with the pack's own fp32 m and lbar:
+ *     sx = s1 + (Nk - M) p + M m,    sxx = s2 + 2 p s1 + (Nk - M) p^2 + M (m^2 + 1 / lbar).
+ *   A row's data term is formed in fp64 from its fp32 log-sum-exp, the integer D_o and the fp32 weight, and added in the fixed order
+ *   of vmp_mixture_diag_pass.  No atomics, one geometry for (N, D, K): stats_out and bound_out are bit-identical from run to run and
+ *   whichever other outputs are requested.  ws (vmp_mixture_diag_mfit_workspace_bytes: blocks x 4 waves x K (1 + 3 D) fp64 words, one
+ *   fp64 word per block and the pivot, blocks = min(512 while K (1 + 3 D) <= 2048 else 256, ceil(N / 2048)); 8-byte aligned) is
+ *   always needed.
+ * vmp_mixture_diag_mfit_iterate: `iterations` x (vmp_mixture_diag_finalize on stats -> vmp_mixture_diag_mfit_pack ->
+ *   vmp_mixture_diag_mfit_pass with stats_out = stats, bound_out = bound) enqueued back to back; stats holds the moments of the
+ *   current r on entry.  r, logr and x_fill, if not NULL, are written by the last pass only.  xbar, S, pi, bound may be NULL.
+ * Errors (decided before any launch): VMP_E_DIM (D outside 1..VMP_DIAG_MAX_D, K outside 1..VMP_MAX_K), VMP_E_BADARG (N < 1; x or pack
+ *   NULL; no output; logr_out without r_out; x_fill_out without mask; ws not 8-byte aligned; a NULL prior, posterior or stats of the
+ *   iteration or the pack builder; iterations < 0), VMP_E_WS (ws NULL or too small).  vmp_mixture_diag_mfit_workspace_bytes and
+ *   vmp_mixture_diag_mfit_pack_words are 0 outside the compiled range.                                                       */
+int    vmp_mixture_diag_mfit_pack_words(int D);
+int    vmp_mixture_diag_mfit_pack(int D, int K, const float* alpha, const float* beta, const float* m, const float* a, const float* b,
+                                  float* pack, void* stream);
+size_t vmp_mixture_diag_mfit_workspace_bytes(int64_t N, int D, int K);
+int    vmp_mixture_diag_mfit_pass(const float* x, const uint8_t* mask, const float* w, int64_t N, int D, int K, const float* pack,
+                                  float* r_out, float* logr_out, float* x_fill_out, double* stats_out, double* bound_out, void* ws,
+                                  size_t ws_bytes, void* stream);
+int    vmp_mixture_diag_mfit_iterate(const float* x, const uint8_t* mask, const float* w, int64_t N, int D, int K, const float* alpha0,
+                                     const float* beta0, const float* m0, const float* a0, const float* b0, float* r, float* logr,
+                                     float* x_fill, float* alpha, float* beta, float* m, float* a, float* b, float* xbar, float* S,
+                                     float* pi, float* pack, double* stats, double* bound, void* ws, size_t ws_bytes, int iterations,
+                                     void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Diagonal-covariance mixture: scoring and filling wide rows (csrc/vmp_diagscore.hip): D up to VMP_DIAG_MAX_D, K up to VMP_MAX_K
  * ------------------------------------------------------------------------------------------------
  * Log posterior predictive density, predictive responsibilities and conditional-mean fills of rows the posterior theta = (alpha,

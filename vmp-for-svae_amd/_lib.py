@@ -71,6 +71,12 @@ _SIGNATURES = {
     'vmp_mixture_diag_bound_terms': (_c.c_int, [_c.c_int, _c.c_int] + [_P] * 10 + [_P, _P]),
     'vmp_mixture_diag_iterate': (_c.c_int, [_P, _c.c_int64, _c.c_int, _c.c_int] + [_P] * 5 + [_P, _P] + [_P] * 8
                                  + [_P, _P, _P, _P, _c.c_size_t, _c.c_int, _P]),
+    'vmp_mixture_diag_mfit_pack_words': (_c.c_int, [_c.c_int]),
+    'vmp_mixture_diag_mfit_pack': (_c.c_int, [_c.c_int, _c.c_int] + [_P] * 5 + [_P, _P]),
+    'vmp_mixture_diag_mfit_workspace_bytes': (_c.c_size_t, [_c.c_int64, _c.c_int, _c.c_int]),
+    'vmp_mixture_diag_mfit_pass': (_c.c_int, [_P, _P, _P, _c.c_int64, _c.c_int, _c.c_int, _P, _P, _P, _P, _P, _P, _P, _c.c_size_t, _P]),
+    'vmp_mixture_diag_mfit_iterate': (_c.c_int, [_P, _P, _P, _c.c_int64, _c.c_int, _c.c_int] + [_P] * 5 + [_P] * 3 + [_P] * 8
+                                      + [_P, _P, _P, _P, _c.c_size_t, _c.c_int, _P]),
     'vmp_mixture_diag_score_pack_words': (_c.c_int, [_c.c_int]),
     'vmp_mixture_diag_score_pack': (_c.c_int, [_c.c_int, _c.c_int] + [_P] * 5 + [_P, _P]),
     'vmp_mixture_diag_score_workspace_bytes': (_c.c_size_t, [_c.c_int64, _c.c_int, _c.c_int]),

@@ -40,11 +40,33 @@ def _dev5(ops, dev, suffix=''):
     return [L.dev_f32(t.detach().to(dev, torch.float32), n + suffix) for t, n in zip(ops, NAMES)]
 
 
-def default_diag_prior(x, K):
-    """alpha_0 = 0.05 / K, beta_0 = 0.5, m_0 = the column means of x, a_0 = 1, b_0 = 1 - on x's device"""
+def _miss_dims(miss, N, D, what):
+    if not torch.is_tensor(miss) or tuple(miss.shape) != (N, D):
+        raise L.VmpError('%s: the missing-data mask must be (%d,%d), got %s' % (what, N, D, tuple(miss.shape) if torch.is_tensor(miss) else type(miss)))
+
+
+def observed_column_means(x, miss=None, weights=None):
+    """((D,) fp64 weighted means of the observed entries of the rows of positive weight - 0 for a column without one -, live (N,D)
+    bool or None): what a missing slot or a row of weight 0 holds (NaN included) is selected out, never multiplied.  Torch plumbing."""
+    if miss is None and weights is None:
+        return x.double().mean(0), None
+    N, D = x.shape
+    live = torch.ones(N, D, dtype=torch.bool, device=x.device) if miss is None else (miss == 0)
+    w = torch.ones(N, dtype=torch.float64, device=x.device) if weights is None else weights.double()
+    live = live & (w > 0)[:, None]
+    num = (torch.where(live, x.double(), torch.zeros((), dtype=torch.float64, device=x.device)) * w[:, None]).sum(0)
+    den = (live.double() * w[:, None]).sum(0)
+    return torch.where(den > 0, num / den.clamp_min(1e-300), torch.zeros_like(num)), live
+
+
+def default_diag_prior(x, K, miss=None, weights=None):
+    """alpha_0 = 0.05 / K, beta_0 = 0.5, m_0 = the column means of x, a_0 = 1, b_0 = 1 - on x's device.  With miss (N,D; nonzero =
+    missing) and / or weights (N,): the weighted means of the observed entries (observed_column_means)."""
     N, D = _x_dims(x, 'default_diag_prior')
     f32 = dict(dtype=torch.float32, device=x.device)
-    mean = x.double().mean(0).to(torch.float32)
+    if miss is not None:
+        _miss_dims(miss, N, D, 'default_diag_prior')
+    mean = observed_column_means(x, miss, weights)[0].to(torch.float32)
     return (torch.full((K,), 0.05 / K, **f32), torch.full((K,), 0.5, **f32), mean[None, :].expand(K, D).contiguous(),
             torch.ones(K, **f32), torch.ones(K, D, **f32))
 
@@ -155,10 +177,13 @@ def diag_bound_terms(prior, theta):
     return out
 
 
-def diag_lower_bound(x, theta, prior=None):
+def diag_lower_bound(x, theta, prior=None, miss=None, weights=None):
     """The variational lower bound of the diagonal posterior theta on the rows of x: a 0-dim fp64 device tensor, data - kl_pi -
     sum_kd kl_ng_kd, with q(z) at its optimum for theta.  Pack, the bound-only pass, the terms, one subtraction: no host
-    synchronisation."""
+    synchronisation.  miss (N,D; nonzero = missing) and / or weights (N,) fp32 >= 0: the bound of a DiagFitLoop fit (q(x_missing | z)
+    at its optimum too), through the bound-only form of mixture_diag_mfit_pass; without them the call is what it was."""
+    if miss is not None or weights is not None:
+        return _mfit_lower_bound(x, theta, prior, miss, weights)
     N, D = _x_dims(x, 'lower_bound_diag')
     if len(theta) != 5 or not torch.is_tensor(theta[2]) or theta[2].dim() != 2:
         raise L.VmpError('lower_bound_diag: theta is (alpha, beta, m (K,D), a, b)')
@@ -357,15 +382,15 @@ class DiagLoop(object):
     kernels (csrc/vmp_diagseed.hip); from_centers() takes the caller's centres (torch plumbing).
     Rows the loop was not fitted on: heldout() (mean log predictive density), heldout_logprob() (per row, with the predictive
     responsibilities on request), fill() (conditional means of missing entries) and run_until() (stop on a validation set) - one
-    streaming pass each (csrc/vmp_diagscore.hip).  Out of scope, refused: fitting on masked or weighted rows, the Student-t flavour,
-    accurate=True; score / impute keep refusing and name heldout / heldout_logprob / fill, sampling (sample / impute_draws) is not
+    streaming pass each (csrc/vmp_diagscore.hip).  Masked or weighted rows are refused here and fitted by the subclass DiagFitLoop.
+    Out of scope, refused: the Student-t flavour, accurate=True; score / impute keep refusing and name heldout / heldout_logprob / fill, sampling (sample / impute_draws) is not
     built."""
 
     def __init__(self, x, r_init, prior=None, miss=None, weights=None, flavour=L.VMP_GMM, accurate=False):
         if miss is not None:
-            raise L.VmpError('DiagLoop: no masks - the diagonal mixture fits complete rows only')
+            raise L.VmpError('DiagLoop: no masks - this loop fits complete rows only (DiagFitLoop fits partly observed rows)')
         if weights is not None:
-            raise L.VmpError('DiagLoop: no weights - the diagonal mixture has no weighted pass')
+            raise L.VmpError('DiagLoop: no weights - this loop has no weighted pass (DiagFitLoop fits weighted rows)')
         if flavour != L.VMP_GMM:
             raise L.VmpError('DiagLoop: Gaussian mixture only (no Student-t flavour)')
         if accurate:
@@ -535,3 +560,208 @@ class DiagLoop(object):
 
     score = impute = _refuse_score
     sample = impute_draws = _refuse_sample
+
+
+# ---- partly observed and weighted rows (csrc/vmp_diagmfit.hip; include/vmp_hip.h "Diagonal-covariance mixture: fitting partly observed
+# and weighted rows") ----
+
+def diag_mfit_pack(alpha, beta, m, a, b):
+    """The E-step pack (K, 3 D + 1) fp32 = [ m | lbar = a / b | hl = -1/2 log lbar | c ] of a posterior for the pass on partly observed
+    and weighted rows (vmp_mixture_diag_mfit_pack); fp64 inside, rounded once.  A component with a non-positive b, a or beta gets a NaN
+    row.  One K-block launch, no host synchronisation."""
+    if not torch.is_tensor(m) or m.dim() != 2:
+        raise L.VmpError('diag_mfit_pack: m must be (K,D)')
+    K, D = m.shape
+    _check_dk(D, K)
+    theta = _dev5(_five((alpha, beta, m, a, b), K, D, 'diag_mfit_pack'), m.device)
+    pack = torch.empty(K, L.lib().vmp_mixture_diag_mfit_pack_words(D), dtype=torch.float32, device=m.device)
+    L.check(L.lib().vmp_mixture_diag_mfit_pack(D, K, *[L.ptr(t) for t in theta], L.ptr(pack), L.stream()), 'vmp_mixture_diag_mfit_pack')
+    return pack
+
+
+def _mfit_dims(x, pack, miss, weights, what):
+    """(N, D, K) of a pass on masked / weighted rows, refused BEFORE the library or a device is touched"""
+    from ._mix import _weights_dims
+    N, D = _x_dims(x, what)
+    if not torch.is_tensor(pack) or pack.dim() != 2 or pack.shape[1] != 3 * D + 1:
+        raise L.VmpError('%s: no masked-fit diagonal pack for D=%d (shape %s, expected (K,%d): diag_mfit_pack)'
+                         % (what, D, tuple(pack.shape) if torch.is_tensor(pack) else type(pack), 3 * D + 1))
+    K = pack.shape[0]
+    _check_dk(D, K)
+    if miss is not None:
+        _miss_dims(miss, N, D, what)
+        if miss.device != x.device:
+            raise L.VmpError('%s: the missing-data mask is on %s, x on %s' % (what, miss.device, x.device))
+    if weights is not None:
+        _weights_dims(x, weights, what)
+    return N, D, K
+
+
+def mixture_diag_mfit_pass(x, pack, miss=None, weights=None, want_r=True, want_logr=False, want_fill=False, want_stats=True,
+                           want_bound=False):
+    """One streaming pass (vmp_mixture_diag_mfit_pass) over the rows of x (N,D) with an optional mask miss (N,D; nonzero = missing)
+    and optional weights (N,) fp32 >= 0 under a diag_mfit_pack: (r (N,K), logr (N,K), x_fill (N,D), stats (K, 1 + 2 D) fp64 = [Nk | sx
+    | sxx] of the completed rows, every row counted w_n times, bound 0-dim fp64 = the data term sum_n w_n (logsumexp_k log rho_nk -
+    1/2 D_o(n) log 2 pi)); outputs that are not wanted are None.  r and logr are unweighted: a weight does not enter a row's own
+    responsibilities.  A row of weight 0 reaches neither stats nor bound whatever it holds; what a missing slot of x holds never
+    enters arithmetic.  want_r=False is the fast form: the pass moves x, mask and weights alone.  want_logr needs want_r, want_fill
+    needs miss.  The weights are taken as they are (check_weights is the loop's business).  stats and bound are the same bits from
+    run to run and for every set of outputs.  No host synchronisation."""
+    what = 'mixture_diag_mfit_pass'
+    N, D, K = _mfit_dims(x, pack, miss, weights, what)
+    if not (want_r or want_logr or want_fill or want_stats or want_bound):
+        raise L.VmpError('%s: no output requested' % what)
+    if want_logr and not want_r:
+        raise L.VmpError('%s: want_logr needs want_r' % what)
+    if want_fill and miss is None:
+        raise L.VmpError('%s: want_fill needs miss (a complete row has nothing to fill)' % what)
+    x = L.dev_f32(x, 'x')
+    dev = x.device
+    pack = L.dev_f32(pack, 'pack', (K, 3 * D + 1))
+    if pack.device != dev:
+        raise L.VmpError('pack is on %s, x on %s' % (pack.device, dev))
+    mask = None if miss is None else _mask_u8(miss)
+    w = None if weights is None else weights.contiguous()
+    f32 = dict(dtype=torch.float32, device=dev)
+    r = torch.empty(N, K, **f32) if want_r else None
+    logr = torch.empty(N, K, **f32) if want_logr else None
+    fill = torch.empty(N, D, **f32) if want_fill else None
+    stats = torch.empty(K, 1 + 2 * D, dtype=torch.float64, device=dev) if want_stats else None
+    bound = torch.empty((), dtype=torch.float64, device=dev) if want_bound else None
+    nb = L.lib().vmp_mixture_diag_mfit_workspace_bytes(N, D, K)
+    ws = L.workspace(dev, nb)
+    L.check(L.lib().vmp_mixture_diag_mfit_pass(L.ptr(x), L.ptr(mask), L.ptr(w), N, D, K, L.ptr(pack), L.ptr(r), L.ptr(logr), L.ptr(fill),
+                                               L.ptr(stats), L.ptr(bound), L.ptr(ws), nb, L.stream()), 'vmp_mixture_diag_mfit_pass')
+    return r, logr, fill, stats, bound
+
+
+def _mfit_lower_bound(x, theta, prior, miss, weights):
+    what = 'lower_bound_diag'
+    N, D, K = _theta_dims(x, theta, what)
+    if miss is not None:
+        _miss_dims(miss, N, D, what)
+    if weights is not None:
+        from ._mix import _weights_dims
+        _weights_dims(x, weights, what)
+    if prior is not None:
+        _five(prior, K, D, what, '_0')
+    x = L.dev_f32(x, 'x')
+    if prior is None:
+        prior = default_diag_prior(x, K, miss=miss, weights=weights)
+    terms = diag_bound_terms(prior, theta)
+    data = mixture_diag_mfit_pass(x, diag_mfit_pack(*theta), miss=miss, weights=weights, want_r=False, want_stats=False, want_bound=True)[4]
+    return data - (terms[0] + terms[1])
+
+
+class DiagFitLoop(DiagLoop):
+    """DiagLoop on partly observed and / or weighted rows: miss (N,D), nonzero = missing, and weights (N,) fp32, finite, >= 0, not all
+    zero, both on x's device; at least one of the two.  The missing entries are latent variables with q(x_nd | z_n = k) = N(m_kd,
+    b_kd / a_k): the posterior keeps its shape, the M-step is the finalize of DiagLoop on the moments of the completed rows, the E-step
+    runs on the observed entries, and both stay exact coordinate ascent - lower_bound() never falls (csrc/vmp_diagmfit.hip, one
+    streaming pass per iteration).  Row n counts w_n times in the moments and in the bound; a weight does not enter a row's own
+    responsibilities, and a row of weight 0 reaches nothing the fit adds up, whatever it holds.  What a missing slot of x holds is
+    never read into arithmetic.  The surface is DiagLoop's (step, run, r, logr, stats, theta, aux, lower_bound, run_until_bound,
+    run_until, heldout, heldout_logprob, fill, predictive_pack) plus filled(): x with its missing entries replaced by sum_k r_nk m_kd.
+    The start: the moments of r_init * w on x with every missing entry (and every row of weight 0) replaced by its column's weighted
+    mean over the observed entries - linear in r, no variance term at the start - through the r_in form of mixture_diag_pass."""
+
+    def __init__(self, x, r_init, miss=None, weights=None, prior=None):
+        what = 'DiagFitLoop'
+        if miss is None and weights is None:
+            raise L.VmpError('DiagFitLoop: neither miss nor weights given - complete unweighted rows are fitted by DiagLoop')
+        N, D = _x_dims(x, what)
+        if not torch.is_tensor(r_init) or r_init.dim() != 2 or r_init.shape[0] != N:
+            raise L.VmpError('%s: r_init has shape %s, expected (%d,K)' % (what, tuple(r_init.shape) if torch.is_tensor(r_init) else type(r_init), N))
+        K = r_init.shape[1]
+        _check_dk(D, K)
+        if prior is not None:
+            _five(prior, K, D, what, '_0')
+        if miss is not None:
+            _miss_dims(miss, N, D, what)
+            if miss.device != x.device:
+                raise L.VmpError('%s: the missing-data mask is on %s, x on %s' % (what, miss.device, x.device))
+        if weights is not None:
+            from ._mix import check_weights
+            check_weights(x, weights)
+        self.x = L.dev_f32(x, 'x')
+        dev = self.x.device
+        r_init = L.dev_f32(r_init, 'r_init', (N, K))
+        self.N, self.D, self.K = N, D, K
+        self.miss = None if miss is None else _mask_u8(miss)
+        self.weights = None if weights is None else weights.contiguous()
+        mean, live = observed_column_means(self.x, self.miss, self.weights)
+        if prior is None:
+            prior = default_diag_prior(self.x, K, miss=self.miss, weights=self.weights)
+        self.prior = _dev5(prior, dev, '_0')
+        self.post = _post_buffers(K, D, dev)
+        self.pack = torch.zeros(K, 3 * D + 1, dtype=torch.float32, device=dev)
+        self._data = torch.zeros((), dtype=torch.float64, device=dev)
+        self._r = torch.empty(N, K, dtype=torch.float32, device=dev)
+        self._logr = None
+        self._fill = None if miss is None else torch.empty(N, D, dtype=torch.float32, device=dev)
+        self._r_ok = self._logr_ok = False
+        self.iterations = 0
+        # the moments of r_init * w on the mean-filled rows: the r_in form of the complete-row pass (its pack's values are not read)
+        x_start = torch.where(live, self.x, mean.to(torch.float32)[None, :])
+        r_start = r_init if self.weights is None else r_init * self.weights[:, None]
+        self._stats = mixture_diag_pass(x_start, torch.zeros(K, 2 * D + 1, dtype=torch.float32, device=dev), r_in=r_start, want_r=False)[2]
+
+    @classmethod
+    def from_centers(cls, x, centers, smooth=0.0, weights=None, prior=None, miss=None):
+        """start from the responsibilities of the nearest of `centers` (K,D) (nearest_center_r, unweighted); complete rows only"""
+        if miss is not None:
+            raise L.VmpError('DiagFitLoop.from_centers: nearest centres of masked wide rows are not built - pass an r_init')
+        return cls(x, nearest_center_r(x, centers, smooth), weights=weights, prior=prior)
+
+    @classmethod
+    def from_seed(cls, x, K, seed, weights=None, smooth=0.0, prior=None, miss=None):
+        """The weighted loop started from the data: the unweighted k-means++ centres of diag_seed_centers(x, K, seed) and their
+        nearest-centre responsibilities diag_seed_assign, then the constructor.  Seeding on masked wide rows is not built (a later
+        change): with miss= this refuses."""
+        if miss is not None:
+            raise L.VmpError('DiagFitLoop.from_seed: k-means++ seeding on masked wide rows is not built yet (a later pull request) - '
+                             'pass an r_init, or seed complete rows with weights=')
+        if weights is None:
+            raise L.VmpError('DiagFitLoop.from_seed: neither miss nor weights given - complete unweighted rows are seeded by DiagLoop.from_seed')
+        from ._mix import check_weights
+        check_weights(x, weights)                                            # before anything is seeded
+        centers, _, _ = diag_seed_centers(x, K, seed)
+        return cls(x, diag_seed_assign(x, centers, smooth)[0], weights=weights, prior=prior)
+
+    def _outputs(self, want_r, want_logr):
+        if want_logr and self._logr is None:
+            self._logr = torch.empty_like(self._r)
+        return (L.ptr(self._r if want_r else None), L.ptr(self._logr if want_logr else None),
+                L.ptr(self._fill if want_r else None))
+
+    def _iterate(self, iterations, want_r, want_logr):
+        r, logr, fill = self._outputs(want_r, want_logr)
+        nb = L.lib().vmp_mixture_diag_mfit_workspace_bytes(self.N, self.D, self.K)
+        ws = L.workspace(self.x.device, nb)
+        p = self.post
+        L.check(L.lib().vmp_mixture_diag_mfit_iterate(
+            L.ptr(self.x), L.ptr(self.miss), L.ptr(self.weights), self.N, self.D, self.K, *[L.ptr(t) for t in self.prior], r, logr, fill,
+            *[L.ptr(p[n]) for n in _POST], L.ptr(self.pack), L.ptr(self._stats), L.ptr(self._data), L.ptr(ws), nb, iterations,
+            L.stream()), 'vmp_mixture_diag_mfit_iterate')
+        self.iterations += iterations
+        self._r_ok, self._logr_ok = want_r, want_logr
+
+    def _refresh(self):
+        """r, log r and the fill of the current posterior by one pass under the current pack"""
+        self._need_iteration('r')
+        r, logr, fill = self._outputs(True, True)
+        nb = L.lib().vmp_mixture_diag_mfit_workspace_bytes(self.N, self.D, self.K)
+        ws = L.workspace(self.x.device, nb)
+        L.check(L.lib().vmp_mixture_diag_mfit_pass(L.ptr(self.x), L.ptr(self.miss), L.ptr(self.weights), self.N, self.D, self.K,
+                                                   L.ptr(self.pack), r, logr, fill, None, None, L.ptr(ws), nb, L.stream()),
+                'vmp_mixture_diag_mfit_pass')
+        self._r_ok = self._logr_ok = True
+
+    def filled(self):
+        """x with its missing entries replaced by sum_k r_nk m_kd under the current posterior (observed entries bit for bit); written
+        by the pass that writes r.  A fit without a mask has nothing to fill."""
+        if self.miss is None:
+            raise L.VmpError('DiagFitLoop.filled: the loop has no mask - nothing to fill')
+        if not self._r_ok:
+            self._refresh()
+        return self._fill

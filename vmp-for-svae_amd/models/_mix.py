@@ -1079,6 +1079,7 @@ class VMPLoop(object):
 
 
 # the diagonal-covariance mixture on wide rows (D up to 64) lives in models/_diag.py; its entry points are reachable from here as well
-from ._diag import (DiagLoop, default_diag_prior, diag_bound_terms, diag_finalize, diag_lower_bound, diag_pack,  # noqa: E402,F401
-                    diag_predictive_impute, diag_predictive_logprob, diag_score_pack, diag_seed_assign, diag_seed_centers,
-                    mixture_diag_pass, mixture_diag_score, nearest_center_r)
+from ._diag import (DiagFitLoop, DiagLoop, default_diag_prior, diag_bound_terms, diag_finalize, diag_lower_bound,  # noqa: E402,F401
+                    diag_mfit_pack, diag_pack, diag_predictive_impute, diag_predictive_logprob, diag_score_pack, diag_seed_assign,
+                    diag_seed_centers, mixture_diag_mfit_pass, mixture_diag_pass, mixture_diag_score, nearest_center_r,
+                    observed_column_means)

@@ -304,11 +304,57 @@ def inference_diag(x, K, seed, iterations=1, r_init=None, prior=None, init='rand
     return (step, _Handle(lambda: loop.logr), _Handle(loop.theta), _Handle(loop.aux))
 
 
-def lower_bound_diag(x, alpha_k, beta_k, m_k, a_k, b_k, prior=None):
+def _diag_fit_handles(loop):
+    def step():
+        return loop.step(want_logr=True)
+
+    def filled():
+        return loop.filled()
+
+    return (step, _Handle(lambda: loop.logr), _Handle(loop.theta), _Handle(loop.aux), _Handle(filled))
+
+
+def inference_diag_missing(x, miss, K, seed, r_init=None, prior=None):
+    """inference_diag() on partly observed rows: miss (N,D), nonzero = missing, on x's device; what the missing slots of x hold is
+    never read into arithmetic.  The missing entries are latent variables with a one-dimensional Gaussian q(x_nd | z_n) each, so the
+    posterior keeps its shape and every iteration is the finalize of inference_diag() on the moments of the completed rows and an
+    E-step on the observed entries, in one streaming HIP pass (csrc/vmp_diagmfit.hip; _mix.DiagFitLoop).  Returns (step, log_r_nk,
+    theta, (x_k, S_k, pi), x_filled): inference_diag()'s four and a handle for x with its missing entries replaced by sum_k r_nk
+    m_kd.  The start is a host-side Dirichlet(1) draw with `seed` unless r_init is given; k-means++ on masked wide rows is not built."""
+    if not torch.is_tensor(x) or x.dim() != 2:
+        raise L.VmpError('inference_diag_missing: x must be (N,D)')
+    if miss is None:
+        raise L.VmpError('inference_diag_missing: needs the missing-data mask (complete rows: inference_diag)')
+    loop = _mix.DiagFitLoop(x, _dirichlet_init(x.shape[0], K, seed, x.device) if r_init is None else r_init, miss=miss, prior=prior)
+    return _diag_fit_handles(loop)
+
+
+def inference_diag_weighted(x, weights, K, seed, miss=None, r_init=None, prior=None, init='random'):
+    """inference_diag() on weighted rows: weights (N,) fp32 on x's device, finite, >= 0, not all zero - row n counts as w_n identical
+    rows (binned counts, coresets, a 0/1 fold over the same resident x; a row of weight 0 reaches nothing the fit adds up, whatever
+    it holds).  A weight does not enter a row's own responsibilities.  miss (N,D) as in inference_diag_missing().  Returns (step,
+    log_r_nk, theta, (x_k, S_k, pi), x_filled); x_filled() is for a fit with a mask.  init='kmeans++' (no r_init, no mask): the
+    unweighted seeded start of _mix.DiagFitLoop.from_seed."""
+    _mix.check_init(init)
+    if not torch.is_tensor(x) or x.dim() != 2:
+        raise L.VmpError('inference_diag_weighted: x must be (N,D)')
+    if weights is None:
+        raise L.VmpError('inference_diag_weighted: needs the weights (unweighted rows: inference_diag / inference_diag_missing)')
+    if r_init is None and init == 'kmeans++':
+        loop = _mix.DiagFitLoop.from_seed(x, K, seed, weights=weights, prior=prior, miss=miss)
+    else:
+        loop = _mix.DiagFitLoop(x, _dirichlet_init(x.shape[0], K, seed, x.device) if r_init is None else r_init, miss=miss,
+                                weights=weights, prior=prior)
+    return _diag_fit_handles(loop)
+
+
+def lower_bound_diag(x, alpha_k, beta_k, m_k, a_k, b_k, prior=None, miss=None, weights=None):
     """The variational lower bound (nats) of the diagonal posterior that inference_diag()'s theta handle returns, on the rows of x:
     two K-sized launches and the bound-only form of the streaming pass.  Returns a 0-dim fp64 DEVICE tensor (deterministic; no host
-    synchronisation)."""
-    return _mix.diag_lower_bound(x, (alpha_k, beta_k, m_k, a_k, b_k), prior=prior)
+    synchronisation).  miss (N,D), nonzero = missing, and / or weights (N,) fp32 >= 0, for the theta of inference_diag_missing() /
+    inference_diag_weighted(): the bound those fits optimise (bound-only form of vmp_mixture_diag_mfit_pass); without them the call
+    is unchanged."""
+    return _mix.diag_lower_bound(x, (alpha_k, beta_k, m_k, a_k, b_k), prior=prior, miss=miss, weights=weights)
 
 
 def predictive_logprob_diag(x, alpha_k, beta_k, m_k, a_k, b_k, miss=None):
